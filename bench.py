@@ -15,6 +15,9 @@ torch.distributed.run it uses the ranks it is given.  The genome is replicated;
 and the 32-byte call records are all-gathered over RCCL inside the timed step.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md section "Measurement" for the byte accounting.
+A plain run sets up, warms up, times --steps steps and prints the headline; --full adds everything else the line can carry
+(per-kernel profile and roofline, the weak block of a strong run, the other copy-interval mode, the coarse block, the CPU
+baselines, the oracle re-check).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -147,7 +150,18 @@ def main():
     ap.add_argument("--no-modes", action="store_true", help="skip the block that re-runs the step in the other interval mode of the copy finder")
     ap.add_argument("--stage", choices=["fine", "coarse"], default="fine",
                     help="fine (default): BASELINE.json's metric; coarse: the companion line of stage 3.1 (all-vs-all seeding + FMEA)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel profile and roofline, the weak-scaling block of a strong run, the other "
+                         "copy-interval mode, the coarse block, the CPU baselines and the oracle re-check (--no-cpu-baseline, --no-coarse, "
+                         "--no-modes and --verify choose among them).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, a seeded sample "
+                         "where an output is large; 64 MB at most)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what the headline needs: none of the side blocks after the timed region
+        args.no_cpu_baseline = args.no_coarse = args.no_modes = True
+        args.verify = 0
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # one process per GPU: start the ranks ourselves (the driver may equally well launch us under torch.distributed.run)
@@ -278,7 +292,8 @@ def main():
         step()
     for _ in range(args.warmup):
         step()
-    ctx.profile(on=True, reset=True)
+    if args.full:
+        ctx.profile(on=True, reset=True)    # per-stage HIP events inside the timed steps: the `kernels` and `roofline` blocks
     ctx.align_stats(reset=True)
     torch.cuda.synchronize()
     if world > 1:
@@ -291,7 +306,7 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t1
-    prof = ctx.profile(on=False)
+    prof = ctx.profile(on=False) if args.full else {}
     align_stats = ctx.align_stats()
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -299,18 +314,21 @@ def main():
         elapsed = float(tt.item())
 
     calls = d_calls.cpu().numpy().view(CALL_DTYPE)[:n_cand].copy()
+    merged_calls = merged.cpu().numpy().view(CALL_DTYPE).copy() if world > 1 else None
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, fine_outputs(ctx, calls, d_cons, state["found"] if args.copies == "found" else None, merged_calls))
     n_te = int((calls["is_te"] != 0).sum())
     if world > 1:
         tn = torch.tensor([n_te], dtype=torch.int64, device=cdev)
         dist.all_reduce(tn)
         n_te_all = int(tn.item())
-        merged_te = int((merged.cpu().numpy().view(CALL_DTYPE)["is_te"] != 0).sum())
+        merged_te = int((merged_calls["is_te"] != 0).sum())
         assert merged_te == n_te_all, "all-gathered records disagree with the per-rank counts"
     else:
         n_te_all = n_te
 
     weak_blk = None
-    if strong:
+    if strong and args.full:
         # The WEAK form as a side block of a strong-scaling line: every rank judges the whole batch (per-GPU work fixed as N grows),
         # a few steps outside the headline's timed region, without the merge of the calls.  No collective sits inside the try
         # blocks: a rank that fails still reaches the barrier and the reductions below.
@@ -499,9 +517,10 @@ def main():
                        "is_te": n_te_all, "parallelism": "replicated genome, candidates %s x%d, all-gather of 32-B calls" %
                                                         ("sharded (length-balanced block-cyclic)" if strong else "per rank", world),
                        "setup_s": round(setup_s, 1)},
-            "roofline": roof,
-            "kernels": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in sorted(kern.items())},
         }
+        if args.full:
+            out["roofline"] = roof
+            out["kernels"] = {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in sorted(kern.items())}
         if weak_blk is not None:
             out["weak"] = weak_blk
         if hasattr(ctx.lib, "hite_debug_judge_clocks"):   # only in a -DJUDGE_CLOCKS development build
@@ -645,6 +664,67 @@ def verify(wv, calls, cons, count):
             "anchor_matches": dict(anchors, note="judged alignments of the sample by how the two 20-base anchors match their first common row: "
                                                  "'end' = an edit on the first / last base of a match, the only class where the real fuzzysearch "
                                                  "package could choose another start / end than the definition the goldens use (oracle/stubs.py)")}
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, so that two builds can be compared output for output
+# ---------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_ROWS = 150_000         # rows of a table beyond which a seeded sample of them is written
+DUMP_CONS_CANDIDATES = 2048     # candidates whose consensus bases are written
+DUMP_CONS_MAX_BASES = 8 << 20   # (float32 each)
+
+
+def _dump_pick(n, k, seed):
+    """all of 0 .. n-1, or a fixed seeded sample of k of them in increasing order"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def _calls_table(calls):
+    """call records -> float64 (records x 7), the columns in CALL_DTYPE's field order"""
+    return np.stack([calls[f].astype(np.float64) for f in calls.dtype.names], axis=1)
+
+
+def fine_outputs(ctx, calls, d_cons, found, merged_calls=None):
+    """the arrays a caller of the fine step receives: the call records of its candidates, the consensus bases of a seeded sample
+    of them and, when copy finding is part of the step (found = the device copy table), the copy records of the same sample;
+    merged_calls: the all-gathered records of every rank"""
+    n = len(calls)
+    out = {}
+    ids = _dump_pick(n, DUMP_MAX_ROWS, 1)
+    out["calls_candidates"], out["calls"] = ids.astype(np.float64), _calls_table(calls[ids])
+    pick = _dump_pick(n, DUMP_CONS_CANDIDATES, 2)
+    end = int((calls["cons_off"] + calls["cons_len"]).max()) if n else 0
+    pool = d_cons[:end].cpu().numpy()
+    parts = [pool[int(o):int(o) + int(k)] for o, k in zip(calls["cons_off"][pick], calls["cons_len"][pick])]
+    out["consensus_candidates"] = pick.astype(np.float64)
+    out["consensus_off"] = np.concatenate([[0], np.cumsum([len(p) for p in parts], dtype=np.int64)]).astype(np.float64)
+    out["consensus"] = np.concatenate(parts + [np.zeros(0, np.uint8)])[:DUMP_CONS_MAX_BASES].astype(np.float32)
+    if found is not None:
+        nc, p_cf, p_ct, p_s1, p_e1, p_mn, p_cl = found
+        cf = ctx.download(p_cf, n + 1, np.int32).astype(np.int64)
+        cols = [ctx.download(p_ct, nc, np.int32), ctx.download(p_s1, nc, np.int64), ctx.download(p_e1, nc, np.int64),
+                ctx.download(p_mn, nc, np.uint8), ctx.download(p_cl, nc, np.uint32) if p_cl else np.zeros(nc, np.uint32)]
+        rows = np.concatenate([np.arange(cf[c], cf[c + 1]) for c in pick] + [np.zeros(0, np.int64)])[:DUMP_MAX_ROWS]
+        out["copies_per_candidate"] = np.diff(cf)[ids].astype(np.float64)
+        out["copies"] = np.stack([c_[rows].astype(np.float64) for c_ in cols], axis=1)     # contig, start1, end1, minus, clip
+    if merged_calls is not None:
+        ids_all = _dump_pick(len(merged_calls), DUMP_MAX_ROWS, 3)
+        out["calls_all_candidates"], out["calls_all"] = ids_all.astype(np.float64), _calls_table(merged_calls[ids_all])
+    return out
+
+
+def write_outputs(path, arrays):
+    """name -> float32 / float64 array  ->  path/<name>.npy"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1070,6 +1150,8 @@ def c5_mode(args):
         # re-packs the context with the library and drops the copy index the table lives in
         calls = d_calls.cpu().numpy().view(CALL_DTYPE)[:n_cand].copy()
         cons_host = d_cons.cpu().numpy()
+        if args.dump_outputs:       # (the last genome's step: its calls, consensus sample and copy records)
+            write_outputs(args.dump_outputs, fine_outputs(ctx, calls, d_cons, state["found"]))
         wv = None
         if (world == 1 and not args.no_cpu_baseline) or args.verify > 0:
             wv = host_workload(w, ctx, state, 0, n_cand)
@@ -1200,8 +1282,8 @@ def coarse_stage(args):
 
     def step():
         ctx.copy_index_build(fresh=True)            # the index is part of the step here (rebuilt on the same handle, from the genome: no kept minimizer tiles)
-        (oc, _os, _oe), st = ctx.coarse_stage_dev(1_000_000, sc, so, 4000, 30000)   # the HSP table never leaves the device
-        return st, len(oc)
+        iv, st = ctx.coarse_stage_dev(1_000_000, sc, so, 4000, 30000)   # the HSP table never leaves the device
+        return st, iv
 
     # two untimed steps at least: the first grows the arenas of the index state, the second consolidates them into one block
     args.warmup = max(args.warmup, 2)
@@ -1212,15 +1294,21 @@ def coarse_stage(args):
         dist.barrier()
     t1 = time.perf_counter()
     for _ in range(args.steps):
-        stats, n_iv = step()
+        stats, iv = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t1
+    n_iv = len(iv[0])
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # the repeat intervals of the genome (chromosome, start, end), as the FMEA step hands them on
+        ids = _dump_pick(n_iv, DUMP_MAX_ROWS, 1)
+        write_outputs(args.dump_outputs, {"intervals_ids": ids.astype(np.float64),
+                                          "intervals": np.stack([a[ids].astype(np.float64) for a in iv], axis=1)})
     if rank == 0:
         ms = 1000.0 * elapsed / max(1, args.steps)
         out = {"metric": "coarse_boundary step (stage 3.1: all-vs-all seeding + FMEA) on the %s synthetic genome" % ("1 Gbp" if mbp == 1000 else "%d Mbp" % mbp),

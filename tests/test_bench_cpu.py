@@ -64,3 +64,71 @@ def test_bench_refuses_to_run_without_a_gpu():
     rc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0"],
                         capture_output=True, text=True)
     assert rc.returncode != 0 and "needs a GPU" in (rc.stdout + rc.stderr)
+
+
+def test_dumped_outputs_are_float_bounded_and_seeded(tmp_path):
+    """--dump-outputs on a batch above the size limit: float32 / float64 arrays only, 64 MB at most, the same seeded sample on every
+    call, and the consensus pieces and copy rows are those of the sampled candidates"""
+    import numpy as np
+    import pytest
+    import torch
+
+    import bench
+    from hite_amd._lib import CALL_DTYPE
+
+    rng = np.random.default_rng(5)
+    n = bench.DUMP_MAX_ROWS + 1000
+    calls = np.zeros(n, dtype=CALL_DTYPE)
+    calls["is_te"] = rng.random(n) < 0.6
+    calls["cons_len"] = np.where(calls["is_te"], rng.integers(50, 9000, n), 0)
+    calls["cons_off"] = np.concatenate([[0], np.cumsum(calls["cons_len"])[:-1]])
+    pool = rng.integers(65, 90, int(calls["cons_len"].sum()) + 64).astype(np.uint8)
+    n_copies = rng.integers(0, 4, n)
+    cf = np.concatenate([[0], np.cumsum(n_copies)]).astype(np.int32)
+    nc = int(cf[-1])
+    table = {1: cf, 2: rng.integers(0, 20, nc).astype(np.int32), 3: rng.integers(1, 10**9, nc), 4: rng.integers(1, 10**9, nc),
+             5: rng.integers(0, 2, nc).astype(np.uint8), 6: rng.integers(0, 2**20, nc).astype(np.uint32)}
+
+    class FakeCtx:
+        def download(self, ptr, count, dtype):
+            a = table[ptr]
+            assert a.dtype == np.dtype(dtype) and len(a) == count
+            return a.copy()
+
+    merged = calls[::-1].copy()
+    got = [bench.fine_outputs(FakeCtx(), calls, torch.from_numpy(pool), (nc, 1, 2, 3, 4, 5, 6), merged) for _ in range(2)]
+    assert set(got[0]) == set(got[1]) and all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+    a = got[0]
+    ids = a["calls_candidates"].astype(np.int64)
+    assert len(ids) == bench.DUMP_MAX_ROWS and np.all(np.diff(ids) > 0)
+    assert np.array_equal(a["calls"][:, 5], calls["cons_len"][ids]) and np.array_equal(a["calls"][:, 6], calls["cons_off"][ids])
+    assert np.array_equal(a["copies_per_candidate"], n_copies[ids])
+    pick = a["consensus_candidates"].astype(np.int64)
+    assert len(pick) == bench.DUMP_CONS_CANDIDATES
+    off = a["consensus_off"].astype(np.int64)
+    for j in (0, 7, len(pick) - 1):
+        c = pick[j]
+        want = pool[calls["cons_off"][c]:calls["cons_off"][c] + calls["cons_len"][c]]
+        if off[j + 1] <= bench.DUMP_CONS_MAX_BASES:
+            assert np.array_equal(a["consensus"][off[j]:off[j + 1]], want.astype(np.float32))
+    assert len(a["consensus"]) == min(off[-1], bench.DUMP_CONS_MAX_BASES)
+    rows = np.concatenate([np.arange(cf[c], cf[c + 1]) for c in pick])
+    assert np.array_equal(a["copies"][:, 1], table[3][rows]) and np.array_equal(a["copies"][:, 4], table[6][rows])
+    assert a["calls_all"].shape == (bench.DUMP_MAX_ROWS, 7)
+
+    bench.write_outputs(str(tmp_path / "d"), a)
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == sorted(k + ".npy" for k in a)
+    back = {f[:-4]: np.load(tmp_path / "d" / f) for f in files}
+    assert all(b.dtype in (np.float32, np.float64) and np.array_equal(b, a[k]) for k, b in back.items())
+    assert sum(b.nbytes for b in back.values()) <= bench.DUMP_MAX_BYTES
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1)})
+
+
+def test_bench_options():
+    """--full and --dump-outputs are options of the bench"""
+    import subprocess
+
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

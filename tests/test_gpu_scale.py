@@ -509,7 +509,7 @@ def test_bench_strong_scaling_line_two_ranks_functional():
 
     env = dict(os.environ)
     env["HITE_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "1", "--warmup", "0", "--full",
            "--no-cpu-baseline", "--no-coarse", "--no-modes", "--verify", "16"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -538,11 +538,42 @@ def _bench_two_ranks(extra, timeout=900):
     return d
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline alone; --dump-outputs writes the last timed step's outputs as float arrays, and
+    two runs with the same arguments write the same arrays"""
+    import json
+    import subprocess
+
+    side = {"roofline", "kernels", "weak", "copy_interval_modes", "coarse", "cpu_baseline", "verify"}
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C2", "--genome-mbp", "20", "--steps", "2",
+               "--warmup", "1", "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "candidates/s"
+        assert not side & set(d), sorted(side & set(d))
+        arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert {"calls", "calls_candidates", "consensus", "consensus_off", "consensus_candidates", "copies", "copies_per_candidate"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        n = d["config"]["candidates_per_gpu"]
+        assert arrays["calls"].shape == (n, 7) and int((arrays["calls"][:, 0] != 0).sum()) == d["config"]["is_te"]
+        assert arrays["copies_per_candidate"].sum() == d["config"]["copies"]
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
 def test_bench_c5_line_two_ranks_functional():
     """config C5 as a node runs it -- one population genome per rank, the per-rank libraries all-gathered (padded consensus pools +
     lengths) and merged on rank 0 -- with two ranks sharing this GPU over gloo: the line is printed, both genomes' libraries reach
     the merge, and the re-judged sample of rank 0 has no mismatch (genomes of 30 Mbp: a functional run)"""
-    d = _bench_two_ranks(["--config", "C5", "--genome-mbp", "30", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--verify", "16"])
+    d = _bench_two_ranks(["--config", "C5", "--genome-mbp", "30", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--verify", "16"])
     cfg = d["config"]
     assert d["scaling"] == "weak" and cfg["genomes"] == 2 and cfg["library_sequences_in"] > 600
     assert 0 < cfg["library_sequences_final"] < cfg["library_sequences_in"]

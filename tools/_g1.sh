@@ -1,4 +1,4 @@
-F="--no-cpu-baseline --no-coarse --no-modes --verify 0 --steps 10 --warmup 2"
+F="--full --no-cpu-baseline --no-coarse --no-modes --verify 0 --steps 10 --warmup 2"
 for WC in 2544 2300 2000 1700 1400; do
   HITE_JUDGE_WAVE_COLS=$WC python bench.py --config C3 $F > gpurun_out/w_$WC.json 2>/dev/null
   python - $WC <<'PY'

@@ -7,8 +7,8 @@ TAG=${1:-r05}
 OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python bench.py --stage coarse --steps 2 --warmup 2 --no-cpu-baseline"
-timeout 900 python bench.py --stage coarse --steps 3 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_coarse.json 2> $OUT/${TAG}_bench_coarse.err
+BENCH="python bench.py --full --stage coarse --steps 2 --warmup 2 --no-cpu-baseline"
+timeout 900 python bench.py --full --stage coarse --steps 3 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_coarse.json 2> $OUT/${TAG}_bench_coarse.err
 rm -rf $OUT/cprof_stats $OUT/cprof_fetch $OUT/cprof_write
 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/cprof_stats -o run -- $BENCH > $OUT/cprof_stats.json 2> $OUT/cprof_stats.log
 if [ "${2:-}" != "nopmc" ]; then
