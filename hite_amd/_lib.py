@@ -53,6 +53,16 @@ def _arr(x, dtype):
     return np.ascontiguousarray(x, dtype=dtype)
 
 
+def seed_sub_shard(rank, world, s, S):
+    """sub-share s of S of the share (rank, world) of the all-vs-all stage (world <= 1: of the whole stage), as the (rank, world)
+    pair hite_seed_shard takes.  hite_seed_shard puts the lower edge of rank k at mass 2.0 * k / world in binary64; k / world and
+    k S / (world S) are the same rational, so their correctly rounded quotients are the same double and every edge of `world` is an
+    edge of world S: the sub-shares rank S .. rank S + S - 1 tile the share exactly, on the device and in the twin."""
+    if world <= 1:
+        rank, world = 0, 1
+    return rank * S + s, world * S
+
+
 class Context:
     """One per process/GPU.  Owns the resident 2-bit genome and device scratch."""
 
@@ -699,6 +709,7 @@ class Context:
     def seed_shard(self, rank, world):
         """the seeding calls of this context compute rank's share of `world` (hite_seed_shard); world <= 1: everything"""
         self._check(self.lib.hite_seed_shard(self.h, int(rank), int(world)), "hite_seed_shard")
+        self._seed_shard = (int(rank), int(world)) if int(world) > 1 else (0, 0)
 
     def _seed_allvsall_once(self, seg_len, max_anchors, cap):
         """one hite_seed_allvsall call -> (table or None, anchors): None when the call's anchors exceed what one call sorts"""
@@ -729,29 +740,32 @@ class Context:
         A search with more anchors than one call sorts (the merged library of eight population genomes: dozens of near-identical
         sequences per family, 5 x 10^9 anchors) runs in SHARES, one after the other -- the (strand, diagonal) ranges of hite_seed_shard,
         whose union, put in share order and sorted stably by (query segment, subject segment), is the whole table record for record
-        (what hite_amd.dist does across ranks)."""
+        (what hite_amd.dist does across ranks).
+        A context that is itself a rank's shard (seed_shard(r, W)) splits ITS share (seed_sub_shard: rank r S + s of world W S) and
+        is the shard (r, W) again afterwards."""
         tab, anchors = self._seed_allvsall_once(seg_len, max_anchors, cap)
         if tab is not None:
             return tab
+        rank0, world0 = getattr(self, "_seed_shard", (0, 0))
         world = 2
         while world * max_anchors < 2 * anchors:
             world *= 2
         while True:
+            if max(world0, 1) * world > 256:
+                raise HiteError("hite_seed_allvsall: %d anchors do not fit %d shares" % (anchors, max(world0, 1) * world // 2))
             parts = []
             try:
-                for r in range(world):
-                    self.seed_shard(r, world)
+                for s in range(world):
+                    self.seed_shard(*seed_sub_shard(rank0, world0, s, world))
                     t, _a = self._seed_allvsall_once(seg_len, max_anchors, cap)
                     if t is None:
                         break
                     parts.append(t)
             finally:
-                self.seed_shard(0, 0)
+                self.seed_shard(rank0, world0)
             if len(parts) == world:
                 break
             world *= 2
-            if world > 256:
-                raise HiteError("hite_seed_allvsall: %d anchors do not fit %d shares" % (anchors, world // 2))
         cat = {k: np.concatenate([t[k] for t in parts]) for k in ("qseg", "sseg", "qs", "qe", "ss", "se")}
         order = np.lexsort((cat["sseg"], cat["qseg"]))          # (stable: equal keys stay in share order)
         out = {k: v[order] for k, v in cat.items()}

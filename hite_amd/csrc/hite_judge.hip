@@ -31,12 +31,15 @@
 #define TILE_COLS 160   // widest column span staged in LDS for the window scans (wider spans read the alignment directly): the workgroup form
 // the wavefront form: a workgroup (= one wavefront) holds 3.7 KB + its tile, and 16 of them fit a CU's 160 KB only when the tile has
 // <= 6.5 KB.  Measured in round 6 (-DJWAV_TILE_COLS, profiles/r06_judge_split.txt): 112 / 128 / 160 columns (9.4 / 9.9 / 11.4 KB per
-// wavefront; the anchor text + match records of <= 1784 / 2040 / 2544 columns fit the same bytes) give 12.1 / 11.8 / 11.9 ms of judges
+// wavefront; the anchor text + match records of <= 1784 / 2040 / 2552 columns fit the same bytes) give 12.1 / 11.8 / 11.9 ms of judges
 // per C3 step: the fourth wavefront per SIMD buys nothing, 160 stays
 #ifndef JWAV_TILE_COLS
 #define JWAV_TILE_COLS 160
 #endif
 #define JWAV_ANCHOR_COLS ((JWAV_TILE_COLS * 6 * 2 * 4 - 16) / 3 / 8 * 8)
+// the wave form's mask tile (JT_TILE_COLS * 6 * JT_W32 * 4 bytes with JT_W32 = 2) holds the ungapped row, 16 bytes of slack and
+// 2 bytes of match record per text start: 2552 columns at the default tile
+static_assert(3 * JWAV_ANCHOR_COLS + 16 <= JWAV_TILE_COLS * 6 * 2 * 4, "anchor text + match records overrun the wave mask tile");
 
 #ifdef JUDGE_CLOCKS
 // development aid (-DJUDGE_CLOCKS): wall-clock ticks per phase, summed over blocks by thread 0
@@ -81,6 +84,7 @@ typedef __attribute__((address_space(3))) jt_u32x4 *jt_lptr16;
 #define JT_W32 4
 #define JT_TILE_COLS TILE_COLS
 #define ANCHOR_LDS_COLS 5104   // ungapped row (<= this many bytes) + 2 bytes of match record per text start fit the 15 KB mask area
+static_assert(ANCHOR_LDS_COLS + 16 + 2 * ANCHOR_LDS_COLS <= JT_TILE_COLS * 6 * JT_W32 * 4, "anchor text + match records overrun the workgroup mask tile");
 #define JT_KERNEL judge_kernel
 #define JT_MSA_PTR jt_gptr
 // minimum waves per SIMD asked of the compiler (it spills to get there).  Measured on C3, workgroup / wave kernel: 5/4 11.3 ms,
@@ -546,7 +550,7 @@ static int env_int(const char *name, int dflt) {
 static JudgeLimits judge_limits(int n) {
     JudgeLimits L;
     // HITE_JUDGE_WAVE_COLS = 0 sends every alignment to the workgroup kernels; the wave kernels' LDS holds the anchor text of
-    // <= JWAV_ANCHOR_COLS (2040) columns, wider alignments would search their anchors in global scratch
+    // <= JWAV_ANCHOR_COLS (2552) columns, wider alignments would search their anchors in global scratch
     L.wcols = env_int("HITE_JUDGE_WAVE_COLS", JWAV_ANCHOR_COLS); L.wrows = env_int("HITE_JUDGE_WAVE_ROWS", 64);
     if (L.wrows > 64) L.wrows = 64;
     if (L.wcols < 0 || L.wrows <= 0) L.wcols = 0;

@@ -205,14 +205,14 @@ def test_judge_golden_kernel_forms(ctx, name, te_type, mode, monkeypatch):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     cases = load_golden(name)
-    if mode == "wave_wide":   # a wide alignment with few rows: above the LDS anchor limit of the wave kernel (2544 columns)
+    if mode == "wave_wide":   # a wide alignment with few rows: above the LDS anchor limit of the wave kernel (2552 columns)
         c = casegen.make_msa_case(seed=4242, te_type=te_type, rows=9, te_len=3300, div=0.04, ins_cols=4, trunc_rows=1, tsd_len=8, tsd_frac=1.0)
         m = O.msa_array(c["seqs"])
         keep = O.sparse_cols(m).astype(bool)
         mc = np.ascontiguousarray(m[:, keep])
         exp, _ = O.judge(te_type, mc, c["cand"], 1)
         g = ctx.judge(te_type, [mc], [c["cand"]], plant=1)[0]
-        assert [g[0], g[1], g[2], g[3]] == exp and mc.shape[1] > 2544
+        assert [g[0], g[1], g[2], g[3]] == exp and mc.shape[1] > 2552
     for plant in (0, 1):
         sub = [c for c in cases if c["plant"] == plant]
         if not sub:
@@ -224,6 +224,99 @@ def test_judge_golden_kernel_forms(ctx, name, te_type, mode, monkeypatch):
                 assert g[1] == "EXC", (i, g, exp)
             else:
                 assert [g[0], g[1], g[2], g[3]] == exp, (i, g, exp)
+
+
+# the widest alignment whose ungapped anchor text + match records a judge kernel keeps in its LDS mask tile (hite_judge.hip):
+WAVE_ANCHOR_LDS_COLS = 2552      # JWAV_ANCHOR_COLS at JWAV_TILE_COLS = 160: the wavefront form (jwav), and the default HITE_JUDGE_WAVE_COLS
+BLOCK_ANCHOR_LDS_COLS = 5104     # ANCHOR_LDS_COLS of the workgroup form (jblk)
+
+
+@pytest.fixture(scope="module")
+def anchor_limit_cases():
+    """the alignments of test_judge_at_anchor_lds_limits with the oracle's calls: built once, shared by the kernel forms, never changed"""
+    import judge_limit_cases as JL
+
+    cases = JL.build(WAVE_ANCHOR_LDS_COLS, BLOCK_ANCHOR_LDS_COLS)
+    JL.check_conditions(cases)
+    assert sorted({c["C"] for c in cases}) == [2536, 2544, 2551, 2552, 2553, 2560, 2568, 5088, 5103, 5104, 5105, 5120]
+    assert sorted({c["rows"] for c in cases}) == [9, 64, 65] and len(cases) == 3 * 36
+    print("alignments the oracle calls TE, by type and width:", JL.te_counts(cases))
+    return cases, JL.build_repetitive(WAVE_ANCHOR_LDS_COLS, BLOCK_ANCHOR_LDS_COLS)
+
+
+def _assert_call(g, exp, bounds, what):
+    if exp[0] == "EXC":
+        assert g[1] == "EXC", (what, g, exp)
+        return
+    assert [g[0], g[1], g[2], g[3]] == exp, (what, g[:2], g[3:], exp[:2], exp[3:])
+    if exp[0]:
+        assert (g[4], g[5]) == tuple(bounds), (what, g[4:], bounds)
+
+
+@pytest.mark.parametrize("mode", ["wave_default", "wave_wide", "block_only", "wave_two_kernels", "block_two_kernels"])
+def test_judge_at_anchor_lds_limits(ctx, anchor_limit_cases, mode, monkeypatch):
+    """Alignments of exactly 2536 .. 2568 and 5088 .. 5120 columns x 9 / 64 / 65 rows, all three TE types, against the oracle: the
+    widths either side of the two limits up to which a judge kernel keeps the ungapped anchor text and the match records in its LDS
+    mask tile (above: global scratch), and the row counts either side of the wavefront class.  An off-by-one at a limit overruns
+    one LDS region into its neighbour without a fault -- only a wrong call shows it.  Every alignment has a row without gaps (text
+    of C bytes); per type at least a third are TE calls, and candidates that reach to 8 columns from either edge put the anchors
+    into the first / last text starts.  Each alignment alone with plant 0 and 1, then all of a type as ONE batch between ~30 narrow
+    goldens (both classes in the work lists, neighbours for an overrun to damage).  A second group has tandem arrays of the
+    candidate's ends inside the element, which sends the anchor search through the form that uses the match records."""
+    env = {"wave_default": {"HITE_JUDGE_WAVE_MIN_BATCH": "0", "HITE_JUDGE_LDS": "0"},
+           "wave_wide": {"HITE_JUDGE_WAVE_COLS": "60000", "HITE_JUDGE_OVERLAP": "0", "HITE_JUDGE_WAVE_MIN_BATCH": "0", "HITE_JUDGE_LDS": "0"},
+           "block_only": {"HITE_JUDGE_WAVE_COLS": "0", "HITE_JUDGE_LDS": "0"},
+           "wave_two_kernels": {"HITE_JUDGE_WAVE_MIN_BATCH": "0", "HITE_JUDGE_LDS": "0", "HITE_JUDGE_SPLIT": "3"},
+           "block_two_kernels": {"HITE_JUDGE_WAVE_COLS": "0", "HITE_JUDGE_LDS": "0", "HITE_JUDGE_SPLIT": "3"}}[mode]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    limit_cases, repetitive = anchor_limit_cases
+    if mode == "wave_default":
+        # the class border itself (hite_judge_classify_dev, as hite_judge_dev splits a batch): 64 rows x 2552 columns is the last
+        # alignment of the wavefront class (JUDGE_CLS_WAVE = 1), one more row or column goes to the workgroup (JUDGE_CLS_BLOCK = 0)
+        import ctypes as C
+
+        import torch
+
+        dev = torch.device("cuda", 0)
+        d_rows = torch.tensor([9, 9, 64, 64, 65, 1], dtype=torch.int32).to(dev)
+        d_cols = torch.tensor([WAVE_ANCHOR_LDS_COLS, WAVE_ANCHOR_LDS_COLS + 1, WAVE_ANCHOR_LDS_COLS, WAVE_ANCHOR_LDS_COLS + 1, WAVE_ANCHOR_LDS_COLS, 1],
+                              dtype=torch.int32).to(dev)
+        d_cls = torch.full((6,), 255, dtype=torch.uint8).to(dev)
+        torch.cuda.synchronize()
+        rc = ctx.lib.hite_judge_classify_dev(ctx.h, 6, C.c_void_p(d_rows.data_ptr()), C.c_void_p(d_cols.data_ptr()), C.c_void_p(d_cls.data_ptr()), None)
+        assert rc == 0
+        assert ctx.download(d_cls.data_ptr(), 6, np.uint8).tolist() == [1, 0, 1, 0, 0, 1]
+    n_alone = n_batch = 0
+    for name, te_type in (("judge_tir", "tir"), ("judge_non_ltr", "non_ltr"), ("judge_helitron", "helitron")):
+        sub = [c for c in limit_cases + repetitive if c["te_type"] == te_type]
+        for plant in (0, 1):
+            for c in sub:
+                g = ctx.judge(te_type, [c["mc"]], [c["cand"]], plant=plant)[0]
+                _assert_call(g, *c["exp"][plant], (mode, te_type, c["rows"], c["C"], plant, "alone"))
+                n_alone += 1
+        golden = [c for c in load_golden(name) if c["clean"] and len(c["clean"][0]) > 0]
+        n_gold = 0
+        for plant in (0, 1):
+            gold = [c for c in golden if c["plant"] == plant][:30]
+            n_gold += len(gold)
+            # interleaved: a golden after every boundary alignment while they last
+            order = []
+            for i in range(max(len(sub), len(gold))):
+                order += [("limit", sub[i])] if i < len(sub) else []
+                order += [("golden", gold[i])] if i < len(gold) else []
+            msas = [c["mc"] if kind == "limit" else O.msa_array(c["clean"]) for kind, c in order]
+            got = ctx.judge(te_type, msas, [c["cand"] for _k, c in order], plant=plant)
+            for i, ((kind, c), g) in enumerate(zip(order, got)):
+                if kind == "limit":
+                    _assert_call(g, *c["exp"][plant], (mode, te_type, c["rows"], c["C"], plant, "batch", i))
+                elif c["expected"][0] == "EXC":
+                    assert g[1] == "EXC", (mode, te_type, plant, i, g, c["expected"])
+                else:
+                    assert [g[0], g[1], g[2], g[3]] == c["expected"], (mode, te_type, plant, "golden in the batch", i, g, c["expected"])
+                n_batch += 1
+        assert n_gold >= 25, (name, n_gold)
+    assert n_alone == 2 * (len(limit_cases) + len(repetitive)) and n_batch > n_alone
 
 
 @pytest.mark.parametrize("te_type", ["tir", "non_ltr", "helitron"])
@@ -977,6 +1070,92 @@ def test_reference_tuples_clip_probe_vs_twin(ctx):
     print("reference tuples: %d records, %d with a clip, estimate within 3 bases of the finder's at both ends for %d; TE calls %d (with the finder's words: %d) of %d"
           % (n_rec, n_nonzero, n_near, n_te, sum(r[0] for r in res6), len(res)))
     assert n_te >= 0.9 * sum(r[0] for r in res6)
+
+
+def test_clip_probe_on_a_whole_candidate_table(ctx):
+    """hite_copy_config(0): the records carry the whole candidate, so nothing was clipped -- and a table passed WITHOUT clip words
+    (the finder's 5-tuples on the host, the finder's device table with no clip pointer) still goes through clip_probe_kernel on
+    every call.  Pinned here: the probed words are orc_clip_probe's, record for record; the stage's calls on the probed table are
+    the twin chain's, and equal those of the same table with an explicit zero-filled clip array, on the host and on the device.
+    The probe does NOT answer 0|0 throughout: on this genome (the neighbouring test's) the twin estimates a clip for 44 of 345
+    records (12.8 %; one base at one end for 42 of them), which here leaves all 16 calls as they are with zeros -- the twin chain
+    says so before the device is asked.  It is not harmless everywhere: on synth_small.make(23, n_fam=24) the twin chain builds
+    one of 12 consensi two bases shorter from the probed words (65 of 396 non-zero) than from zeros; there the calls are held
+    to the twin's for each form, not to each other."""
+    import oracle_pipeline as OP
+    import synth_small
+    import torch
+    from hite_amd._lib import CALL_DTYPE
+
+    def words_of_twin(g, tab):
+        out = []
+        for cand, cps in zip(g["cands"], tab):
+            ws = []
+            for t in cps:
+                pr = O.clip_probe(cand, OP._interval(g["contigs"][t[0]], t[1], t[2], t[3]))
+                ws.append(((pr >> 16) | ((pr & 0xffff) << 16)) if t[3] else pr)
+            out.append(ws)
+        return out
+
+    dev = torch.device("cuda", 0)
+    try:
+        ctx.copy_config(False)
+        O.find_copies_config(False)
+        for seed, n_fam, harmless in ((29, 20, True), (23, 24, False)):
+            g = synth_small.make(seed, n_fam=n_fam)
+            ctx.genome_pack(g["contigs"])
+            ctx.release_copy_index()
+            whole = ctx.find_copies(g["cands"], clips=True)
+            assert whole == O.find_copies(g["contigs"], g["cands"], clips=True)
+            assert all(cp[5] == 0 for t in whole for cp in t) and sum(len(t) for t in whole) > 300
+            ref5 = [[(t[0], t[1], t[2], t[3], t[2] - t[1] + 1) for t in cp] for cp in whole]
+            zero6 = [[t[:5] + (0,) for t in cp] for cp in whole]
+            exp_words = words_of_twin(g, ref5)
+            assert ctx.clip_probe(g["cands"], ref5) == exp_words
+            flat = [w for ws in exp_words for w in ws]
+            n_nonzero = sum(w != 0 for w in flat)
+            print("whole-candidate table, seed %d: the probe estimates a clip for %d of %d records" % (seed, n_nonzero, len(flat)))
+            assert 0 < n_nonzero < 0.2 * len(flat)           # (the twin does not say 0|0 throughout: equality with the twin is the contract)
+            exp5 = [OP.fine_stage_candidate("tir", cand, cp, g["contigs"], plant=1) for cand, cp in zip(g["cands"], ref5)]
+            exp0 = [OP.fine_stage_candidate("tir", cand, cp, g["contigs"], plant=1) for cand, cp in zip(g["cands"], zero6)]
+            assert (exp5 == exp0) == harmless, (seed, sum(a != b for a, b in zip(exp5, exp0)))
+            res5, _ = ctx.flank_region_align("tir", g["cands"], ref5, plant=1)
+            res0, _ = ctx.flank_region_align("tir", g["cands"], zero6, plant=1)
+            assert [[r[0], r[1], r[2], r[3]] for r in res5] == exp5
+            assert [[r[0], r[1], r[2], r[3]] for r in res0] == exp0
+            if harmless:
+                assert res5 == res0 and sum(r[0] for r in res5) >= 5
+            # the device table: no clip pointer (probed) against a zero-filled clip array
+            cb = [c.encode() for c in g["cands"]]
+            off = np.zeros(len(cb) + 1, dtype=np.int64)
+            np.cumsum([len(c) for c in cb], out=off[1:])
+            d_cand = torch.from_numpy(np.frombuffer(b"".join(cb) + b"\0" * 64, dtype=np.uint8).copy()).to(dev)
+            d_off = torch.from_numpy(off).to(dev)
+            n, nbytes = len(cb), int(off[-1])
+            cap = nbytes + 200 * n + 4096
+            ctx.copy_index_build()
+            outs = []
+            for form in ("probed", "zeros"):
+                d_calls = torch.zeros(n * 32, dtype=torch.uint8, device=dev)
+                d_cons = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+                nc, p_cf, p_ct, p_s1, p_e1, p_mn, _an = ctx.find_copies_dev(n, d_cand.data_ptr(), d_off.data_ptr(), nbytes)
+                assert nc == len(flat)
+                d_zero = torch.zeros(nc + 16, dtype=torch.int32, device=dev)
+                torch.cuda.synchronize()
+                ctx.flank_region_align_dev("tir", 1, n, d_cand.data_ptr(), d_off.data_ptr(), p_cf, nc, p_ct, p_s1, p_e1, p_mn, 50, d_calls.data_ptr(),
+                                           d_cons.data_ptr(), cap, d_clip=d_zero.data_ptr() if form == "zeros" else 0)
+                torch.cuda.synchronize()
+                calls = ctx.download(d_calls.data_ptr(), n * 32, np.uint8).view(CALL_DTYPE)
+                cons = ctx.download(d_cons.data_ptr(), cap, np.uint8)
+                outs.append([[bool(c["is_te"]), cons[c["cons_off"]:c["cons_off"] + c["cons_len"]].tobytes().decode() if c["is_te"] else "", int(c["row_num"])]
+                             for c in calls])
+            assert outs[0] == [[e[0], e[2], e[3]] for e in exp5], seed
+            assert outs[1] == [[e[0], e[2], e[3]] for e in exp0], seed
+            if harmless:
+                assert outs[0] == outs[1]
+    finally:
+        ctx.copy_config(None)
+        O.find_copies_config(None)
 
 
 def test_aligned_interval_mode_through_the_host_mirror(ctx, tmp_path):
@@ -1886,6 +2065,48 @@ def test_seed_shard_partitions_the_hsp_table(ctx):
     assert auto.get("shares", 1) >= 4 and auto["stats"][1] == anchors
     for k in keys:
         assert np.array_equal(auto[k], whole[k]), k
+
+
+def test_sharded_context_keeps_its_shard_through_the_auto_split(ctx):
+    """a context that is rank r of 3 (what hite_amd.dist.coarse_stage_sharded sets before it seeds) and whose share has more anchors
+    than one call sorts: Context.seed_allvsall splits THAT share (sub-share s of S = rank r S + s of world 3 S) -- the table is the
+    rank's share and the twin's, record for record, the anchors are the share's, the context is rank r of 3 afterwards, and the
+    three tables together are the unsharded one.  (Before, the split returned the whole table and left the context unsharded.)"""
+    import synth_small
+    from oracle_ctx import OracleCtx
+
+    g = synth_small.make(31, n_fam=14, n_chr=3, chr_len=150_000)
+    ctx.genome_pack(g["contigs"])
+    ctx.release_copy_index()
+    keys = ("qseg", "sseg", "qs", "qe", "ss", "se")
+    whole = ctx.seed_allvsall(seg_len=50_000)
+    tw = OracleCtx()
+    tw.genome_pack(g["contigs"])
+    parts = []
+    try:
+        for r in range(3):
+            ctx.seed_shard(r, 3)
+            tw.seed_shard(r, 3)
+            share = ctx.seed_allvsall(seg_len=50_000)
+            twin = tw.seed_allvsall(seg_len=50_000)
+            auto = ctx.seed_allvsall(seg_len=50_000, max_anchors=share["stats"][1] // 3)
+            assert auto.get("shares", 1) >= 2 and auto["stats"][1] == share["stats"][1], (r, auto.get("shares"), auto["stats"], share["stats"])
+            for k in keys:
+                assert np.array_equal(auto[k], share[k]), (r, k, len(auto[k]), len(share[k]))
+                assert np.array_equal(auto[k], twin[k]), (r, k)
+            assert 0 < len(auto["qseg"]) < len(whole["qseg"])
+            again = ctx.seed_allvsall(seg_len=50_000)          # the shard survived the split
+            for k in keys:
+                assert np.array_equal(again[k], share[k]), (r, k, len(again[k]), len(share[k]))
+            parts.append(np.stack([np.asarray(auto[k], dtype=np.int64) for k in keys], axis=1))
+    finally:
+        ctx.seed_shard(0, 0)
+    rows = np.concatenate(parts)
+    rows = rows[np.argsort(rows[:, 0] * 100000 + rows[:, 1], kind="stable")]
+    for i, k in enumerate(keys):
+        assert np.array_equal(rows[:, i], np.asarray(whole[k], dtype=np.int64)), k
+    again = ctx.seed_allvsall(seg_len=50_000)
+    assert all(np.array_equal(again[k], whole[k]) for k in keys)
 
 
 def test_coarse_stage_sharded_over_rccl_world1(ctx):

@@ -672,3 +672,131 @@ def test_twin_padded_rows_and_the_aligned_interval_mode():
     te = lambda table: sum(bool(OP.fine_stage_candidate("tir", c, t, g["contigs"], plant=1)[0]) for c, t in zip(g["cands"], table))  # noqa: E731
     n_pad, n_bare, n_whole = te(tab), te([[cp[:4] for cp in t] for t in tab]), te(whole)
     assert n_pad >= n_bare and n_pad >= 0.9 * n_whole, (n_pad, n_bare, n_whole)
+
+
+def _twin_share(tw, rank, world, seg_len):
+    tw.seed_shard(rank, world)
+    try:
+        t = tw.seed_allvsall(seg_len=seg_len)
+    finally:
+        tw.seed_shard(0, 0)
+    return np.stack([np.asarray(t[k], dtype=np.int64) for k in ("qseg", "sseg", "qs", "qe", "ss", "se")], axis=1)
+
+
+def _shard_edge(G, k, world):
+    """seed_shard_edge (hite_copies.hip / hite_oracle_copies.c) restated: only to say which sub-shares are EMPTY"""
+    import math
+
+    if k <= 0:
+        return 0
+    if k >= world:
+        return 4 * G + 64
+    mass = 2.0 * k / world
+    strand = 1 if mass >= 1.0 else 0
+    t = mass - strand
+    d = G * math.sqrt(2.0 * t) if t <= 0.5 else 2.0 * G - G * math.sqrt(2.0 * (1.0 - t))
+    return (2 * G if strand else 0) + (int(max(d, 0.0)) & ~63)
+
+
+def test_sub_shards_tile_a_ranks_share():
+    """hite_amd._lib.seed_sub_shard, the composition Context.seed_allvsall uses when a context that is rank r of W has to split its
+    share in S: the twin's share (r, W) is the twin's shares seed_sub_shard(r, W, s, S), s = 0 .. S - 1, concatenated in that order
+    and sorted stably by (query segment, subject segment) -- record for record, for S that are no power of two as well; on a
+    genome of 800 bases 40 sub-shares have neighbouring edges on the same multiple of 64: empty ones, which must own nothing"""
+    import synth_small
+    from hite_amd._lib import seed_sub_shard
+    from oracle_ctx import OracleCtx
+
+    assert seed_sub_shard(0, 0, 3, 4) == (3, 4) and seed_sub_shard(2, 3, 1, 4) == (9, 12)
+    tw = OracleCtx()
+    tw.genome_pack(synth_small.make(31, n_fam=10, n_chr=2, chr_len=120_000)["contigs"])
+    n_rec = 0
+    for W, S in ((2, 2), (3, 4), (5, 8), (7, 3)):
+        for r in range(W):
+            share = _twin_share(tw, r, W, 50_000)
+            rows = np.concatenate([_twin_share(tw, *seed_sub_shard(r, W, s, S), 50_000) for s in range(S)])
+            rows = rows[np.lexsort((rows[:, 1], rows[:, 0]))]
+            assert np.array_equal(rows, share), (W, S, r, len(rows), len(share))
+            n_rec += len(share)
+    assert n_rec > 200
+    # a genome so small that sub-shares are empty: two contigs of 400 bases that share 300
+    rng = np.random.default_rng(5)
+    fam = casegen.rand_seq(rng, 300)
+    tiny = [casegen.rand_seq(rng, 60) + fam + casegen.rand_seq(rng, 40), casegen.rand_seq(rng, 30) + fam + casegen.rand_seq(rng, 70)]
+    tw.genome_pack(tiny)
+    W, S, G = 5, 8, 800
+    n_empty = n_rec = 0
+    for r in range(W):
+        share = _twin_share(tw, r, W, 50_000)
+        parts = []
+        for s in range(S):
+            k, world = seed_sub_shard(r, W, s, S)
+            parts.append(_twin_share(tw, k, world, 50_000))
+            if _shard_edge(G, k, world) == _shard_edge(G, k + 1, world):
+                n_empty += 1
+                assert len(parts[-1]) == 0
+        rows = np.concatenate(parts)
+        rows = rows[np.lexsort((rows[:, 1], rows[:, 0]))]
+        assert np.array_equal(rows, share), (r, len(rows), len(share))
+        n_rec += len(share)
+    assert n_empty >= 1 and n_rec >= 2, (n_empty, n_rec)
+
+
+def test_auto_split_of_a_sharded_context_through_the_twin():
+    """Context.seed_allvsall's own loop (hite_amd/_lib.py) with the two device calls answered by the twin: a context that is rank
+    r of 3 and has to split returns ITS share -- not the whole table -- and is rank r of 3 afterwards; unsharded it returns the
+    whole table as before.  (The twin counts no anchors: its records stand in for them.)"""
+    import types
+
+    import synth_small
+    from hite_amd._lib import Context, HiteError
+    from oracle_ctx import OracleCtx
+
+    class TwinSeeding(Context):
+        def __init__(self, contigs):
+            self.tw = OracleCtx()
+            self.tw.genome_pack(contigs)
+            self.h = None
+            self.set = []
+            self.lib = types.SimpleNamespace(hite_seed_shard=self._set)
+
+        def _set(self, _h, rank, world):
+            self.set.append((rank, world))
+            self.tw.seed_shard(rank, world)
+            return 0
+
+        def _seed_allvsall_once(self, seg_len, max_anchors, cap):
+            t = self.tw.seed_allvsall(seg_len=seg_len)
+            n = len(t["qseg"])
+            if n > max_anchors:
+                return None, n
+            return dict(t, stats=(0, n, n, n)), n
+
+        def close(self):
+            pass
+
+    keys = ("qseg", "sseg", "qs", "qe", "ss", "se")
+    c = TwinSeeding(synth_small.make(31, n_fam=10, n_chr=2, chr_len=120_000)["contigs"])
+    whole = c.seed_allvsall(seg_len=50_000)
+    auto = c.seed_allvsall(seg_len=50_000, max_anchors=len(whole["qseg"]) // 3)
+    assert auto["shares"] >= 4 and all(np.array_equal(auto[k], whole[k]) for k in keys) and c.set[-1] == (0, 0)
+    total = 0
+    for r in range(3):
+        c.seed_shard(r, 3)
+        share = c.seed_allvsall(seg_len=50_000)
+        n = len(share["qseg"])
+        assert 0 < n < len(whole["qseg"])
+        auto = c.seed_allvsall(seg_len=50_000, max_anchors=n // 3)
+        assert auto["shares"] >= 2 and auto["stats"][1] == n
+        assert all(np.array_equal(auto[k], share[k]) for k in keys), r
+        assert c.set[-1] == (r, 3)
+        again = c.seed_allvsall(seg_len=50_000)
+        assert all(np.array_equal(again[k], share[k]) for k in keys), r
+        total += n
+    assert total == len(whole["qseg"])
+    # more sub-shares than the 256 the stage allows: the error it always gave, and the context is still its rank
+    c.seed_shard(2, 3)
+    with pytest.raises(HiteError):
+        c.seed_allvsall(seg_len=50_000, max_anchors=1)
+    assert c.set[-1] == (2, 3)
+    c.seed_shard(0, 0)
