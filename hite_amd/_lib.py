@@ -41,6 +41,8 @@ def load():
         lib.hite_genome_bases.restype = C.c_int64
         lib.hite_host_free.restype = None
         lib.hite_host_free.argtypes = [C.c_void_p]
+        lib.hite_protein_lib_release.restype = None
+        lib.hite_protein_lib_release.argtypes = [C.c_void_p]
         _lib = lib
     return _lib
 
@@ -89,6 +91,8 @@ class Context:
 
     def close(self):
         self.release_copy_index()
+        for lib in list(getattr(self, "_prot_libs", ())):      # before the context, like the copy-finder state
+            lib.release()
         if getattr(self, "_pipe_state", None) is not None and getattr(self, "h", None):
             self.lib.hite_pipeline_release(self._pipe_state)
             self._pipe_state = C.c_void_p(None)
@@ -420,6 +424,74 @@ class Context:
         self._check(self.lib.hite_itr_search(self.h, C.c_int64(n), _p(buf), _p(off), int(end_len), C.c_double(min_identity), int(min_len),
                                              int(match), int(mismatch), int(gap_open), int(gap_extend), _p(out)), "hite_itr_search")
         return out
+
+    # ---- translated protein search (get_domain_info, Util.py:4571: blastx -evalue 1e-20 -outfmt 6) -------------------
+    @staticmethod
+    def _csr(seqs):
+        sb = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        off = np.zeros(len(sb) + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in sb], out=off[1:])
+        return np.frombuffer(b"".join(sb) + b"\0" * 16, dtype=np.uint8), off
+
+    def translate6(self, seqs):
+        """-> per sequence its six frames (+1 +2 +3 -1 -2 -3) as str: standard code, X for a codon with a non-ACGT base, * for a stop"""
+        n = len(seqs)
+        if n == 0:
+            return []
+        buf, off = self._csr(seqs)
+        foff = np.zeros(6 * n + 1, dtype=np.int64)
+        out = np.zeros(int(off[-1]) * 2 + 16, dtype=np.uint8)       # six frames of L bases hold at most 2 L residues
+        self._check(self.lib.hite_translate6(self.h, C.c_int64(n), _p(buf), _p(off), C.c_int64(len(out)), _p(out), _p(foff)), "hite_translate6")
+        txt = out.tobytes()
+        return [[txt[foff[6 * q + f]:foff[6 * q + f + 1]].decode() for f in range(6)] for q in range(n)]
+
+    def protein_lib(self, proteins):
+        """proteins (str / bytes, letters) -> the handle protein_search takes: the seed index of the library on the device.  Released by
+        its release(), or by close() before the context."""
+        return ProteinLib(self, proteins)
+
+    def protein_search(self, queries, lib, evalue=1e-20, stats=None, batch_bases=1 << 20, cap=1 << 16):
+        """the HSPs of `blastx -evalue <evalue> -outfmt 6` by the definition in include/hite_gpu.h -> int32 [n, 10]: query, protein,
+        frame (+-1..3), q_start, q_end, s_start, s_end, raw score, identical columns, columns; ordered by (query, score descending,
+        protein, frame, q_start, s_start).  The queries go to the library in batches of about batch_bases bases; a batch whose
+        HSPs exceed `cap` is asked again with the room it reported.  stats (a dict): seed hits, survivors, tasks are added up."""
+        if lib.ctx is not self or lib.h is None:
+            raise HiteError("protein_search: the library handle belongs to another context or was released")
+        sb = [s.encode() if isinstance(s, str) else bytes(s) for s in queries]
+        parts = []
+        a = 0
+        while a < len(sb):
+            b, nb = a, 0
+            while b < len(sb) and (b == a or nb + len(sb[b]) <= batch_bases):
+                nb += len(sb[b])
+                b += 1
+            buf, off = self._csr(sb[a:b])
+            room = int(cap)
+            while True:
+                out = np.zeros((10, max(room, 1)), dtype=np.int32)
+                n_out = C.c_int64(0)
+                st = np.zeros(3, dtype=np.int64)
+                rc = self.lib.hite_protein_search(self.h, lib.h, C.c_int64(b - a), _p(buf), _p(off), C.c_double(evalue), C.c_int64(out.shape[1]),
+                                                  *[_p(out[k]) for k in range(10)], C.byref(n_out), _p(st))
+                if rc == -4 and n_out.value > out.shape[1]:       # HITE_ECAP: now the room is known
+                    room = n_out.value
+                    continue
+                self._check(rc, "hite_protein_search")
+                break
+            rec = np.ascontiguousarray(out[:, :n_out.value].T)
+            rec[:, 0] += a
+            parts.append(rec)
+            if stats is not None:
+                for k, name in enumerate(("hits", "survivors", "tasks")):
+                    stats[name] = stats.get(name, 0) + int(st[k])
+            a = b
+        return np.concatenate(parts) if parts else np.zeros((0, 10), dtype=np.int32)
+
+    def protein_smin(self, m, n, evalue):
+        """the smallest raw score whose E-value m n K exp(-lambda S) is <= evalue (host arithmetic of the library)"""
+        s = C.c_int32(0)
+        self._check(self.lib.hite_protein_smin(C.c_int64(m), C.c_int64(n), C.c_double(evalue), C.byref(s)), "hite_protein_smin")
+        return s.value
 
     # ---- FMEA (get_longest_repeats_v4 + process_all_seqs, Util.py:4122) --------------------------------
     def fmea_chain(self, qseg, sseg, qs, qe, ss, se, seg_chrom, seg_off, skip_gap, max_len):
@@ -860,3 +932,27 @@ class Context:
         if count:
             self._check(self.lib.hite_memcpy_d2h(_p(out), C.c_void_p(d_ptr), C.c_int64(out.nbytes)), "hite_memcpy_d2h")
         return out
+
+
+class ProteinLib:
+    """a protein library resident on the device (hite_protein_lib_build): residue codes + the 20^4-bucket seed directory"""
+
+    def __init__(self, ctx, proteins):
+        self.ctx = ctx
+        self.h = None
+        buf, off = Context._csr(proteins)
+        self.n_prot = len(off) - 1
+        self.n_res = int(off[-1])
+        h = C.c_void_p(None)
+        ctx._check(ctx.lib.hite_protein_lib_build(ctx.h, C.c_int64(self.n_prot), _p(buf), _p(off), C.byref(h)), "hite_protein_lib_build")
+        self.h = h
+        if not hasattr(ctx, "_prot_libs"):
+            ctx._prot_libs = []
+        ctx._prot_libs.append(self)
+
+    def release(self):
+        if self.h is not None and getattr(self.ctx, "h", None):
+            self.ctx.lib.hite_protein_lib_release(self.h)
+        self.h = None
+        if self in getattr(self.ctx, "_prot_libs", ()):
+            self.ctx._prot_libs.remove(self)

@@ -3,9 +3,10 @@
 /root/reference/module/judge_Non_LTR_transposons.py:16-144): <tmp_output_dir>/confident_non_ltr_{i}.fa.
 
 Candidates: as in the reference they come from the flanked repeats (`--seqs`): polyA/T or tandem tail + TSD structures
-(get_candidate_non_LTR -> search_polyA_TSD, on the GPU), SINE class first, then LINE.  The rescue of LINEs without a TSD by
-protein-domain search (blastx, external) is not part of this build.  `--candidates <fa>` (extension) passes a ready
-candidate file instead.
+(get_candidate_non_LTR -> search_polyA_TSD, on the GPU), SINE class first, then LINE.  The recall of low-copy
+candidates by intact protein domains (util.rescue_low_copy) runs `blastx` when it is installed; HITE_DOMAIN_SEARCH=gpu runs the
+build's own translated search (hite_protein_search) in its place, and without either nothing is recalled that way and the
+stage log says so.  `--candidates <fa>` (extension) passes a ready candidate file instead.
 GPU: one pass of flank_region_align_v5 with judge_boundary_v9 (homology boundaries, polyA / tandem tail within 10 columns
 of the 3' boundary, 8-20 bp TSD with <= 1 edit upstream of the 5' boundary)."""
 import argparse

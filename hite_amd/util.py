@@ -7,9 +7,12 @@ finder (get_full_length_copies_minimap2; `all_copies=` / `copy_finder=` of flank
 (run_itrsearch, Util.py:216) is an in-tree GPU stage pinned to the tool's own output; `trf` and `cd-hit-est` are called where the
 reference calls them when they are installed (the build's own masker / clustering otherwise); the low-copy recall of TIR
 candidates by structure (Util.py:8196-8213: short-TIR signatures + terminal inverted repeats) is reproduced, and so is the
-decision of the recall by protein domains (:8215-8276) on a blastx domain table; blastx itself stays external.
+decision of the recall by protein domains (:8215-8276) on a blastx domain table.  `blastx` itself is called when it is installed;
+the build's own translated search (protein_search_outfmt6: six-frame translation, 4-mer seeds, banded Gotoh on the GPU; the
+definition is in include/hite_gpu.h) takes its place with search="gpu" / domain_search="gpu" or HITE_DOMAIN_SEARCH=gpu.
 """
 import itertools
+import math
 import os
 import re
 import shutil
@@ -1352,26 +1355,30 @@ def flank_region_align_v5(candidate_sequence_path, real_TEs, flanking_len, refer
     return true_tes, low_copy
 
 
-def rescue_low_copy(TE_type, low_copy, plant, work_dir, tandem_masker=None, ctx=None, library_dir=None, threads=1):
+def rescue_low_copy(TE_type, low_copy, plant, work_dir, tandem_masker=None, ctx=None, library_dir=None, threads=1, domain_search=None):
     """The recall of low-copy elements (Util.py:8196-8276): the low-copy sequences go through TRF (tandem repeats -> N) when `trf`
     is installed and through the build's own masker otherwise (`tandem_masker(names, contigs) -> contigs` overrides it).  TIR
     stage: those with a short-TIR signature (get_short_tir_contigs) or a terminal inverted repeat (remove_no_tirs: the in-tree
     stage where the reference runs `itrsearch -i 0.7 -l 7`) are real TEs, with their masked sequence as the tool writes it; the
     others, and the low-copy Helitron / non-LTR candidates, are searched for intact protein domains (get_domain_info: blastx
     against <library_dir>/TIRPeps.lib | HelitronPeps.lib | non_LTR.lib, a hit over >= 95 % of a protein recalls the element with
-    its unmasked sequence).  library_dir defaults to $HITE_LIBRARY_DIR, then <HiTE>/library beside the package (as scripts/judge_Other_transposons.py); blastx is an external tool: when it or the library is
-    missing that recall finds nothing and the stage log says so.  -> (rescued, still low copy), both in the reference's order."""
+    its unmasked sequence).  library_dir defaults to $HITE_LIBRARY_DIR, then <HiTE>/library beside the package (as scripts/judge_Other_transposons.py).
+    domain_search: "gpu" = the build's own translated search, "blastx" = the external tool, None = $HITE_DOMAIN_SEARCH, else the
+    external tool when it is installed; when the search or the library is missing that recall finds nothing and the stage log says
+    so.  -> (rescued, still low copy), both in the reference's order."""
+    mode = _domain_search_mode(domain_search)
     if not low_copy or TE_type not in _PROTEIN_LIB:
         return {}, dict(low_copy)
     # the reference always looks in <HiTE>/library (Util.py:8215-8230: cur_dir + '/library/...'); here: the argument, then
     # $HITE_LIBRARY_DIR, then <HiTE>/library beside the package (as scripts/judge_Other_transposons.py does)
     library_dir = library_dir or os.environ.get("HITE_LIBRARY_DIR") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "library")
     lib = os.path.join(library_dir, _PROTEIN_LIB[TE_type]) if library_dir else None
-    can_search = shutil.which("blastx") is not None and lib is not None and os.path.exists(lib)
+    can_search = (mode == "gpu" or shutil.which("blastx") is not None) and lib is not None and os.path.exists(lib)
     if not can_search:
         # (said once per stage call, in the stage's stderr log: a user must know what this run cannot recall)
         sys.stderr.write("[hite_amd] %d low-copy %s candidate%s: blastx or the protein library (%s) is not there, nothing is recalled by its "
-                         "protein domains (Util.py:8215-8276)%s\n" % (len(low_copy), TE_type, "" if len(low_copy) == 1 else "s",
+                         "protein domains (Util.py:8215-8276; HITE_DOMAIN_SEARCH=gpu / domain_search=\"gpu\" runs the build's own search "
+                         "instead of blastx)%s\n" % (len(low_copy), TE_type, "" if len(low_copy) == 1 else "s",
                                                                       lib or "set HITE_LIBRARY_DIR", "" if TE_type == "tir" else
                                                                       ": low-copy %s elements stay in the low-copy file" % TE_type))
         if TE_type != "tir":
@@ -1396,7 +1403,7 @@ def rescue_low_copy(TE_type, low_copy, plant, work_dir, tandem_masker=None, ctx=
         cons = os.path.join(work_dir, "low_copy.%s.fa" % ("no_tir" if TE_type == "tir" else "masked"))
         table = cons + "." + TE_type + "_domain"
         store_fasta(to_search, cons)
-        if get_domain_info(cons, lib, table, threads, os.path.join(work_dir, TE_type + "_domain")):
+        if get_domain_info(cons, lib, table, threads, os.path.join(work_dir, TE_type + "_domain"), search=mode, ctx=ctx):
             for n in intact_domain_names(table, lib):
                 if n in low_copy:
                     rescued[n] = low_copy[n]
@@ -1519,17 +1526,75 @@ def pet_partitions(items, partitions):
     return parts
 
 
-def get_domain_info(cons, lib, output_table, threads, temp_dir):
+_DOMAIN_SEARCH_MODES = ("gpu", "blastx")
+
+
+def _domain_search_mode(search):
+    """the switch of the domain search: the argument, then $HITE_DOMAIN_SEARCH, then None (blastx when it is installed)"""
+    mode = search if search is not None else (os.environ.get("HITE_DOMAIN_SEARCH") or None)
+    if mode is not None and mode not in _DOMAIN_SEARCH_MODES:
+        raise ValueError("domain search %r: expected one of %s" % (mode, ", ".join(_DOMAIN_SEARCH_MODES)))
+    return mode
+
+
+def protein_search_outfmt6(query_path, lib_path, out_path, evalue=1e-20, ctx=None, protein_lib=None):
+    """The build's own translated search where the reference runs `blastx -db <lib> -evalue 1e-20 -query <query> -outfmt 6`: writes
+    the twelve columns qseqid sseqid pident length mismatch gapopen qstart qend sstart send evalue bitscore, one line per HSP (the
+    definition: include/hite_gpu.h; minus-strand hits have qstart > qend as the tool prints them).  pident = 100 identical /
+    columns; evalue = m n K exp(-lambda S) without length adjustment, bitscore = (lambda S - ln K) / ln 2 with lambda 0.267,
+    K 0.041; mismatch and gapopen are written as 0: they are not computed, and neither the reference (Util.py:1025-1033) nor
+    blastx_domain_table reads them.  protein_lib: a handle of ctx.protein_lib for this library (built here otherwise).
+    -> the number of lines."""
+    ctx = ctx or get_ctx()
+    qnames, qseqs = read_fasta(query_path)
+    pnames, pseqs = read_fasta(lib_path)
+    own = protein_lib is None
+    plib = ctx.protein_lib([pseqs[n] for n in pnames]) if own else protein_lib
+    try:
+        rec = ctx.protein_search([qseqs[n] for n in qnames], plib, evalue=evalue)
+        n_res = plib.n_res
+    finally:
+        if own:
+            plib.release()
+    lam, k = 0.267, 0.041
+    with open(out_path, "w") as f:
+        for (q, p, _frame, qs, qe, ss, se, sc, idn, cols) in rec.tolist():
+            ev = float(len(qseqs[qnames[q]]) // 3) * float(n_res) * k * math.exp(-lam * float(sc))
+            f.write("%s\t%s\t%.3f\t%d\t0\t0\t%d\t%d\t%d\t%d\t%.2e\t%.1f\n" % (qnames[q], pnames[p], 100.0 * idn / cols, cols, qs, qe, ss, se, ev,
+                                                                                  (lam * sc - math.log(k)) / math.log(2.0)))
+    return len(rec)
+
+
+def get_domain_info(cons, lib, output_table, threads, temp_dir, search=None, ctx=None):
     """get_domain_info (Util.py:4571-4612), same arguments: `blastx -evalue 1e-20 -outfmt 6` of the sequences of `cons`
     (in `threads` partitions dealt as the reference's PET deals them) against the protein library `lib`, the fragments chained per
     protein (blastx_domain_table), written as the reference's table: a header line, an empty line, then
-    TE \t protein \t TE_start \t TE_end \t protein_start \t protein_end.  blastx (NCBI BLAST+) is an external search and
-    stays one: without it the table holds the header only and a warning says so.  -> True when the search ran."""
+    TE \t protein \t TE_start \t TE_end \t protein_start \t protein_end.  search: "gpu" = the build's own translated search
+    (protein_search_outfmt6) writes the partitions' -outfmt 6 files, "blastx" = the external tool (NCBI BLAST+), None =
+    $HITE_DOMAIN_SEARCH, else the external tool; without a search the table holds the header only and a warning says so.
+    -> True when the search ran."""
     os.makedirs(temp_dir, exist_ok=True)
     names, contigs = read_fasta(cons)
+    mode = _domain_search_mode(search)
     ran = False
     rows = []
-    if names and shutil.which("blastx") is not None and lib is not None and os.path.exists(lib):
+    have_lib = lib is not None and os.path.exists(lib)
+    if names and mode == "gpu" and have_lib:
+        ctx = ctx or get_ctx()
+        _pn, pseqs = read_fasta(lib)
+        plib = ctx.protein_lib([pseqs[n] for n in _pn])
+        try:
+            for pi, part in enumerate(pet_partitions([(n, contigs[n]) for n in names], max(1, int(threads)))):
+                if not part:
+                    continue
+                query, out = os.path.join(temp_dir, "%d.fa" % pi), os.path.join(temp_dir, "%d.out" % pi)
+                store_fasta(dict(part), query)
+                protein_search_outfmt6(query, lib, out, 1e-20, ctx=ctx, protein_lib=plib)
+                rows.extend(blastx_domain_table(out, 100))
+        finally:
+            plib.release()
+        ran = True
+    elif names and mode != "gpu" and shutil.which("blastx") is not None and have_lib:
         if not all(os.path.exists(lib + ext) for ext in (".phr", ".pin", ".psq")) and shutil.which("makeblastdb"):
             subprocess.run("cd %s && makeblastdb -dbtype prot -in %s > /dev/null 2>&1" % (os.path.dirname(lib) or ".", lib), shell=True, check=False)
         for pi, part in enumerate(pet_partitions([(n, contigs[n]) for n in names], max(1, int(threads)))):
@@ -1542,7 +1607,8 @@ def get_domain_info(cons, lib, output_table, threads, temp_dir):
                 rows.extend(blastx_domain_table(out, 100))
         ran = True
     elif names:
-        sys.stderr.write("[hite_amd] blastx or the protein library %s not found: no low-copy element is recalled by its protein domains\n" % lib)
+        sys.stderr.write("[hite_amd] blastx or the protein library %s not found: no low-copy element is recalled by its protein domains "
+                         "(HITE_DOMAIN_SEARCH=gpu / search=\"gpu\" runs the build's own search instead of blastx)\n" % lib)
     with open(output_table, "w") as f:
         f.write("TE_name\tdomain_name\tTE_start\tTE_end\tdomain_start\tdomain_end\n\n")
         for r in rows:

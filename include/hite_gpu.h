@@ -286,6 +286,68 @@ int hite_itr_search_dev(hite_ctx *ctx, int64_t n, const uint8_t *d_seqs, const i
                         double min_identity, int32_t min_len, int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend,
                         int32_t *d_out, void *stream);
 
+/* ---- translated protein search --- get_domain_info  Util.py:4571-4612 (third-party `blastx -evalue 1e-20 -outfmt 6`) -------------
+ * The search behind the recall of low-copy candidates by intact protein domains (Util.py:8215-8276; the fragments are chained by
+ * multiple_alignment_blastx_v1 :1006-1262).  In-tree stage, not pinned to the tool (no machine of the project has it): the
+ * definition below, its CPU twin tests/protein_twin.py + tests/protein_twin.c, HIP == twin record for record.  No SEG masking, no
+ * composition-based statistics, no length adjustment of the search space.
+ *  1 translation: the query in upper case; frames +1 +2 +3 read it, -1 -2 -3 its reverse complement; standard genetic code, a codon
+ *    with a byte outside ACGT is X, a stop '*'; residue t of frame f covers bases f + 3 t .. f + 3 t + 2 (0-based) of that strand, a
+ *    trailing partial codon is dropped.  Library letters outside the 20 standard residues (either case) are X.  A protein of more than
+ *    65 535 residues or a query of more than 196 605 bases is HITE_EINVAL.
+ *  2 scores: '*' against anything -4, else X against anything -1, else BLOSUM62; a gap of g residues costs 11 + g.
+ *  3 seeds: four consecutive equal standard residues at frame position i and protein position j; a 4-mer with fewer than three distinct
+ *    letters is no seed.
+ *  4 ungapped filter: every seed is extended along its diagonal, to the right from its last column and to the left from its first;
+ *    a side keeps the first position of its best running sum and stops at either sequence's end or once the sum has dropped MORE
+ *    than 16 below that best.  Segment = seed + both extensions; it survives with a score >= 41 (22 bits under lambda 0.3176,
+ *    K 0.134).  Survivors with the same (query, frame, protein, diagonal, segment) count once.
+ *  5 tasks: per (query, frame, protein) the survivors by (diagonal d = j - i, segment start, segment end); one joins the open cluster
+ *    while d <= c + 16, c = the diagonal of the cluster's first survivor.  The cluster by (segment start, segment end) splits where a
+ *    segment starts more than 128 residues after the largest segment end so far.  A piece is a task: band c - 24 .. c + 39 (64
+ *    diagonals), frame rows max(0, first start - 128) .. min(L_f - 1, largest end + 128).
+ *  6 gapped alignment: the best local alignment (Gotoh) over the cells (i, j) of the task's rows and band with 0 <= j < protein
+ *    length; other cells do not exist.  E(i,j) (gap in the protein, from (i-1,j)) = max(H - 12, E - 1), F(i,j) (gap in the frame, from
+ *    (i,j-1)) likewise, opening preferred on a tie; H = max(H(i-1,j-1) + s, E, F) preferring the diagonal, then E, then F; values
+ *    below 1 are 0 = no alignment, and the diagonal move starts a new alignment at (i, j) when H(i-1,j-1) is 0.  The best cell is the
+ *    first maximum in row-major order.  Start cell, identical columns (equal standard residues) and columns are those of the path
+ *    these preferences choose (propagated forward with the scores; no traceback).
+ *  7 E = m n K exp(-lambda S), lambda 0.267, K 0.041 (gapped BLOSUM62 11/1), m = floor(query bases / 3), n = all library residues;
+ *    hite_protein_smin turns the requested E-value into the smallest integer S with E <= evalue (binary64, once per query), the
+ *    device compares integers.
+ *  8 output: per (query, frame, protein) the HSPs by (score descending, frame start, protein start, frame end, protein end); one is
+ *    dropped when it shares its start cell or its end cell with a kept one or lies inside a kept one on both sequences.  Query
+ *    coordinates are 1-based bases (minus strand: q_start > q_end, as the tool prints them), protein coordinates 1-based residues.
+ *    Final order: (query, score descending, protein, frame in the order +1 +2 +3 -1 -2 -3, q_start, s_start).  Nothing depends on
+ *    launch geometry or on the order of an atomic append.
+ *
+ * hite_translate6: step 1 alone (host in, host out): aa_out = the six frames of every query as letters, frame 6 q + f (f = 0..5 for
+ * +1 +2 +3 -1 -2 -3) at frame_off[6 q + f] .. frame_off[6 q + f + 1]; frame_off (6 n + 1 entries) is always filled, HITE_ECAP when
+ * frame_off[6 n] > cap. */
+int hite_translate6(hite_ctx *ctx, int64_t n, const uint8_t *nt, const int64_t *nt_off, int64_t cap, uint8_t *aa_out, int64_t *frame_off);
+/* the library: n_prot proteins as letters + CSR.  Builds the 20^4-bucket seed directory (entries in position order).  *state_io
+ * (initially NULL; an existing handle is released first) owns the index and the grow-only arena of every search; release it with
+ * hite_protein_lib_release before the context is destroyed. */
+int hite_protein_lib_build(hite_ctx *ctx, int64_t n_prot, const uint8_t *aa, const int64_t *aa_off, void **state_io);
+void hite_protein_lib_release(void *state);
+/* steps 1-8 for n_query queries (bytes + CSR).  Parallel output arrays of `cap` entries: query, protein (indices), frame (+-1..3),
+ * q_start, q_end, s_start, s_end, raw score, identical columns, columns; *n_out = the number of HSPs; HITE_ECAP when it exceeds cap
+ * (the first cap are written, nothing behind them).  stats (may be NULL): seed hits, distinct survivors, tasks.  Bit score and
+ * E-value are the caller's arithmetic on the raw score. */
+int hite_protein_search(hite_ctx *ctx, void *state, int64_t n_query, const uint8_t *nt, const int64_t *nt_off, double evalue, int64_t cap,
+                        int32_t *o_query, int32_t *o_prot, int32_t *o_frame, int32_t *o_qstart, int32_t *o_qend, int32_t *o_sstart,
+                        int32_t *o_send, int32_t *o_score, int32_t *o_ident, int32_t *o_cols, int64_t *n_out, int64_t *stats);
+/* host code (no GPU needed).  Step 7: *smin for m query residues and n library residues. */
+int hite_protein_smin(int64_t m, int64_t n, double evalue, int32_t *smin);
+/* step 5 on survivors ordered as step 5 says, each once (frame = index into frame_len[n_frames], the frame lengths in residues)
+ * -> tasks (frame, protein, c, first row, last row) in the order of their groups; HITE_ECAP when there are more than cap. */
+int hite_protein_tasks(int64_t n, const int32_t *frame, const int32_t *prot, const int32_t *diag, const int32_t *seg_start,
+                       const int32_t *seg_end, int64_t n_frames, const int32_t *frame_len, int64_t cap, int32_t *o_frame, int32_t *o_prot,
+                       int32_t *o_c, int32_t *o_lo, int32_t *o_hi, int64_t *n_out);
+/* the filter of step 8 on the HSPs of one (query, frame, protein) group (0-based inclusive cells): keep[k] = 1 when HSP k stays */
+int hite_protein_hsp_filter(int64_t n, const int32_t *score, const int32_t *f_start, const int32_t *p_start, const int32_t *f_end,
+                            const int32_t *p_end, uint8_t *keep);
+
 /* ---- copy finding: this build's GPU-native stage where the reference runs the external
  * `minimap2 -ax map-ont -N 300 -p 0.2` + SAM filtering (get_full_length_copies_minimap2, Util.py:7933-8030;
  * third-party, unpinned -> parity is pinned against the build's own CPU twin, oracle/hite_oracle_copies.c,
