@@ -123,6 +123,8 @@ __device__ __noinline__ void tr_seed_hit(const TrTile &T, int wl, int blk, uint3
         uint32_t pb;
         if (pw >= 0) pb = tr_bad(T, pw, p);
         else {   // two words back of the tile's first word: from global memory (once per tile and period)
+                 // (only a stride of 32 from the tile's first block gets here, and that block starts on a multiple of the tile's 4096 bases,
+                 //  hence of TR_RESEED: it extends whatever `prev` says.  The branch keeps the rule whole should the two constants part.)
             const int64_t q = pwi + (p >> 4);
             const int sh = 2 * (p & 15);
             const uint32_t sb = tr_funnel(bases[q + 1], bases[q], sh);
@@ -251,7 +253,7 @@ __global__ void tr_apply_kernel(int64_t nw32, const uint32_t *__restrict__ trmas
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 
-// Tandem repeats of the resident genome (periods 1 .. max_period, TRF's 2 7 7 scheme, score >= 50) become N for every later
+// Tandem repeats of the resident genome (periods 1 .. max_period, match 2 / edit 5 between neighbouring copies, score >= 50) become N for every later
 // stage.  mask_bits_host (optional): (n_bases + 31) / 32 words, bit i & 31 of word i >> 5 = base i of the concatenated contigs
 // is masked -- what the host side needs to write the reference's .mask FASTA.
 extern "C" int hite_tr_mask(hite_ctx *ctx, int32_t max_period, uint32_t *mask_bits_host, int64_t *masked_bases_out) {

@@ -252,15 +252,13 @@ def test_ext_align_device_function_vs_twin(tmp_path):
     assert n_cases == 1600 and n_cut > 160 and n_full > 160 and n_fast_cols > 50_000
 
 
-def test_tr_seed_kernel_logic_vs_twin(tmp_path):
-    """the tandem-repeat masker's kernel body (tile load, every thread's scan of its words over the periods, leftmost-of-run rule, extension,
-    mask bits) run thread by thread on the host == oracle/hite_oracle_trf.c, on a multi-contig genome with N runs"""
-    import casegen
-    from test_trmask import twin_mask
-
+def _tr_seed_lib(tmp_path, body=None):
+    """the `tr_seed` block of hite_trmask.hip (or `body`, a variant of it) built for the host: host_tr_mask runs it tile by tile,
+    thread by thread; seeds are extended on the spot (there is no list on the host)"""
     ext = _block(os.path.join(ROOT, "hite_amd", "csrc", "hite_ext.h"), "ext_align_dev")
-    body = _block(os.path.join(ROOT, "hite_amd", "csrc", "hite_trmask.hip"), "tr_seed")
-    lib = _build(tmp_path, "trseed", "#define EXT_LUT_PTR const uint32_t *\n" + ext + r"""
+    if body is None:
+        body = _block(os.path.join(ROOT, "hite_amd", "csrc", "hite_trmask.hip"), "tr_seed")
+    return _build(tmp_path, "trseed", "#define EXT_LUT_PTR const uint32_t *\n" + ext + r"""
 #define TR_MAXEXT 4096
 #define TR_MINSCORE 50
 #define TR_RESEED 2048
@@ -278,8 +276,10 @@ extern "C" void host_tr_mask(const uint32_t *bases, const uint32_t *nmask, const
     }
 }
 """)
-    seq, _planted = casegen.make_tandem_case(777, G=40_000, n_arr=40)
-    contigs = [seq[:9_000], seq[9_000:9_777] + "N" * 40 + seq[9_777:30_003], seq[30_003:], "ACGT" * 10, "ACGTTGCA" * 5]
+
+
+def _host_tr_mask(lib, contigs, max_period):
+    """-> the bool mask over the concatenated contigs that the host-built block computes"""
     genome = np.frombuffer("".join(contigs).encode(), dtype=np.uint8)
     G = len(genome)
     coff = np.zeros(len(contigs) + 1, dtype=np.int64)
@@ -290,11 +290,51 @@ extern "C" void host_tr_mask(const uint32_t *bases, const uint32_t *nmask, const
     nm = np.concatenate([nm, np.zeros(40, np.uint32)])
     tr = np.zeros((G + 31) // 32 + 4, dtype=np.uint32)
     lib.host_tr_mask(bases.ctypes.data_as(C.POINTER(C.c_uint32)), nm.ctypes.data_as(C.POINTER(C.c_uint32)), coff.ctypes.data_as(O.i64p),
-                     len(contigs), C.c_int64(G), 500, tr.ctypes.data_as(C.POINTER(C.c_uint32)))
-    got = np.unpackbits(tr.view(np.uint8), bitorder="little")[:G].astype(bool)
+                     len(contigs), C.c_int64(G), int(max_period), tr.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return np.unpackbits(tr.view(np.uint8), bitorder="little")[:G].astype(bool)
+
+
+def test_tr_seed_kernel_logic_vs_twin(tmp_path):
+    """the tandem-repeat masker's kernel body (tile load, every thread's scan of its words over the periods, leftmost-of-run rule, extension,
+    mask bits) run thread by thread on the host == oracle/hite_oracle_trf.c, on a multi-contig genome with N runs"""
+    import casegen
+    from test_trmask import twin_mask
+
+    lib = _tr_seed_lib(tmp_path)
+    seq, _planted = casegen.make_tandem_case(777, G=40_000, n_arr=40)
+    contigs = [seq[:9_000], seq[9_000:9_777] + "N" * 40 + seq[9_777:30_003], seq[30_003:], "ACGT" * 10, "ACGTTGCA" * 5]
+    got = _host_tr_mask(lib, contigs, 500)
     exp = twin_mask(contigs)
     assert exp.sum() > 3000
     assert np.array_equal(got, exp), (int(got.sum()), int(exp.sum()), np.flatnonzero(got != exp)[:10])
+
+
+def test_tr_seed_kernel_logic_at_period_tile_and_contig_edges(tmp_path):
+    """the same block == the twin on every input of tests/trmask_cases.py: max_period on both sides of every border of tr_scan_word's
+    groups and strides, arrays across tile borders and reseed points with contig ends beside them, genomes shorter than a block, a word
+    or a tile.  The device tests (test_gpu_trmask.py) run the same cases: one that fails there and passes here is wrong in what only
+    the device has (LDS staging, the seed list, tr_extend_kernel, tr_apply_kernel, the launch geometry)."""
+    import trmask_cases as TC
+    from test_trmask import twin_mask
+
+    lib = _tr_seed_lib(tmp_path)
+    assert TC.period_genome() == TC.period_case()[0]
+    bad, twin_count = [], {}
+    for label, contigs, P in TC.all_cases():
+        got, exp = _host_tr_mask(lib, contigs, P), twin_mask(contigs, P)
+        twin_count[label] = int(exp.sum())
+        if not np.array_equal(got, exp):
+            bad.append((label, int(got.sum()), int(exp.sum()), np.flatnonzero(got != exp)[:6].tolist()))
+    assert len(twin_count) == len(TC.PERIODS) + len(TC.BORDER_CUTS) * len(TC.BORDER_PERIODS) + len(TC.BLOCK1_PERIODS) + len(TC.TINY) * len(TC.TINY_PERIODS)
+    # the twin's own counts, recorded with the cases
+    assert {P: twin_count["period-P%d" % P] for P in TC.PERIODS} == TC.TWIN_MASKED
+    for label, _contigs, _P, count in TC.border_cases():
+        assert twin_count[label] == count, label
+    assert {P: twin_count["block1-P%d" % P] for P in TC.BLOCK1_PERIODS} == TC.BLOCK1_TWIN_MASKED
+    for s in TC.TINY:
+        want = TC.tiny_expect_500(s)
+        assert want is None or twin_count["tiny-%s-P500" % TC.tiny_label(s)] == want, s
+    assert not bad, bad
 
 
 def test_copy_name_order_vs_python_strings(tmp_path):
