@@ -425,6 +425,28 @@ class Context:
                                              int(match), int(mismatch), int(gap_open), int(gap_extend), _p(out)), "hite_itr_search")
         return out
 
+    # ---- pairwise identity (the -c / -A of cd-hit-est -aS 0.95 -aL 0.95 -c <c> -G 0 -g 1 -A 80) ---------------------------
+    def pair_identity(self, seqs, pairs, band=32):
+        """seqs: str / bytes; pairs: rows (a_id, a_start, a_end, b_id, b_start, b_end, strand), intervals 0-based and half-open, the
+        second one reverse-complemented when strand != 0 -> int32 [n_pair, 2]: (cost, matches) of the banded edit alignment that
+        include/hite_gpu.h defines ("pairwise identity"); (-1, 0) for a pair beyond a limit or outside its sequences.  The identity is
+        matches / (cost + matches)."""
+        pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 7)
+        n = len(pr)
+        out = np.zeros((n, 2), dtype=np.int32)
+        if n == 0:
+            return out
+        buf, off = self._csr(seqs)
+        cost, mat = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        ai, bi = _arr(pr[:, 0], np.int32), _arr(pr[:, 3], np.int32)
+        if (ai != pr[:, 0]).any() or (bi != pr[:, 3]).any():
+            raise HiteError("pair_identity: a sequence id does not fit 32 bits")
+        self._check(self.lib.hite_pair_identity(self.h, C.c_int64(len(off) - 1), _p(buf), _p(off), C.c_int64(n), _p(ai), _p(_arr(pr[:, 1], np.int64)),
+                                                _p(_arr(pr[:, 2], np.int64)), _p(bi), _p(_arr(pr[:, 4], np.int64)), _p(_arr(pr[:, 5], np.int64)),
+                                                _p(_arr(pr[:, 6] != 0, np.uint8)), C.c_int32(int(band)), _p(cost), _p(mat)), "hite_pair_identity")
+        out[:, 0], out[:, 1] = cost, mat
+        return out
+
     # ---- translated protein search (get_domain_info, Util.py:4571: blastx -evalue 1e-20 -outfmt 6) -------------------
     @staticmethod
     def _csr(seqs):

@@ -13,9 +13,12 @@ from hite_amd import util  # noqa: E402
 
 def run_cd_hit(inp, outp, threads):
     """cd-hit-est -aS .95 -aL .95 -c .8 -G 0 -g 1 -A 80 (judge_TIR_transposons.py:87); when it is not installed the build's own
-    stand-in removes the redundant sequences (util.remove_redundant_sequences) -- the step is never skipped"""
+    stand-in removes the redundant sequences (util.remove_redundant_sequences) -- the step is never skipped.  The stand-in is
+    given -c 0.8 and -A 80 as well; they take effect with HITE_CLUSTER_IDENTITY=gpu (the pairwise identity of include/hite_gpu.h
+    on every chain that passes the coverage tests), by default it clusters on coverage alone.  Either way parity with cd-hit-est
+    itself is unpinned."""
     if shutil.which("cd-hit-est") is None:
-        util.remove_redundant_sequences(inp, outp, 0.95, 0.95)
+        util.remove_redundant_sequences(inp, outp, 0.95, 0.95, c=0.8, min_aligned=80)
         return
     subprocess.run("cd-hit-est -aS 0.95 -aL 0.95 -c 0.8 -G 0 -g 1 -A 80 -i %s -o %s -T %d -M 0 > /dev/null 2>&1" % (inp, outp, threads),
                    shell=True, check=False)

@@ -10,6 +10,8 @@ candidates by structure (Util.py:8196-8213: short-TIR signatures + terminal inve
 decision of the recall by protein domains (:8215-8276) on a blastx domain table.  `blastx` itself is called when it is installed;
 the build's own translated search (protein_search_outfmt6: six-frame translation, 4-mer seeds, banded Gotoh on the GPU; the
 definition is in include/hite_gpu.h) takes its place with search="gpu" / domain_search="gpu" or HITE_DOMAIN_SEARCH=gpu.
+The clustering that stands in for `cd-hit-est` (remove_redundant_sequences) works on chain coverage alone by default; with
+identity="gpu" or HITE_CLUSTER_IDENTITY=gpu its -c / -A rest on the pairwise identity of include/hite_gpu.h (Context.pair_identity).
 """
 import itertools
 import math
@@ -1048,20 +1050,38 @@ def deredundant_for_LTR_v5(redundant_ltr, work_dir, threads, type, coverage_thre
         subprocess.run("cd-hit-est -aS 0.95 -aL 0.95 -c %s -G 0 -g 1 -A 80 -i %s -o %s -T 0 -M 0 > /dev/null 2>&1" %
                        (coverage_threshold, cons_path, final_path), shell=True, check=False)
     else:
-        remove_redundant_sequences(cons_path, final_path, 0.95, 0.95, device=device, ctx=ctx)     # the build's stand-in, never a plain copy
+        # the build's stand-in, never a plain copy; -c takes effect with HITE_CLUSTER_IDENTITY=gpu
+        remove_redundant_sequences(cons_path, final_path, 0.95, 0.95, device=device, ctx=ctx, c=coverage_threshold)
     return cons_path
 
 
-def remove_redundant_sequences(inp, outp, aS=0.95, aL=0.95, device=0, ctx=None):
+def _cluster_identity_on(identity):
+    """the switch of the identity test of remove_redundant_sequences: the argument, then $HITE_CLUSTER_IDENTITY; "gpu" is on"""
+    mode = identity if identity is not None else os.environ.get("HITE_CLUSTER_IDENTITY")
+    return mode == "gpu"
+
+
+def remove_redundant_sequences(inp, outp, aS=0.95, aL=0.95, device=0, ctx=None, c=None, min_aligned=80, identity=None):
     """The build's stand-in for `cd-hit-est -aS 0.95 -aL 0.95 -c <c> -G 0 -g 1 -A 80 -i inp -o outp` (judge_TIR_transposons.py:87,
     Util.py:12330; cd-hit-est is an external tool: PARITY UNPINNED), used when it is not installed -- the step is never skipped.
     Greedy incremental clustering in cd-hit's order (longest first, ties in input order): a sequence joins the first longer
     representative that a chain of library-vs-library hits (hite_seed_allvsall + hite_lib_chain, the stages of the library
     merge) covers to >= aS of the shorter and >= aL of the longer sequence; otherwise it becomes a representative.  The
-    representatives are written longest first, as cd-hit-est writes them.  Identity is not computed: hits are runs of shared
-    15-base minimizers, which sequences below ~85 % identity hardly have (cd-hit's -c 0.8 / 0.95 asks for less / more)."""
+    representatives are written longest first, as cd-hit-est writes them.
+    By default identity is not computed: hits are runs of shared 15-base minimizers, which sequences below ~85 % identity hardly
+    have (cd-hit's -c 0.8 / 0.95 asks for less / more), so `c` and `min_aligned` are ignored.
+    identity="gpu" (or HITE_CLUSTER_IDENTITY=gpu when the argument is None; anything else is off) with `c` given puts -c and -A on
+    the pairwise identity of include/hite_gpu.h (hite_pair_identity; twin tests/identity_twin.py): every chain record that passes
+    the two coverage tests goes, once, into one batched Context.pair_identity call -- the query interval and the subject interval
+    of the record (the bases the chain covers; the reverse-complemented subject when its coordinates descend), band 32 -- and
+    counts only if both intervals hold >= min_aligned bases and matches >= c * (cost + matches) in binary64.  A record the
+    primitive refuses (cost -1: an interval above 32 767 bases, or a length difference the band cannot hold) does not count, so
+    such a pair is not merged; one line on stderr gives the number of those records.  The greedy pass and the output order are the
+    same.  This is an edit-distance identity over the chained interval, not cd-hit's banded local alignment (2 / -2 / -6 / -1):
+    parity with the tool itself stays unpinned."""
     names, contigs = read_fasta(inp)
     work = [n for n in names if len(contigs[n]) > 0]         # (nothing is aligned here: no length limit)
+    by_identity = c is not None and _cluster_identity_on(identity)
     drop = set()
     if len(work) > 1:
         if ctx is None:
@@ -1071,12 +1091,20 @@ def remove_redundant_sequences(inp, outp, aS=0.95, aL=0.95, device=0, ctx=None):
         qs, qe, ss, se = _stretch_hits(q, s_, qs, qe, ss, se, lens, [contigs[n].upper() for n in work])
         recs = ctx.lib_chain(q, s_, qs, qe, ss, se, lens, min(aS, aL), 5_000_000)
         covered = {}
-        for (_ch, qi, a, b, si, c, d) in recs:
+        candidates = {}                                      # (identity test) the records that pass the coverage tests, each once
+        for (_ch, qi, a, b, si, s0, s1) in recs:
             if qi == si:
                 continue
-            cq, cs = (b - a) / lens[qi], abs(d - c) / lens[si]
+            cq, cs = (b - a) / lens[qi], abs(s1 - s0) / lens[si]
             short_cov, long_cov = (cq, cs) if lens[qi] <= lens[si] else (cs, cq)
             if short_cov >= aS and long_cov >= aL:
+                if by_identity:
+                    candidates.setdefault((qi, a, b, si, s0, s1), None)
+                    continue
+                covered.setdefault(qi, set()).add(si)
+                covered.setdefault(si, set()).add(qi)
+        if by_identity:
+            for qi, si in _identity_filter(ctx, [contigs[n] for n in work], lens, list(candidates), float(c), int(min_aligned)):
                 covered.setdefault(qi, set()).add(si)
                 covered.setdefault(si, set()).add(qi)
         order = sorted(range(len(work)), key=lambda i: (-lens[i], i))
@@ -1090,6 +1118,27 @@ def remove_redundant_sequences(inp, outp, aS=0.95, aL=0.95, device=0, ctx=None):
     keep.sort(key=lambda n: -len(contigs[n]))          # (stable: ties stay in input order)
     store_fasta({n: contigs[n] for n in keep}, outp)
     return outp
+
+
+def _identity_filter(ctx, seqs, lens, records, c, min_aligned, band=32):
+    """the -c / -A test of remove_redundant_sequences on chain records (q, q0, q1, s, s0, s1) as hite_lib_chain writes them: the query
+    bases [q0, q1); the subject bases [s0, s1) on the forward strand and, when the coordinates descend (s0 = s_start - 1 > s1 = s_end
+    of a minus-strand chain), [s1 - 1, s0 + 1) reverse-complemented.  -> the (q, s) of the records that count."""
+    pairs = []
+    for (qi, a, b, si, s0, s1) in records:
+        lo, hi, strand = (s0, s1, 0) if s0 <= s1 else (s1 - 1, s0 + 1, 1)
+        pairs.append((qi, max(0, a), min(lens[qi], b), si, max(0, lo), min(lens[si], hi), strand))
+    res = ctx.pair_identity(seqs, pairs, band=band) if pairs else np.zeros((0, 2), dtype=np.int32)
+    out, refused = [], 0
+    for p, (cost, matches) in zip(pairs, res.tolist()):
+        if cost < 0:
+            refused += 1
+            continue
+        if p[2] - p[1] >= min_aligned and p[5] - p[4] >= min_aligned and float(matches) >= c * float(cost + matches):
+            out.append((p[0], p[3]))
+    sys.stderr.write("remove_redundant_sequences: identity test on %d chain records, %d refused by the pairwise identity (over 32 767 bases "
+                     "or outside its band): not merged\n" % (len(pairs), refused))
+    return out
 
 
 def mask_genome_intactTE(TE_lib, genome_path, work_dir=None, thread=1, ref_index=0, debug=0, device=0):
