@@ -284,7 +284,8 @@ __global__ void __launch_bounds__(256) star_layout_sparse_kernel(MsaParams P, in
                 kw = 1;
                 if (s_nkw <= LAY_KW_LIST) kw = s_kwres[p - base];
                 else {
-                    // more such positions in one round than the list holds (it never happened on C2 / C3): the lane walks the rows
+                    // more such positions in one round than the list holds (it never happened on C2 / C3; the kwlist_* cases of
+                    // tests/test_gpu_star_layout.py make it happen, at 257 and beyond, in round 0 and in round 1): the lane walks the rows
                     for (;;) {
                         int cnt = 0;
                         for (int r = 1; r < R; r++) cnt += row_ins(ops + (int64_t)r * (m + 1), p, m, P.win_len[g0 + msa_src(P.row_map, g0, r)]) > kw;
