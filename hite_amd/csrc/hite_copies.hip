@@ -11,9 +11,10 @@
 //     from the sorted hashes (round 5; it was an append in arbitrary order + a 7-pass sort on (hash, position));
 //   query: candidate minimizers (wave per candidate, LDS tile of 64 windows, private regions + pack) -> directory
 //     lookup -> occurrence counts -> scan -> wave-cooperative hit expansion (key = candidate | relative strand |
-//     diagonal) -> radix sort (10-bit digits) -> cluster flags where the diagonal jumps -> extreme anchors per
-//     cluster by a wave-level segmented min / max scan -> coverage filter + boundary extrapolation (two passes,
-//     per-candidate counters) -> radix sort by (candidate | anchors desc | start) -> top 300.
+//     diagonal) -> per-candidate sort in LDS whose epilogue finds the diagonal clusters, their extreme anchors and
+//     the chains among them (12-byte hits / HITE_HIT_SEGSORT=0: global radix sort -> cluster flags -> scan ->
+//     cluster arrays -> chain list) -> chain table -> end extension -> coverage filter + boundary extrapolation
+//     (two passes, per-candidate counters) -> radix sort by (candidate | anchors desc | start) -> top 300.
 //   The second half of the file is the all-vs-all seeding of stage 3.1 on the same index (hite_seed_allvsall).
 // Bound: HBM streaming for the sorts (12 B in + 12 B out per element per pass) and L2-latency for the
 // directory lookups; integer work only.
@@ -585,9 +586,10 @@ __global__ void hit_hist_kernel(int n_cand, const int64_t *__restrict__ q_first,
 // ---------------------------------------------------------------------------------------------
 // per-candidate sort of the hits.  The hits of a candidate are generated contiguously (hit_off[q_first[c]] ..), so the order
 // (candidate, strand, diagonal) only has to be established INSIDE every candidate's range: a workgroup loads the range into
-// LDS, sorts it there on the (strand | diagonal) field by a stable LSD radix sort (4-bit digits, two LDS buffers) and writes
-// it back in place -- one global read and one write of 8 bytes per hit where the global radix sort of round 3 made five
-// passes (5 x 16 B + histograms).  Four classes by hits per candidate (C3: <= 2048: 75 % of the candidates, 51 % of the hits;
+// LDS, sorts it there on the (strand | diagonal) field by a stable LSD radix sort (4-bit digits, two LDS buffers) and takes
+// the candidate's chains from the sorted range where it lies (hs_chains) -- one global read of 8 bytes per hit and 24 bytes
+// written per chain, where the global radix sort of round 3 made five passes (5 x 16 B + histograms) and the cluster kernels
+// behind it four more over the hits.  Four classes by hits per candidate (C3: <= 2048: 75 % of the candidates, 51 % of the hits;
 // <= 4096: 19 % / 31 %; <= 8192: 5 % / 14 %; above: 0.6 % / 3.6 %, profiles of round 3): 2 x 16, 2 x 32, 2 x 64 KB of LDS (the
 // last one holds a CU by itself), and global ping-pong buffers (the range against the sorter's spare array) for the rest.  Stable, like the global passes it replaces: the table is
 // the same, hit for hit.  (Packed 8-byte hits only; the 12-byte form keeps the global sort.)
@@ -598,13 +600,17 @@ __global__ void hit_hist_kernel(int n_cand, const int64_t *__restrict__ q_first,
 #define HS_NCLS 4
 typedef __attribute__((address_space(3))) unsigned long long *hs_lptr;
 __global__ void hit_sort_classify_kernel(int n_cand, const int64_t *__restrict__ q_first, const int64_t *__restrict__ hit_off,
-                                         unsigned *__restrict__ counts /* HS_NCLS */, int32_t *__restrict__ lists /* HS_NCLS x n_cand */) {
+                                         unsigned *__restrict__ counts /* HS_NCLS */, int32_t *__restrict__ lists /* HS_NCLS x n_cand */,
+                                         unsigned long long *__restrict__ n_clusters) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     long long k = 0;
     if (c < n_cand) k = hit_off[q_first[c + 1]] - hit_off[q_first[c]];
     const int cls = k <= 1 ? -1 : (k <= HS_SMALL ? 0 : (k <= HS_MID ? 1 : (k <= HS_MEDIUM ? 2 : 3)));
     // one atomic per wavefront and class (50 000 atomics on three addresses cost 0.5 ms)
     const int lane = threadIdx.x & 63;
+    // a candidate with a single hit is sorted by nobody: its one cluster is counted here (the sort's epilogue counts the others)
+    const unsigned long long single = __ballot(k == 1);
+    if (single != 0ull && lane == 0) atomicAdd(n_clusters, (unsigned long long)__popcll(single));
 #pragma unroll
     for (int q = 0; q < HS_NCLS; q++) {
         const unsigned long long m = __ballot(cls == q);
@@ -641,22 +647,163 @@ __device__ __forceinline__ void hs_pass(PS src, PD dst, int n, int shift, CT *s_
     }
     __syncthreads();
 }
+// ---- chains = clusters with >= 3 anchors whose query span is >= 95 % of their genome span and whose ends are short enough to
+// extend.  Everything behind the clustering reads a dense record per chain, in a table of `cap` entries: chains with a long end
+// to extend (>= EXT_LONG bases) are listed from the front, the others from the back, counters[0] / [1] count them (the
+// extension takes its tasks front to back, so the long chains -- the tail of the kernel otherwise -- start first).
+#define EXT_LONG 384
+#define EXT_MAXLEN 2048     // an end of more than this many bases beyond the outermost anchor is not extended: no chain
+struct ChainRec {
+    unsigned long long lo, hi;      // extreme anchors, qo << 32 | gpos: min qo -> smallest gpos, max qo -> largest gpos
+    unsigned cs, na;                // candidate << 1 | relative strand; anchors
+};
+// 0: no chain, 1: chain with a long end, 2: the other chains
+__device__ __forceinline__ int chain_class(int na, unsigned long long lo, unsigned long long hi, long long Lq) {
+    if (na < C_MINANCH) return 0;
+    const long long qlo = (long long)(lo >> 32), glo = (long long)(lo & 0xffffffffull);
+    const long long qhi = (long long)(hi >> 32), ghi = (long long)(hi & 0xffffffffull);
+    if ((qhi + CK - qlo) * 100 < 95 * (ghi + CK - glo)) return 0;
+    const long long nl = qlo, nr = Lq - (qhi + CK);
+    if (nl > EXT_MAXLEN || nr > EXT_MAXLEN) return 0;
+    return (nl >= EXT_LONG || nr >= EXT_LONG) ? 1 : 2;
+}
+// Epilogue of the per-candidate sort: the chains of ONE candidate straight from its sorted range r[0, n) (LDS, or global for the
+// ping-pong class) -- cluster_flag_kernel's rule, run lengths, the extreme anchors per run and chain_class, with no flag, cluster
+// id or cluster array in global memory.  Wave per chunk of 64 hits: a segmented scan over the lanes (shuffles) closes the runs
+// that begin and end inside the chunk; per chunk, the piece before its first run start (p_*: length, bit 31 = the whole chunk
+// continues into the next one) and the piece from its last run start to its end (t_*) go to the scratch, and a thread per chunk
+// then joins t_ with the p_ of the chunks that follow (a step per 64 hits of a run, not per hit: at most 128 steps in the LDS
+// classes.  The runs are disjoint, so all the joins of a candidate together read each chunk record once; in the global class the
+// lane that joins a run of r hits reads r / 64 records from L2 while its neighbours wait -- 16 for a run of a thousand anchors).
+// The chains are staged in the scratch (long ones from the front, the others from the back; at most n / 3 of them) and appended
+// to the table with ONE pair of atomics per candidate; the clusters are counted per workgroup and added once, after its last
+// candidate.  The scratch is the buffer that does not hold the sorted range: 20 (n / 3) + 40 ceil(n / 64)
+// bytes <= 8 n from n = 57 on, and <= 8 CAP for every n <= CAP of the LDS classes.
+typedef __attribute__((address_space(3))) unsigned *hs_lptr32;
+template <class S64, class S32>
+__device__ __forceinline__ void hs_chain_stage(int na, unsigned long long lo, unsigned long long hi, unsigned rel, long long Lq, int maxch,
+                                               S64 st_lo, S64 st_hi, S32 st_cr, int *s_n) {
+    const int cls = chain_class(na, lo, hi, Lq);
+    if (!cls) return;
+    const int pos = cls == 1 ? atomicAdd(&s_n[0], 1) : maxch - 1 - atomicAdd(&s_n[1], 1);
+    st_lo[pos] = lo; st_hi[pos] = hi; st_cr[pos] = ((unsigned)na << 1) | rel;
+}
+template <int NT, class P64, class S64, class S32>
+__device__ __forceinline__ void hs_chains(P64 r, int n, S64 scr, unsigned c, const HitFmt &F, long long Lq, const int64_t *__restrict__ coff,
+                                          int nc, ChainRec *__restrict__ tab, unsigned long long cap, unsigned long long *__restrict__ counters,
+                                          int *s_n /* [0..1] zero on entry and on return; [2] += the candidate's clusters */,
+                                          unsigned long long *s_base /* [2] */) {
+    const int lane = threadIdx.x & 63;
+    const int maxch = n / C_MINANCH, nch = (n + 63) >> 6;
+    S64 st_lo = scr, st_hi = st_lo + maxch, p_lo = st_hi + maxch, p_hi = p_lo + nch, t_lo = p_hi + nch, t_hi = t_lo + nch;
+    S32 st_cr = (S32)(t_hi + nch), p_c = st_cr + maxch, t_c = p_c + nch;
+    int nclw = 0;
+    for (int j = threadIdx.x >> 6; j < nch; j += NT / 64) {
+        const int i = j * 64 + lane;
+        const bool have = i < n;
+        unsigned long long lo = 0xffffffffffffffffull, hi = 0ull;
+        int head = 1, cnt = 0;            // lanes past the end: empty runs of their own
+        unsigned rel = 0u;
+        if (have) {
+            const unsigned long long b = r[i];
+            const long long db = hit_dbias(F, b), gb = db - DBIAS + hit_qo(F, b, 0);
+            lo = hi = ((unsigned long long)hit_qo(F, b, 0) << 32) | ((unsigned long long)gb & 0xffffffffull);
+            cnt = 1;
+            rel = hit_rel(F, b);
+            if (i > 0) {                  // (i = 0: the candidate changes)
+                const unsigned long long a = r[i - 1];
+                const long long da = hit_dbias(F, a), ga = da - DBIAS + hit_qo(F, a, 0);
+                head = hit_strand_key(F, a) != hit_strand_key(F, b) || db - da > C_TD;
+                if (!head) { const int ca = contig_of(coff, nc, ga); head = gb < coff[ca] || gb >= coff[ca + 1]; }
+            }
+        }
+        const unsigned long long headmask = __ballot(have && head);
+        nclw += __popcll(headmask);
+        const int next_head = __shfl_down(head, 1);
+        int f = head;                     // does the piece of the run up to this lane begin inside the chunk?
+#pragma unroll
+        for (int dd = 1; dd < 64; dd <<= 1) {
+            const unsigned long long olo = __shfl_up(lo, dd), ohi = __shfl_up(hi, dd);
+            const int ocnt = __shfl_up(cnt, dd), of = __shfl_up(f, dd);
+            if (lane >= dd && !f) { lo = olo < lo ? olo : lo; hi = ohi > hi ? ohi : hi; cnt += ocnt; f = of; }
+        }
+        const bool last_chunk = j == nch - 1;
+        const bool ends = have && (i == n - 1 || (lane < 63 && next_head));
+        if (ends && f) hs_chain_stage(cnt, lo, hi, rel, Lq, maxch, st_lo, st_hi, st_cr, s_n);
+        if (headmask == 0ull) {           // no run starts here: all of it continues the run of an earlier chunk
+            if (lane == (last_chunk ? n - 1 - j * 64 : 63)) { p_lo[j] = lo; p_hi[j] = hi; p_c[j] = (unsigned)cnt | (last_chunk ? 0u : 0x80000000u); t_c[j] = 0u; }
+        } else {
+            const int h0 = __ffsll((long long)headmask) - 1;
+            if (lane == (h0 > 0 ? h0 - 1 : 0)) { p_c[j] = h0 > 0 ? (unsigned)cnt : 0u; if (h0 > 0) { p_lo[j] = lo; p_hi[j] = hi; } }
+            // the run that is open at the end of the chunk (the last chunk's has ended, and is staged above)
+            if (lane == 63) { t_c[j] = last_chunk ? 0u : (((unsigned)cnt << 1) | rel); t_lo[j] = lo; t_hi[j] = hi; }
+        }
+    }
+    if (lane == 0 && nclw) atomicAdd(&s_n[2], nclw);
+    __syncthreads();
+    for (int j = threadIdx.x; j < nch; j += NT) {
+        const unsigned tc = t_c[j];
+        if (!tc) continue;
+        unsigned long long lo = t_lo[j], hi = t_hi[j];
+        int cnt = (int)(tc >> 1);
+        for (int m = j + 1; m < nch; m++) {
+            const unsigned pc = p_c[m];
+            if (pc & 0x7fffffffu) {
+                const unsigned long long olo = p_lo[m], ohi = p_hi[m];
+                lo = olo < lo ? olo : lo; hi = ohi > hi ? ohi : hi; cnt += (int)(pc & 0x7fffffffu);
+            }
+            if (!(pc >> 31)) break;
+        }
+        hs_chain_stage(cnt, lo, hi, tc & 1u, Lq, maxch, st_lo, st_hi, st_cr, s_n);
+    }
+    __syncthreads();
+    const int nL = s_n[0], nS = s_n[1];
+    if (threadIdx.x == 0) {
+        s_base[0] = nL ? atomicAdd(&counters[0], (unsigned long long)nL) : 0ull;
+        s_base[1] = nS ? atomicAdd(&counters[1], (unsigned long long)nS) : 0ull;
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < nL + nS; q += NT) {
+        const bool lng = q < nL;
+        const int pos = lng ? q : maxch - 1 - (q - nL);
+        const unsigned long long e = lng ? s_base[0] + (unsigned long long)q : s_base[1] + (unsigned long long)(q - nL);
+        if (e < cap) {
+            const unsigned cr = st_cr[pos];
+            ChainRec R;
+            R.lo = st_lo[pos]; R.hi = st_hi[pos]; R.cs = (c << 1) | (cr & 1u); R.na = cr >> 1;
+            tab[lng ? e : cap - 1 - e] = R;
+        }
+    }
+    if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
+    __syncthreads();
+}
 template <int CAP /* elements per LDS buffer; 0: global ping-pong */, int NT /* threads */>
 __global__ void __launch_bounds__(NT) hit_segsort_kernel(const unsigned *__restrict__ count, const int32_t *__restrict__ list,
                                                          const int64_t *__restrict__ q_first, const int64_t *__restrict__ hit_off,
                                                          unsigned long long *__restrict__ hkey, unsigned long long *__restrict__ spare,
-                                                         int shift0, int bits) {
+                                                         int shift0, int bits, const int64_t *__restrict__ cand_off,
+                                                         const int64_t *__restrict__ coff, int nc, ChainRec *__restrict__ tab,
+                                                         unsigned long long cap, unsigned long long *__restrict__ counters,
+                                                         unsigned long long *__restrict__ n_clusters) {
     typedef typename std::conditional<(CAP > 0), uint16_t, unsigned>::type CT;
     __shared__ CT s_cnt[16 * NT];
     __shared__ int s_scan[16];
+    __shared__ int s_n[3];
+    __shared__ unsigned long long s_base[2];
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_dyn[];
     const unsigned cnt = *count;
     const int passes = (bits + 3) / 4;
+    HitFmt F;                              // (packed hits only)
+    F.qbits = shift0; F.dbits = bits - 1; F.hval = nullptr;
+    if (threadIdx.x < 3) s_n[threadIdx.x] = 0;
+    __syncthreads();
     for (unsigned it = blockIdx.x; it < cnt; it += gridDim.x) {
         const int c = list[it];
         const int64_t o = hit_off[q_first[c]];
         const int n = (int)(hit_off[q_first[c + 1]] - o);
+        const long long Lq = cand_off[c + 1] - cand_off[c];
         unsigned long long *g = hkey + o;
+        // the sorted range is read by the epilogue alone and is not written back
         if (CAP > 0) {
             hs_lptr a = (hs_lptr)s_dyn, bq = (hs_lptr)s_dyn + CAP;
             for (int i = threadIdx.x; i < n; i += NT) a[i] = g[i];
@@ -664,18 +811,19 @@ __global__ void __launch_bounds__(NT) hit_segsort_kernel(const unsigned *__restr
             for (int ps = 0; ps < passes; ps++) {
                 if (ps & 1) hs_pass<NT, CT>(bq, a, n, shift0 + 4 * ps, s_cnt, s_scan); else hs_pass<NT, CT>(a, bq, n, shift0 + 4 * ps, s_cnt, s_scan);
             }
-            hs_lptr r = (passes & 1) ? bq : a;
-            for (int i = threadIdx.x; i < n; i += NT) g[i] = r[i];
-            __syncthreads();
+            if (passes & 1) hs_chains<NT, hs_lptr, hs_lptr, hs_lptr32>(bq, n, a, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
+            else hs_chains<NT, hs_lptr, hs_lptr, hs_lptr32>(a, n, bq, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
         } else {
             unsigned long long *h = spare + o;
             for (int ps = 0; ps < passes; ps++) {
                 if (ps & 1) hs_pass<NT, CT>(h, g, n, shift0 + 4 * ps, s_cnt, s_scan); else hs_pass<NT, CT>(g, h, n, shift0 + 4 * ps, s_cnt, s_scan);
             }
-            if (passes & 1) { for (int i = threadIdx.x; i < n; i += NT) g[i] = h[i]; }
-            __syncthreads();
+            if (passes & 1) hs_chains<NT, unsigned long long *, unsigned long long *, unsigned *>(h, n, g, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
+            else hs_chains<NT, unsigned long long *, unsigned long long *, unsigned *>(g, n, h, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
         }
     }
+    // the clusters of all the candidates this workgroup took: ONE atomic per workgroup (the last hs_chains ended with a barrier)
+    if (threadIdx.x == 0 && s_n[2]) atomicAdd(n_clusters, (unsigned long long)s_n[2]);
 }
 
 __global__ void cluster_flag_kernel(int64_t nh, const unsigned long long *__restrict__ hkey, HitFmt F,
@@ -746,18 +894,15 @@ __global__ void cluster_acc_init_kernel(int64_t ncl, unsigned long long *__restr
 }
 
 // ---- chains -> copies: base-level end extension + the reference's two coverage filters (definition: header of the twin) --
-// chains = clusters with >= 3 anchors whose query span is >= 95 % of their genome span; their ids go to a dense list
-// (a thread per cluster of the 10^8 diagonal clusters would leave one or two live lanes per wavefront in the extension).
-// Chains with a long end to extend (>= EXT_LONG bases) are listed from the front, the others from the back of the same array:
-// the extension takes its tasks front to back, so the long chains -- the tail of the kernel otherwise -- start first.
-#define EXT_LONG 384
-#define EXT_MAXLEN 2048     // an end of more than this many bases beyond the outermost anchor is not extended: no chain
+// the chain table (ChainRec, above the per-candidate sort) from the cluster arrays: the 12-byte hit form and the global sort, whose
+// clusters are found by the kernels above (the per-candidate sort writes the same records from its own epilogue).  A dense table:
+// a thread per cluster of the 10^8 diagonal clusters would leave one or two live lanes per wavefront in the extension.
 #define CL_ITEMS 16         // clusters per thread: ONE pair of atomics on the two list counters per 4096 clusters (one per wavefront
                             // was a million same-address atomics: 10 ms)
 __global__ void __launch_bounds__(256) chain_list_kernel(int64_t ncl, const unsigned long long *__restrict__ hkey, HitFmt F,
                                                          const unsigned *__restrict__ c_first, const unsigned long long *__restrict__ c_lo,
                                                          const unsigned long long *__restrict__ c_hi, const int64_t *__restrict__ cand_off,
-                                                         unsigned *__restrict__ list, unsigned long long cap,
+                                                         ChainRec *__restrict__ tab, unsigned long long cap,
                                                          unsigned long long *__restrict__ counters /* [0] long, [1] short */) {
     __shared__ int s_scan[8];
     __shared__ unsigned long long s_base[2];
@@ -767,16 +912,9 @@ __global__ void __launch_bounds__(256) chain_list_kernel(int64_t ncl, const unsi
         for (int it = 0; it < CL_ITEMS; it++) {
             const int64_t k = tile + it * 256 + threadIdx.x;
             if (k < ncl && (int)(c_first[k + 1] - c_first[k]) >= C_MINANCH) {
-                const long long qlo = (long long)(c_lo[k] >> 32), glo = (long long)(c_lo[k] & 0xffffffffull);
-                const long long qhi = (long long)(c_hi[k] >> 32), ghi = (long long)(c_hi[k] & 0xffffffffull);
-                if ((qhi + CK - qlo) * 100 >= 95 * (ghi + CK - glo)) {
-                    const unsigned c = hit_cand(F, hkey[c_first[k]]);
-                    const long long Lq = cand_off[c + 1] - cand_off[c];
-                    const long long nl = qlo, nr = Lq - (qhi + CK);
-                    if (nl <= EXT_MAXLEN && nr <= EXT_MAXLEN) {
-                        if (nl >= EXT_LONG || nr >= EXT_LONG) wantL |= 1u << it; else wantS |= 1u << it;
-                    }
-                }
+                const unsigned c = hit_cand(F, hkey[c_first[k]]);
+                const int cls = chain_class((int)(c_first[k + 1] - c_first[k]), c_lo[k], c_hi[k], cand_off[c + 1] - cand_off[c]);
+                if (cls == 1) wantL |= 1u << it; else if (cls == 2) wantS |= 1u << it;
             }
         }
         int tot;
@@ -788,16 +926,20 @@ __global__ void __launch_bounds__(256) chain_list_kernel(int64_t ncl, const unsi
         __syncthreads();
         unsigned long long oL = s_base[0] + (unsigned long long)(pre & 0xffff), oS = s_base[1] + (unsigned long long)(pre >> 16);
         for (int it = 0; it < CL_ITEMS; it++) {
-            const unsigned k = (unsigned)(tile + it * 256 + threadIdx.x);
-            if ((wantL >> it) & 1u) { if (oL < cap) list[oL] = k; oL++; }
-            if ((wantS >> it) & 1u) { if (oS < cap) list[cap - 1 - oS] = k; oS++; }
+            if (!(((wantL | wantS) >> it) & 1u)) continue;
+            const int64_t k = tile + it * 256 + threadIdx.x;
+            const unsigned long long key = hkey[c_first[k]];
+            ChainRec R;
+            R.lo = c_lo[k]; R.hi = c_hi[k]; R.cs = (hit_cand(F, key) << 1) | hit_rel(F, key); R.na = c_first[k + 1] - c_first[k];
+            if ((wantL >> it) & 1u) { if (oL < cap) tab[oL] = R; oL++; }
+            else { if (oS < cap) tab[cap - 1 - oS] = R; oS++; }
         }
         __syncthreads();
     }
 }
-// chain number e (long ones first) -> cluster id
-__device__ __forceinline__ unsigned chain_at(const unsigned *__restrict__ list, unsigned long long cap, unsigned long long n_long, unsigned long long e) {
-    return e < n_long ? list[e] : list[cap - 1 - (e - n_long)];
+// chain number e (long ones first) -> its record
+__device__ __forceinline__ ChainRec chain_at(const ChainRec *__restrict__ tab, unsigned long long cap, unsigned long long n_long, unsigned long long e) {
+    return e < n_long ? tab[e] : tab[cap - 1 - (e - n_long)];
 }
 
 #include "hite_ext.h"
@@ -807,9 +949,7 @@ using ExtState = ExtStateT<ExtCopyMode>;
 // and a lane that has finished takes the next task from the queue while its neighbours go on (the lengths run from 0 to
 // thousands of columns: with a fixed task per thread every wavefront waited for its longest).  Refill when a quarter of
 // the lanes is idle, so that the set-up code is paid for 16 tasks at a time.
-__global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long long *__restrict__ counters, const unsigned *__restrict__ list,
-                                                           const unsigned long long *__restrict__ hkey, HitFmt F, const unsigned *__restrict__ c_first,
-                                                           const unsigned long long *__restrict__ c_lo, const unsigned long long *__restrict__ c_hi,
+__global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long long *__restrict__ counters, const ChainRec *__restrict__ tab,
                                                            const uint8_t *__restrict__ cand, const int64_t *__restrict__ cand_off,
                                                            const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask,
                                                            const int64_t *__restrict__ coff, int nc, unsigned long long cap,
@@ -838,14 +978,13 @@ __global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long l
             if (!active) {
                 const unsigned long long t = base + (unsigned long long)__popcll(idle & ((1ull << lane) - 1ull));
                 if (t < ntask) {
-                    const unsigned k = chain_at(list, cap, n_long, t >> 1);
+                    const ChainRec R = chain_at(tab, cap, n_long, t >> 1);
                     const int side = (int)(t & 1ull);
-                    const unsigned long long key = hkey[c_first[k]];
-                    const unsigned c = hit_cand(F, key), rel = hit_rel(F, key);
+                    const unsigned c = R.cs >> 1, rel = R.cs & 1u;
                     const int64_t qb = cand_off[c];
                     const int Lq = (int)(cand_off[c + 1] - qb);
-                    const long long qlo = (long long)(c_lo[k] >> 32), glo = (long long)(c_lo[k] & 0xffffffffull);
-                    const long long qhi = (long long)(c_hi[k] >> 32), ghi = (long long)(c_hi[k] & 0xffffffffull);
+                    const long long qlo = (long long)(R.lo >> 32), glo = (long long)(R.lo & 0xffffffffull);
+                    const long long qhi = (long long)(R.hi >> 32), ghi = (long long)(R.hi & 0xffffffffull);
                     const int ctg = contig_of(coff, nc, glo);
                     // the query in the orientation of the genome: rel = 1 reads the reverse complement of the candidate, x -> Lq - 1 - x
                     if (side == 0)        // x = qlo - 1, qlo - 2, ..., 0
@@ -879,10 +1018,8 @@ __global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long l
 // last aligned base, <= 5 % of the candidate: see the twin's header).
 template <bool WRITE>
 __global__ void __launch_bounds__(256) chain_copy_kernel(const unsigned long long *__restrict__ counters, unsigned long long cap,
-                                                         const unsigned *__restrict__ list, const int32_t *__restrict__ x_i,
-                                                         const int32_t *__restrict__ x_t, const unsigned long long *__restrict__ hkey, HitFmt F,
-                                                         const unsigned *__restrict__ c_first, const unsigned long long *__restrict__ c_lo,
-                                                         const unsigned long long *__restrict__ c_hi, const int64_t *__restrict__ cand_off,
+                                                         const ChainRec *__restrict__ tab, const int32_t *__restrict__ x_i,
+                                                         const int32_t *__restrict__ x_t, const int64_t *__restrict__ cand_off,
                                                          const int64_t *__restrict__ coff, int nc, unsigned long long *__restrict__ ckey,
                                                          unsigned *__restrict__ cval, int32_t *__restrict__ r_contig, int64_t *__restrict__ r_s1,
                                                          int64_t *__restrict__ r_e1, uint8_t *__restrict__ r_minus, int32_t *__restrict__ r_anch,
@@ -893,13 +1030,12 @@ __global__ void __launch_bounds__(256) chain_copy_kernel(const unsigned long lon
     if (n_long + n_short > cap) n_short = cap - n_long;
     const unsigned long long nch = n_long + n_short;
     for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < nch; e += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned k = chain_at(list, cap, n_long, e);
-        const int na = (int)(c_first[k + 1] - c_first[k]);
-        const unsigned long long key = hkey[c_first[k]];
-        const unsigned c = hit_cand(F, key), rel = hit_rel(F, key);
+        const ChainRec R = chain_at(tab, cap, n_long, e);
+        const int na = (int)R.na;
+        const unsigned c = R.cs >> 1, rel = R.cs & 1u;
         const long long Lq = cand_off[c + 1] - cand_off[c];
-        const long long qlo = (long long)(c_lo[k] >> 32), glo = (long long)(c_lo[k] & 0xffffffffull);
-        const long long qhi = (long long)(c_hi[k] >> 32), ghi = (long long)(c_hi[k] & 0xffffffffull);
+        const long long qlo = (long long)(R.lo >> 32), glo = (long long)(R.lo & 0xffffffffull);
+        const long long qhi = (long long)(R.hi >> 32), ghi = (long long)(R.hi & 0xffffffffull);
         const long long clip_l = qlo - x_i[2 * e], clip_r = Lq - (qhi + CK) - x_i[2 * e + 1];
         const long long aligned = Lq - clip_l - clip_r;
         const long long a0 = glo - x_t[2 * e], a1 = ghi + CK + x_t[2 * e + 1];          // genome interval of the aligned part
@@ -1211,10 +1347,10 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
     if (n_cand == 0 || cand_bytes <= 0 || S->M == 0) return HITE_OK;
     // candidate minimizers
     unsigned long long qcap = (unsigned long long)(cand_bytes * 0.32) + 4096 + (unsigned long long)n_cand;
-    unsigned *q_c, *q_pos, *q_hs, *occ_lo, *hval, *c_first, *cval;
-    int32_t *occ_n, *flag, *per_cand, *per_cand300;
-    int64_t *hit_off, *cid, *bs, *cstart, *ofirst;
-    unsigned long long *hkey, *c_lo, *c_hi, *ckey;
+    unsigned *q_c, *q_pos, *q_hs, *occ_lo, *hval, *cval;
+    int32_t *occ_n, *per_cand, *per_cand300;
+    int64_t *hit_off, *bs, *cstart, *ofirst;
+    unsigned long long *hkey, *ckey;
     CCHK(arena_alloc(ctx, A, qcap * 4, &p)); q_c = (unsigned *)p;
     CCHK(arena_alloc(ctx, A, qcap * 4, &p)); q_pos = (unsigned *)p;
     CCHK(arena_alloc(ctx, A, qcap * 4, &p)); q_hs = (unsigned *)p;
@@ -1291,92 +1427,100 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
     }
     Sorter so;
     CCHK(sorter_from_arena(so, ctx, A, st, nh));
-    int tk_sh = hite_prof_begin(ctx, "radix_sort_hits", st);
-    {   // the key has a hole: the diagonal (gpos - qo + DBIAS < n_bases + DBIAS) rarely needs its 33 bits.  Two runs of stable
-        // passes -- the diagonal's bits, then strand + candidate -- take 3 + 2 passes at 1 Gbp / 2^17 candidates where the
-        // 51-bit key as a whole takes 6; the sorted pair of buffers is taken over instead of copied back
-        static const bool seg_sort = [] { const char *e = getenv("HITE_HIT_SEGSORT"); return !(e && *e && atoi(e) == 0); }();
-        if (F.qbits && seg_sort) {
-            // per-candidate sort in LDS (above): classify, then one launch per class
-            unsigned *hs_counts; int32_t *hs_lists;
-            CCHK(arena_alloc(ctx, A, 16, &p)); hs_counts = (unsigned *)p;
-            CCHK(arena_alloc(ctx, A, (size_t)HS_NCLS * n_cand * 4 + 16, &p)); hs_lists = (int32_t *)p;
-            HITE_CHECK(ctx, hipMemsetAsync(hs_counts, 0, 16, st));
-            hipLaunchKernelGGL(hit_sort_classify_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, q_first, hit_off, hs_counts, hs_lists);
-            static unsigned long long attr_done = 0ull;      // bit = device id: the attribute belongs to the device the kernel runs on
-            const unsigned long long dev_bit = 1ull << (ctx->device & 63);
-            if (!(attr_done & dev_bit)) {
-                HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&hit_segsort_kernel<HS_MEDIUM, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HS_MEDIUM * 8));
-                attr_done |= dev_bit;
-            }
-            const int sbits = dbits + 1;
-            const int gsm = n_cand < 8192 ? n_cand : 8192, gmd = n_cand < 2048 ? n_cand : 2048, glg = n_cand < 1024 ? n_cand : 1024;
-            // the few large ranges (long chains, 32 KB of LDS each) run on a side stream beside the small ones; the medium class
-            // takes a CU's whole LDS and follows on the main stream
-            hipStream_t sside[HITE_AUX_STREAMS];
-            hipEvent_t ev_fork, ev_join[HITE_AUX_STREAMS];
-            CCHK(hite_aux_streams(ctx, 1, sside, &ev_fork, ev_join));
-            HITE_CHECK(ctx, hipEventRecord(ev_fork, st));
-            HITE_CHECK(ctx, hipStreamWaitEvent(sside[0], ev_fork, 0));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<0, 512>), dim3(glg), dim3(512), 0, sside[0], hs_counts + 3, hs_lists + (size_t)3 * n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_SMALL, 256>), dim3(gsm), dim3(256), 2 * HS_SMALL * 8, st, hs_counts, hs_lists, q_first, hit_off, hkey, so.k2, F.qbits, sbits);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MID, 256>), dim3(gmd), dim3(256), 2 * HS_MID * 8, st, hs_counts + 1, hs_lists + (size_t)n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MEDIUM, 512>), dim3(gmd), dim3(512), 2 * HS_MEDIUM * 8, st, hs_counts + 2, hs_lists + (size_t)2 * n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits);
-            HITE_CHECK(ctx, hipEventRecord(ev_join[0], sside[0]));
-            HITE_CHECK(ctx, hipStreamWaitEvent(st, ev_join[0], 0));
-            HITE_CHECK(ctx, hipGetLastError());
-        } else if (F.qbits) {
-            CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, F.qbits, F.qbits + dbits));
-            CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, F.qbits + dbits, F.qbits + dbits + 1 + cbits));
-        } else {
-            CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, 0, dbits));
-            CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, 33, 34 + cbits));
-            F.hval = hval;
-        }
-    }
-    hite_prof_end(ctx, tk_sh, st);
-    // clusters
-    CCHK(arena_alloc(ctx, A, (size_t)(nh + 1) * 4, &p)); flag = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(nh + 2) * 8, &p)); cid = (int64_t *)p;
-    int64_t *bs2;
-    CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(nh) * 8, &p)); bs2 = (int64_t *)p;
-    int tk_cluster_flag_kernel = hite_prof_begin(ctx, "cluster_flag_kernel", st);
-    hipLaunchKernelGGL(cluster_flag_kernel, CGRID(nh), 0, st, nh, hkey, F, ctx->d_contig_off, ctx->n_contigs, flag);
-    hite_prof_end(ctx, tk_cluster_flag_kernel, st);
-    CCHK(scan_excl_buf<int32_t>(ctx, bs2, flag, nh, cid, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, cid + nh, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(read_back(ctx, S, st, 1));
-    const int64_t ncl = S->h_pin[0];
-    S->last[2] = ncl;
-    CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 8, &p)); c_lo = (unsigned long long *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 8, &p)); c_hi = (unsigned long long *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(ncl + 2) * 4, &p)); c_first = (unsigned *)p;
-    hipLaunchKernelGGL(cluster_first_kernel, CGRID(nh), 0, st, nh, flag, cid, c_first, ncl);
-    int tk_cluster_acc_kernel = hite_prof_begin(ctx, "cluster_acc_kernel", st);
-    hipLaunchKernelGGL(cluster_acc_init_kernel, CGRID(ncl), 0, st, ncl, c_lo, c_hi);
-    hipLaunchKernelGGL(cluster_acc_kernel, CGRID(nh), 0, st, nh, hkey, F, flag, cid, c_lo, c_hi);
-    hite_prof_end(ctx, tk_cluster_acc_kernel, st);
-    // chains -> end extension -> copies.  The chain list is sized for the worst case (every chain needs >= 3 hits); its length
+    // chains -> end extension -> copies.  The chain table is sized for the worst case (every chain needs >= 3 hits); its length
     // stays on the device (the kernels behind it run grid-stride loops up to the count they read there)
     const unsigned long long chcap = (unsigned long long)(nh / C_MINANCH) + 1;
-    unsigned *chain_list; int32_t *x_i, *x_t;
-    CCHK(arena_alloc(ctx, A, (size_t)chcap * 4, &p)); chain_list = (unsigned *)p;
+    ChainRec *chain_tab;
+    CCHK(arena_alloc(ctx, A, (size_t)chcap * sizeof(ChainRec), &p)); chain_tab = (ChainRec *)p;
+    unsigned long long *d_ncl = (unsigned long long *)(S->d_scal + 2);        // clusters, counted on the device by the per-candidate sort
+    unsigned long long *d_nchain = (unsigned long long *)(S->d_scal + 4);     // [0] long chains, [1] short chains, [2] task queue
+    static const bool seg_sort = [] { const char *e = getenv("HITE_HIT_SEGSORT"); return !(e && *e && atoi(e) == 0); }();
+    const bool fused = F.qbits && seg_sort;      // packed hits: the per-candidate sort writes the chain table itself
+    int tk_sh = hite_prof_begin(ctx, "radix_sort_hits", st);
+    if (fused) {
+        // per-candidate sort in LDS (above) with the chains as its epilogue: classify, then one launch per class.  No flag, cluster
+        // id or cluster array, no sorted hits written back, and no read-back of the cluster count: it arrives with the copy counts
+        unsigned *hs_counts; int32_t *hs_lists;
+        CCHK(arena_alloc(ctx, A, 16, &p)); hs_counts = (unsigned *)p;
+        CCHK(arena_alloc(ctx, A, (size_t)HS_NCLS * n_cand * 4 + 16, &p)); hs_lists = (int32_t *)p;
+        HITE_CHECK(ctx, hipMemsetAsync(hs_counts, 0, 16, st));
+        HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
+        hipLaunchKernelGGL(hit_sort_classify_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, q_first, hit_off, hs_counts, hs_lists, d_ncl);
+        static unsigned long long attr_done = 0ull;      // bit = device id: the attribute belongs to the device the kernel runs on
+        const unsigned long long dev_bit = 1ull << (ctx->device & 63);
+        if (!(attr_done & dev_bit)) {
+            HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&hit_segsort_kernel<HS_MEDIUM, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HS_MEDIUM * 8));
+            attr_done |= dev_bit;
+        }
+        const int sbits = dbits + 1;
+        const int gsm = n_cand < 8192 ? n_cand : 8192, gmd = n_cand < 2048 ? n_cand : 2048, glg = n_cand < 1024 ? n_cand : 1024;
+        // the few large ranges (long chains, 32 KB of LDS each) run on a side stream beside the small ones; the medium class
+        // takes a CU's whole LDS and follows on the main stream
+        hipStream_t sside[HITE_AUX_STREAMS];
+        hipEvent_t ev_fork, ev_join[HITE_AUX_STREAMS];
+        CCHK(hite_aux_streams(ctx, 1, sside, &ev_fork, ev_join));
+        HITE_CHECK(ctx, hipEventRecord(ev_fork, st));
+        HITE_CHECK(ctx, hipStreamWaitEvent(sside[0], ev_fork, 0));
+#define HS_CHAIN_ARGS d_cand_off, ctx->d_contig_off, ctx->n_contigs, chain_tab, chcap, d_nchain, d_ncl
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<0, 512>), dim3(glg), dim3(512), 0, sside[0], hs_counts + 3, hs_lists + (size_t)3 * n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_SMALL, 256>), dim3(gsm), dim3(256), 2 * HS_SMALL * 8, st, hs_counts, hs_lists, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MID, 256>), dim3(gmd), dim3(256), 2 * HS_MID * 8, st, hs_counts + 1, hs_lists + (size_t)n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MEDIUM, 512>), dim3(gmd), dim3(512), 2 * HS_MEDIUM * 8, st, hs_counts + 2, hs_lists + (size_t)2 * n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
+#undef HS_CHAIN_ARGS
+        HITE_CHECK(ctx, hipEventRecord(ev_join[0], sside[0]));
+        HITE_CHECK(ctx, hipStreamWaitEvent(st, ev_join[0], 0));
+        HITE_CHECK(ctx, hipGetLastError());
+    } else if (F.qbits) {
+        // the key has a hole: the diagonal (gpos - qo + DBIAS < n_bases + DBIAS) rarely needs its 33 bits.  Two runs of stable
+        // passes -- the diagonal's bits, then strand + candidate -- take 3 + 2 passes at 1 Gbp / 2^17 candidates where the
+        // 51-bit key as a whole takes 6; the sorted pair of buffers is taken over instead of copied back
+        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, F.qbits, F.qbits + dbits));
+        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, F.qbits + dbits, F.qbits + dbits + 1 + cbits));
+    } else {
+        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, 0, dbits));
+        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, 33, 34 + cbits));
+        F.hval = hval;
+    }
+    hite_prof_end(ctx, tk_sh, st);
+    int32_t *x_i, *x_t;
     CCHK(arena_alloc(ctx, A, (size_t)chcap * 8, &p)); x_i = (int32_t *)p;
     CCHK(arena_alloc(ctx, A, (size_t)chcap * 8, &p)); x_t = (int32_t *)p;
-    HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
-    unsigned long long *d_nchain = (unsigned long long *)(S->d_scal + 4);     // [0] long chains, [1] short chains, [2] task queue
-    int tk_ext = hite_prof_begin(ctx, "chain_extend_kernel", st);
-    {
+    int64_t ncl = -1;                            // fused: known with the final read-back
+    int tk_ext;
+    if (!fused) {
+        // clusters of the globally sorted hits (12-byte hits, HITE_HIT_SEGSORT=0): flags, ids, extreme anchors, then the same chain
+        // table.  The default path has none of these arrays
+        int32_t *flag; int64_t *cid, *bs2; unsigned *c_first; unsigned long long *c_lo, *c_hi;
+        CCHK(arena_alloc(ctx, A, (size_t)(nh + 1) * 4, &p)); flag = (int32_t *)p;
+        CCHK(arena_alloc(ctx, A, (size_t)(nh + 2) * 8, &p)); cid = (int64_t *)p;
+        CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(nh) * 8, &p)); bs2 = (int64_t *)p;
+        int tk_cluster_flag_kernel = hite_prof_begin(ctx, "cluster_flag_kernel", st);
+        hipLaunchKernelGGL(cluster_flag_kernel, CGRID(nh), 0, st, nh, hkey, F, ctx->d_contig_off, ctx->n_contigs, flag);
+        hite_prof_end(ctx, tk_cluster_flag_kernel, st);
+        CCHK(scan_excl_buf<int32_t>(ctx, bs2, flag, nh, cid, st));
+        HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, cid + nh, 8, hipMemcpyDeviceToDevice, st));
+        CCHK(read_back(ctx, S, st, 1));
+        ncl = S->h_pin[0];
+        CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 8, &p)); c_lo = (unsigned long long *)p;
+        CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 8, &p)); c_hi = (unsigned long long *)p;
+        CCHK(arena_alloc(ctx, A, (size_t)(ncl + 2) * 4, &p)); c_first = (unsigned *)p;
+        hipLaunchKernelGGL(cluster_first_kernel, CGRID(nh), 0, st, nh, flag, cid, c_first, ncl);
+        int tk_cluster_acc_kernel = hite_prof_begin(ctx, "cluster_acc_kernel", st);
+        hipLaunchKernelGGL(cluster_acc_init_kernel, CGRID(ncl), 0, st, ncl, c_lo, c_hi);
+        hipLaunchKernelGGL(cluster_acc_kernel, CGRID(nh), 0, st, nh, hkey, F, flag, cid, c_lo, c_hi);
+        hite_prof_end(ctx, tk_cluster_acc_kernel, st);
+        HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
+        tk_ext = hite_prof_begin(ctx, "chain_extend_kernel", st);
         int64_t lblocks = (ncl + 256 * CL_ITEMS - 1) / (256 * CL_ITEMS);
         if (lblocks > 16384) lblocks = 16384;
         if (lblocks < 1) lblocks = 1;
-        hipLaunchKernelGGL(chain_list_kernel, dim3((unsigned)lblocks), dim3(256), 0, st, ncl, hkey, F, c_first, c_lo, c_hi, d_cand_off, chain_list, chcap, d_nchain);
-    }
+        hipLaunchKernelGGL(chain_list_kernel, dim3((unsigned)lblocks), dim3(256), 0, st, ncl, hkey, F, c_first, c_lo, c_hi, d_cand_off, chain_tab, chcap, d_nchain);
+    } else tk_ext = hite_prof_begin(ctx, "chain_extend_kernel", st);
     {
         // persistent lanes: every lane takes (chain, end) tasks from the queue until it is empty
         unsigned long long want_blocks = (2ull * chcap + 255ull) / 256ull;
         const unsigned eblocks = (unsigned)(want_blocks < 2048ull ? (want_blocks ? want_blocks : 1ull) : 2048ull);
-        hipLaunchKernelGGL(chain_extend_kernel, dim3(eblocks), dim3(256), 0, st, d_nchain, chain_list, hkey, F, c_first, c_lo, c_hi, d_cand,
+        hipLaunchKernelGGL(chain_extend_kernel, dim3(eblocks), dim3(256), 0, st, d_nchain, chain_tab, d_cand,
                            d_cand_off, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off, ctx->n_contigs, chcap, d_nchain + 2, x_i, x_t);
     }
     hite_prof_end(ctx, tk_ext, st);
@@ -1407,12 +1551,10 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
     {
         unsigned long long want_blocks = (chcap + 255ull) / 256ull;
         const unsigned cblocks = (unsigned)(want_blocks < 8192ull ? (want_blocks ? want_blocks : 1ull) : 8192ull);
-        hipLaunchKernelGGL(chain_copy_kernel<false>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_list, x_i, x_t, hkey, F, c_first, c_lo,
-                           c_hi, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, per_cand,
+        hipLaunchKernelGGL(chain_copy_kernel<false>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_tab, x_i, x_t, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, per_cand,
                            (const int64_t *)nullptr, copy_interval_mode(ctx));
         CCHK(scan_excl_buf<int32_t>(ctx, bs3, per_cand, n_cand, cstart, st));
-        hipLaunchKernelGGL(chain_copy_kernel<true>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_list, x_i, x_t, hkey, F, c_first, c_lo,
-                           c_hi, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, fill,
+        hipLaunchKernelGGL(chain_copy_kernel<true>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_tab, x_i, x_t, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, fill,
                            (const int64_t *)cstart, copy_interval_mode(ctx));
     }
     hite_prof_end(ctx, tk_cluster_copy_kernel, st);
@@ -1422,6 +1564,7 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 1, ofirst + n_cand, 8, hipMemcpyDeviceToDevice, st));
     CCHK(read_back(ctx, S, st, 8));
     const int64_t ncp = S->h_pin[0], nout = S->h_pin[1];
+    S->last[2] = fused ? S->h_pin[2] : ncl;
     S->last[4] = S->h_pin[4]; S->last[5] = S->h_pin[5]; S->last[6] = S->h_pin[7];
     *n_copies = nout;
     S->last[3] = ncp;
