@@ -90,6 +90,24 @@ def gen_fmea(U, tmp):
                              sha256=hashlib.sha256("\n".join(names).encode()).hexdigest()))
 
 
+def gen_fmea_limits(U, tmp):
+    """the small tables of tests/fmea_limit_cases.py (sweep rounds, length and key limits, the filter's threshold pairs, the rank
+    cases of 3 and 257 segments) through the reference's get_longest_repeats_v4: rows + segment places + the names it keys"""
+    import fmea_limit_cases as FC
+
+    recs = []
+    for label, c in FC.fixture_cases():
+        seg = FC.segment_names(c)
+        assert len(set(seg)) == len(seg), label
+        rows = [(seg[q], seg[s], qs, qe, ss, se) for q, s, qs, qe, ss, se in FC.rows_of(c).tolist()]
+        p = os.path.join(tmp, "fmea_limits.out")
+        with open(p, "w") as f:
+            f.writelines(casegen.hsp_to_blast6_lines(rows))
+        names = list(U.load_from_file(U.get_longest_repeats_v4(p, c["skip_gap"], c["max_len"], 0)).keys())
+        recs.append(FC.fixture_record(label, c, names))
+    dump("fmea_limits", recs)
+
+
 def run_msa_case(U, tmp, case):
     raw = os.path.join(tmp, "aln.fa")
     write_fasta(raw, case["names"], case["seqs"])
@@ -1528,10 +1546,12 @@ def main():
     assert os.environ.get("PYTHONHASHSEED") == "0", "run with PYTHONHASHSEED=0"
     U = ref_harness.load_reference_util()
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["fmea", "judge", "search", "tsd", "kmer", "gather", "tails", "host", "ltr", "nonltr", "qcopies", "libdedup", "bothends", "split", "bucketing", "consv1", "trf", "rfm", "chainvar", "edge", "itr", "lcr"]
+    which = sys.argv[1:] or ["fmea", "judge", "search", "tsd", "kmer", "gather", "tails", "host", "ltr", "nonltr", "qcopies", "libdedup", "bothends", "split", "bucketing", "consv1", "trf", "rfm", "chainvar", "edge", "itr", "lcr", "fmea_limits"]
     with tempfile.TemporaryDirectory() as tmp:
         if "fmea" in which:
             gen_fmea(U, tmp)
+        if "fmea_limits" in which:
+            gen_fmea_limits(U, tmp)
         if "judge" in which:
             gen_judge(U, tmp)
         if "search" in which:

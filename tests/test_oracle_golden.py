@@ -16,6 +16,17 @@ def test_fmea_golden():
         assert got == case["expected"]
 
 
+def test_fmea_limits_golden():
+    """the twin on the reference's answers for the small FMEA limit tables (sweep rounds, length and key limits, threshold pairs of
+    the containment filter, rank cases): tests/fmea_limit_cases.py builds them with segment ids that are not their ranks"""
+    import fmea_limit_cases as FC
+
+    recs = load_golden("fmea_limits")
+    assert len(recs) >= 40
+    for rec in recs:
+        assert FC.twin_names(FC.case_of_record(rec)) == rec["expected"], rec["label"]
+
+
 def test_sparse_cols_golden():
     n = 0
     for name in ("judge_tir", "judge_non_ltr", "judge_helitron"):
