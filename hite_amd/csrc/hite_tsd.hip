@@ -2,7 +2,8 @@
 // (/root/reference/module/Util.py:7734-7845; batch driver search_confident_tir_batch_v1 :6533).
 //
 // One wavefront per flanked candidate.  For each k in {2,3,4,5,6,8,9,10,11} the k-mers of the two
-// +-dist windows around the raw boundaries become 3-bit-per-base codes in LDS (A C G T N/other),
+// +-dist windows around the raw boundaries become 3-bit-per-base codes in LDS (A C G T other: a code that holds
+// an "other" is equal for different bytes, R / Y / N ..., and is confirmed on the bytes; the reference compares strings),
 // lanes own right-window positions and scan the left codes (the reference's dict keeps, per k-mer,
 // the left occurrence closest to the raw start and the running closest right occurrence), records
 // are de-duplicated with the set semantics of TSD_set, filtered (NN, length < 100, TG..CA,
@@ -11,8 +12,11 @@
 // Integer / byte work only; per candidate ~(len+100) bytes in, <= 1.6 KB out: latency bound.
 #include "hite_common.h"
 
-#define TW 128        // max window length (2*dist+1 <= 101 in every reference call)
-#define MAXREC 1024   // 9 k values x <= 101 right positions
+#define TW 128        // max window length (2*dist+1 <= 101 in every reference call; the entry point takes dist <= 63: 127)
+// Records of one candidate before the cut.  A record belongs to one (k, right position), so at dist 63 (windows of 127): the seven
+// k other than 2 and 4 have at most 125 + 123 + 122 + 120 + 119 + 118 + 117 = 844 right positions, k = 2 at most 126, and k = 4
+// needs TTAA at the right position, which 127 bases hold at most 31 times: 1001 < MAXREC, the slot guard below never drops one.
+#define MAXREC 1024
 
 struct TsdShared {
     unsigned long long lcode[TW], rcode[TW];
@@ -23,7 +27,17 @@ struct TsdShared {
 };
 
 __device__ __forceinline__ unsigned code3(uint8_t c) {
-    switch (c) { case 'A': return 1; case 'C': return 2; case 'G': return 3; case 'T': return 4; default: return 5; }  /* N and every folded byte */
+    switch (c) { case 'A': return 1; case 'C': return 2; case 'G': return 3; case 'T': return 4; default: return 5; }  /* every other byte: N, R, Y ... */
+}
+// does the code of a k-mer hold a 5?  Only then can equal codes stand for different bytes.
+__device__ __forceinline__ bool code_has_other(unsigned long long code, int k) {
+    bool o = false;
+    for (int q = 0; q < k; q++) o = o || ((code >> (3 * q)) & 7) == 5;
+    return o;
+}
+__device__ __forceinline__ bool same_kmer(const uint8_t *a, const uint8_t *b, int k) {
+    for (int q = 0; q < k; q++) if (a[q] != b[q]) return false;
+    return true;
 }
 
 __global__ void __launch_bounds__(64) tsd_kmer_kernel(int n, const uint8_t *__restrict__ seqs, const int64_t *__restrict__ seq_off,
@@ -62,10 +76,11 @@ __global__ void __launch_bounds__(64) tsd_kmer_kernel(int n, const uint8_t *__re
             const unsigned long long rc = S.rcode[i];
             const int cur_pos = rs + i - 1;
             if (rc != 0 && cur_pos >= 0 && cur_pos <= len - 1) {
+                const bool other = code_has_other(rc, k);
                 // left_pos: occurrence closest to raw_start, first wins ties (Util.py:7769-7777)
                 int best = -1, bd = 0;
                 for (int j = 0; j + k <= llen; j++) {
-                    if (S.lcode[j] != rc) continue;
+                    if (S.lcode[j] != rc || (other && !same_kmer(seq + ls + j, seq + rs + i, k))) continue;
                     int lp = ls + j + k;
                     if (lp < 0 || lp > len - 1) continue;
                     int d = lp - raw_start; if (d < 0) d = -d;
@@ -75,7 +90,7 @@ __global__ void __launch_bounds__(64) tsd_kmer_kernel(int n, const uint8_t *__re
                     // right_pos at the time this occurrence is visited: best among right occurrences 0..i (:7788-7794)
                     int rb = -1, rd = 0;
                     for (int j = 0; j <= i; j++) {
-                        if (S.rcode[j] != rc) continue;
+                        if (S.rcode[j] != rc || (other && !same_kmer(seq + rs + j, seq + rs + i, k))) continue;
                         int rp = rs + j - 1;
                         if (rp < 0 || rp > len - 1) continue;
                         int d = rp - raw_end; if (d < 0) d = -d;
@@ -103,8 +118,10 @@ __global__ void __launch_bounds__(64) tsd_kmer_kernel(int n, const uint8_t *__re
             const int ts = S.lpos_best[i], te = S.rpos_best[i];
             if (ts < 0) continue;
             const unsigned long long rc = S.rcode[i];
+            const bool other = code_has_other(rc, k);
             bool dup = false;
-            for (int j = 0; j < i; j++) if (S.rcode[j] == rc && S.lpos_best[j] == ts && S.rpos_best[j] == te) { dup = true; break; }
+            for (int j = 0; j < i; j++)
+                if (S.rcode[j] == rc && S.lpos_best[j] == ts && S.rpos_best[j] == te && (!other || same_kmer(seq + rs + j, seq + rs + i, k))) { dup = true; break; }
             if (dup) continue;
             bool nn = false;
             for (int q = 0; q + 1 < k; q++) if (seq[rs + i + q] == 'N' && seq[rs + i + q + 1] == 'N') nn = true;

@@ -260,7 +260,9 @@ int hite_ltr_both_ends(hite_ctx *ctx, int32_t n, const uint8_t *msa, const int64
  * search_confident_tir_batch_v1 passes them (Util.py:6550), tsd_search_distance = flank (<= 63).
  * Per candidate up to 100 records (tsd_len, tir_start, tir_end, distance), 0-based inclusive, in the
  * canonical order (distance, tir_start, tir_end, tsd_len) that replaces the reference's
- * PYTHONHASHSEED-dependent tie order; rec_out is n x 100 x 4 int32, cnt_out[n] (-1: window too long). */
+ * PYTHONHASHSEED-dependent tie order; rec_out is n x 100 x 4 int32, cnt_out[n] (-1: window too long).
+ * Any byte is a letter of its own, as in the reference's string compare: a k-mer with R never pairs with
+ * the same k-mer with Y or N (the sequences are not folded; the "NN" filter is literal). */
 int hite_tsd_kmer(hite_ctx *ctx, int32_t n, const uint8_t *seqs, const int64_t *seq_off, int32_t flank, int32_t plant,
                   int32_t *rec_out, int32_t *cnt_out);
 int hite_tsd_kmer_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_seqs, const int64_t *d_seq_off, int32_t flank,

@@ -108,6 +108,31 @@ def gen_fmea_limits(U, tmp):
     dump("fmea_limits", recs)
 
 
+def gen_tsd_limits(U):
+    """a thinned set of the small cases of tests/tsd_limit_cases.py through the reference's search_confident_tir_v4 and
+    search_polyA_TSD: inputs + what the reference returned (k-mer cases at the cut: only the items closer than the farthest kept)"""
+    import tsd_limit_cases as TC
+
+    recs = []
+    for c in TC.fixture_cases():
+        seq, flank = c["seq"], c["flank"]
+        if c["kind"] == "kmer":
+            res = U.search_confident_tir_v4(seq, flank + 1, len(seq) - flank, flank, "q", c["plant"])
+            items = []
+            for name, s in res.items():
+                parts = name.split("-")
+                tsd = [p for p in parts if p.startswith("tsd_")][0][4:]
+                dist = int([p for p in parts if p.startswith("distance_")][0][9:])
+                items.append([dist, tsd, s])
+            recs.append(dict(c, **TC.fixture_kmer_result(items)))
+        else:
+            found, tsd_seq, nl = U.search_polyA_TSD(seq, flank, c["win5"], list(range(8, 21)))
+            recs.append(dict(c, found=bool(found), tsd=tsd_seq, non_ltr=nl))
+    print("tsd_limits:", len(recs), "cases,", sum(r["kind"] == "kmer" for r in recs), "k-mer,", sum(r.get("n", 0) >= TC.TOP for r in recs), "at the cut,",
+          sum(bool(r.get("found")) for r in recs), "with a non-LTR TSD")
+    dump("tsd_limits", recs)
+
+
 def run_msa_case(U, tmp, case):
     raw = os.path.join(tmp, "aln.fa")
     write_fasta(raw, case["names"], case["seqs"])
@@ -1546,12 +1571,14 @@ def main():
     assert os.environ.get("PYTHONHASHSEED") == "0", "run with PYTHONHASHSEED=0"
     U = ref_harness.load_reference_util()
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["fmea", "judge", "search", "tsd", "kmer", "gather", "tails", "host", "ltr", "nonltr", "qcopies", "libdedup", "bothends", "split", "bucketing", "consv1", "trf", "rfm", "chainvar", "edge", "itr", "lcr", "fmea_limits"]
+    which = sys.argv[1:] or ["fmea", "judge", "search", "tsd", "kmer", "gather", "tails", "host", "ltr", "nonltr", "qcopies", "libdedup", "bothends", "split", "bucketing", "consv1", "trf", "rfm", "chainvar", "edge", "itr", "lcr", "fmea_limits", "tsd_limits"]
     with tempfile.TemporaryDirectory() as tmp:
         if "fmea" in which:
             gen_fmea(U, tmp)
         if "fmea_limits" in which:
             gen_fmea_limits(U, tmp)
+        if "tsd_limits" in which:
+            gen_tsd_limits(U)
         if "judge" in which:
             gen_judge(U, tmp)
         if "search" in which:

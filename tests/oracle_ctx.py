@@ -40,7 +40,17 @@ class OracleCtx:
         return O.itr_search(seqs, end_len, min_identity, min_len, match, mismatch, gap_open, gap_extend)
 
     def tsd_kmer(self, seqs, flank=50, plant=1):
-        return [O.tir_kmer(s, flank + 1, len(s) - flank, flank, plant) for s in seqs]
+        """as Context.tsd_kmer: flanks outside 0..63 are refused; a candidate no longer than one flank has no record (the twin
+        itself refuses a raw end before the sequence)"""
+        if not 0 <= flank <= 63:
+            raise RuntimeError("tsd_kmer: flank %d" % flank)
+        return [O.tir_kmer(s, flank + 1, len(s) - flank, flank, plant) if len(s) > flank else [] for s in seqs]
+
+    def nonltr_prep(self, seqs, flank=50, win5=25):
+        """as Context.nonltr_prep: the twin's six numbers per sequence; the entry point's refusals"""
+        if flank < 0 or not 0 <= win5 <= 25:
+            raise RuntimeError("nonltr_prep: flank %d, win5 %d" % (flank, win5))
+        return O.nonltr_prep(seqs, flank, win5)
 
     def seed_shard(self, rank, world):
         self._shard = (int(rank), int(world))

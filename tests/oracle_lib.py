@@ -361,15 +361,27 @@ def ltr_frame(rows, flank, window, side):
     return bool(ok), int(b.value)
 
 
+def nonltr_prep(seqs, flank=50, win5=25):
+    """the twin's six raw numbers per sequence, as hite_nonltr_prep returns them: (found_TSD, direct (0 none, 1 '+', 2 '-'), TSD start,
+    TSD length, lo, hi of non_ltr_seq).  One buffer for the whole batch, a 0 byte after every sequence."""
+    sb = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    buf = np.frombuffer(b"\0".join(sb) + b"\0", dtype=np.uint8)
+    base = buf.ctypes.data
+    out = np.zeros((max(1, len(sb)), 6), dtype=np.int64)
+    obase = out.ctypes.data
+    fn = lib().orc_search_polyA_TSD
+    fn.restype = None
+    pos = 0
+    for i, b in enumerate(sb):
+        fn(C.c_void_p(base + pos), C.c_int64(len(b)), int(flank), int(win5), C.c_void_p(obase + 48 * i))
+        pos += len(b) + 1
+    return [tuple(int(x) for x in out[i]) for i in range(len(sb))]
+
+
 def search_polyA_TSD(seq, flank=50, win5=25):
     """non-LTR candidate preparation (search_polyA_TSD, Util.py:10915) -> (found_TSD, TSD_seq, non_ltr_seq)"""
     b = seq.encode() if isinstance(seq, str) else bytes(seq)
-    buf = np.frombuffer(b + b"\0", dtype=np.uint8)
-    out = np.zeros(6, dtype=np.int64)
-    L = lib()
-    L.orc_search_polyA_TSD.restype = None
-    L.orc_search_polyA_TSD(_ptr(buf, u8p), C.c_int64(len(b)), int(flank), int(win5), _ptr(out, i64p))
-    found, direct, ts, tn, lo, hi = (int(x) for x in out)
+    found, direct, ts, tn, lo, hi = nonltr_prep([b], flank, win5)[0]
     s = b.decode()
     nl = s[lo:hi] if direct else ""
     if direct == 2:

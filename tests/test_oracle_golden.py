@@ -162,6 +162,19 @@ def test_tir_kmer_edge_golden():
         check_tir_items(items, case)
 
 
+def test_tsd_limits_golden():
+    """the twins of the k-mer TSD search and of search_polyA_TSD against the reference on the small cases of tests/tsd_limit_cases.py:
+    flanks other than 50, the cut at 100, bytes outside ACGT; win5 other than 25, sequences shorter than a flank, the wrapped window"""
+    import tsd_limit_cases as TC
+    from oracle_ctx import OracleCtx
+
+    recs = load_golden("tsd_limits")
+    assert sum(r["kind"] == "kmer" for r in recs) >= 150 and sum(r["kind"] == "nonltr" for r in recs) >= 300
+    assert sum(r.get("n", 0) >= 100 for r in recs) >= 5 and sum(bool(r.get("found")) for r in recs) >= 100
+    twin = OracleCtx()
+    TC.check_fixture(twin.tsd_kmer, twin.nonltr_prep, recs)
+
+
 def test_gather_golden():
     for case in load_golden("gather"):
         contigs = dict(zip(case["names"], case["seqs"]))
