@@ -11,6 +11,7 @@ SO_PATH = os.path.join(_HERE, "libhite_gpu.so")
 
 HITE_TE = {"tir": 0, "helitron": 1, "non_ltr": 2}
 INFO = {0: "", 1: "nb", 2: "fl1", 3: "EXC"}
+HITE_SUBCLUSTER_CHUNK = 64   # include/hite_gpu.h: rows per chunk of hite_msa_subcluster
 
 
 class HiteError(RuntimeError):
@@ -715,6 +716,47 @@ class Context:
         self._check(self.lib.hite_msa_consensus(self.h, nmat, _p(rows), _p(cols), _p(moff), _p(buf), _p(ooff), _p(cons), _p(clen)),
                     "hite_msa_consensus")
         return [cons[ooff[a]:ooff[a] + clen[a]].tobytes().decode("latin-1") for a in range(nmat)]
+
+    def msa_subcluster(self, alignments, cutoff=0.2):
+        """batch of alignments (each a list of equal-length byte strings or a 2-D uint8 array) -> per alignment the sub-clusters of its
+        rows, a list of lists of row indices in order of their leaders: the leader clustering include/hite_gpu.h defines
+        (hite_msa_subcluster; the value util.ninja_stand_in returns, where the reference runs Ninja)"""
+        nmat = len(alignments)
+        if nmat == 0:
+            self._check(self.lib.hite_msa_subcluster(self.h, 0, None, None, None, None, C.c_double(cutoff), None, None, None),
+                        "hite_msa_subcluster")
+            return []
+        rows = np.zeros(nmat, dtype=np.int32)
+        cols = np.zeros(nmat, dtype=np.int64)
+        flat = []
+        for a, al in enumerate(alignments):
+            if isinstance(al, np.ndarray):
+                if al.ndim != 2:
+                    raise ValueError("msa_subcluster: an alignment array has two dimensions")
+                rows[a], cols[a] = al.shape
+                flat.append(np.ascontiguousarray(al, dtype=np.uint8).reshape(-1))
+                continue
+            rb = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in al]
+            if any(len(r) != len(rb[0]) for r in rb):
+                raise ValueError("ragged alignment")
+            rows[a], cols[a] = len(rb), len(rb[0]) if rb else 0
+            flat.append(np.frombuffer(b"".join(rb), dtype=np.uint8))
+        buf = np.concatenate(flat + [np.zeros(16, dtype=np.uint8)])
+        moff = np.zeros(nmat + 1, dtype=np.int64)
+        np.cumsum(rows.astype(np.int64) * cols, out=moff[1:])
+        roff = np.zeros(nmat + 1, dtype=np.int64)
+        np.cumsum(rows, out=roff[1:])
+        sub = np.zeros(int(roff[-1]) + 1, dtype=np.int32)
+        nsub = np.zeros(nmat, dtype=np.int32)
+        self._check(self.lib.hite_msa_subcluster(self.h, nmat, _p(rows), _p(cols), _p(moff), _p(buf), C.c_double(cutoff), _p(roff), _p(sub),
+                                                 _p(nsub)), "hite_msa_subcluster")
+        sub, at, out = sub.tolist(), roff.tolist(), []
+        for a, k in enumerate(nsub.tolist()):
+            groups = [[] for _ in range(k)]
+            for r, g in enumerate(sub[at[a]:at[a + 1]]):
+                groups[g].append(r)
+            out.append(groups)
+        return out
 
     def ltr_both_ends(self, alignments, cur_seqs, flank):
         """FiLTR get_both_ends_frame on a batch: alignments = lists of equal-length rows, cur_seqs = terminal sequences ->

@@ -84,6 +84,8 @@ struct hite_ctx {
     const uint8_t *d_judge_cls;     // per alignment: JUDGE_CLS_* (NULL: hite_judge_dev classifies by itself)
     JudgeFuse judge_fuse;           // win == NULL: the LDS classes copy their alignment from d_msa
     void *fmea_arena;               // grow-only arena of the sort / sweep / chain routines of hite_fmea.hip (Arena *; hite_fmea_release)
+    int32_t subcluster_chunk;       // rows per chunk of hite_msa_subcluster: HITE_SUBCLUSTER_CHUNK or $HITE_SUBCLUSTER_CHUNK_ROWS (hite_ctx_create)
+    int64_t subcluster_batch_bytes; // alignment bytes it sends up at a time ($HITE_SUBCLUSTER_BATCH_BYTES; 0: its default)
 };
 void hite_fmea_release(hite_ctx *ctx);
 int hite_aux_streams(hite_ctx *ctx, int k, hipStream_t *st, hipEvent_t *fork_ev, hipEvent_t *join_ev);

@@ -24,6 +24,16 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
     if (!c) return HITE_ENOMEM;
     c->device = device_id;
     c->copy_interval = -1;
+    // test knobs of hite_msa_subcluster (hite_subcluster.hip), read here so that two contexts of a process may differ
+    c->subcluster_chunk = HITE_SUBCLUSTER_CHUNK;
+    if (const char *e = getenv("HITE_SUBCLUSTER_CHUNK_ROWS")) {
+        const long v = strtol(e, nullptr, 10);
+        if (v >= 1 && v <= HITE_SUBCLUSTER_CHUNK) c->subcluster_chunk = (int32_t)v;
+    }
+    if (const char *e = getenv("HITE_SUBCLUSTER_BATCH_BYTES")) {
+        const long long v = strtoll(e, nullptr, 10);
+        if (v >= 1) c->subcluster_batch_bytes = (int64_t)v;
+    }
     if (hipSetDevice(device_id) != hipSuccess) { free(c); return HITE_EHIP; }
     *out = c;
     return HITE_OK;

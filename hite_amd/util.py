@@ -20,6 +20,7 @@ import re
 import shutil
 import subprocess
 import sys
+import time
 
 import numpy as np
 
@@ -858,27 +859,50 @@ def _star_align_clusters(ctx, clusters):
     return out
 
 
-def _generate_cons_batch(ctx, clusters, ninja=None):
+def _subcluster_on(subcluster):
+    """the switch of the sub-clustering route of _generate_cons_batch: the argument, then $HITE_SUBCLUSTER; "gpu" is on"""
+    mode = subcluster if subcluster is not None else os.environ.get("HITE_SUBCLUSTER")
+    return mode == "gpu"
+
+
+def _generate_cons_batch(ctx, clusters, ninja=None, subcluster=None, seconds=None):
     """generate_cons_v1 (Util.py:12457-12498) for a batch of clusters, each a list of (name, sequence) in file order:
     alignment -> sub-clusters (Ninja in the reference, ninja_stand_in here; `ninja` = per cluster {id: [names]} overrides it,
     which is how the goldens pin everything around the external tool) -> alignment of every sub-cluster -> strict-majority
     consensus (cons_from_mafft_v1) named after the sub-cluster's LAST member.  A cluster that yields no consensus returns
-    its sequences unchanged; members the aligner dropped pass unchanged as well.  -> per cluster {name: sequence}."""
+    its sequences unchanged; members the aligner dropped pass unchanged as well.  -> per cluster {name: sequence}.
+    subcluster="gpu" (or HITE_SUBCLUSTER=gpu when the argument is None; anything else is off) takes the sub-clusters of ALL first
+    alignments from one Context.msa_subcluster call (hite_msa_subcluster: the same leader clustering on the device) instead of
+    ninja_stand_in cluster by cluster; the result is the same.  seconds: a dict that receives the wall seconds of the steps
+    (align_first, subcluster, align_second, consensus)."""
+    clock = time.perf_counter
+    t0 = clock()
     need_first = [ci for ci in range(len(clusters)) if ninja is None or ninja[ci] is None]
     first = dict(zip(need_first, _star_align_clusters(ctx, [clusters[ci] for ci in need_first])))
+    t1 = clock()
+    kept_names, mats = {}, {}
+    for ci in need_first:
+        rows = first[ci][0]
+        names = [n for n, _s in clusters[ci] if n in rows]
+        if names:
+            kept_names[ci] = names
+            mats[ci] = np.frombuffer("".join(rows[n] for n in names).encode(), dtype=np.uint8).reshape(len(names), -1)
+    order = sorted(mats)
+    if _subcluster_on(subcluster):
+        groups = dict(zip(order, ctx.msa_subcluster([mats[ci] for ci in order], NINJA_CUTOFF))) if order else {}
+    else:
+        groups = {ci: ninja_stand_in(mats[ci]) for ci in order}
+    t2 = clock()
     subs, owner = [], []
     passed = [dict() for _ in clusters]
     for ci, cl in enumerate(clusters):
         seq_of = dict(cl)
         if ci in first:
-            rows, dropped = first[ci]
-            for n in dropped:                # not placed in the cluster's alignment: passes unchanged
+            for n in first[ci][1]:           # not placed in the cluster's alignment: passes unchanged
                 passed[ci][n] = seq_of[n]
-            names = [n for n, _s in cl if n in rows]
-            if not names:
+            if ci not in groups:
                 continue
-            mat = np.frombuffer("".join(rows[n] for n in names).encode(), dtype=np.uint8).reshape(len(names), -1)
-            parts = [[names[r] for r in grp] for grp in ninja_stand_in(mat)]
+            parts = [[kept_names[ci][r] for r in grp] for grp in groups[ci]]
         else:
             parts = [list(ninja[ci][k]) for k in ninja[ci]]
         for part in parts:
@@ -886,6 +910,7 @@ def _generate_cons_batch(ctx, clusters, ninja=None):
                 subs.append([(n, seq_of[n]) for n in part])
                 owner.append(ci)
     second = _star_align_clusters(ctx, subs)
+    t3 = clock()
     als, who = [], []
     for si, (sub, (rows, dropped)) in enumerate(zip(subs, second)):
         for n in dropped:
@@ -895,6 +920,8 @@ def _generate_cons_batch(ctx, clusters, ninja=None):
             als.append([rows[n] for n in kept])
             who.append((owner[si], kept[-1]))
     cons = ctx.msa_consensus(als) if als else []
+    if seconds is not None:
+        seconds.update(align_first=t1 - t0, subcluster=t2 - t1, align_second=t3 - t2, consensus=clock() - t3)
     out = [dict() for _ in clusters]
     for (ci, last), c in zip(who, cons):
         out[ci][last] = c
@@ -906,13 +933,14 @@ def _generate_cons_batch(ctx, clusters, ninja=None):
     return out
 
 
-def generate_cons_v1(cluster_id, cur_cluster_path, cluster_dir, threads, device=0, ninja_clusters=None):
+def generate_cons_v1(cluster_id, cur_cluster_path, cluster_dir, threads, device=0, ninja_clusters=None, subcluster=None):
     """generate_cons_v1 (Util.py:12457), same arguments: the FASTA of one cluster -> {name: consensus}.  ninja_clusters: the
-    parsed output of Ninja ({id: [names]}, read_Ninja_clusters) when the caller has one; else the build's stand-in."""
+    parsed output of Ninja ({id: [names]}, read_Ninja_clusters) when the caller has one; else the build's stand-in, on the host
+    or, with subcluster="gpu" / HITE_SUBCLUSTER=gpu, on the device (_generate_cons_batch)."""
     names, contigs = read_fasta(cur_cluster_path)
     if not names:
         return {}
-    return _generate_cons_batch(get_ctx(device), [[(n, contigs[n]) for n in names]], [ninja_clusters])[0]
+    return _generate_cons_batch(get_ctx(device), [[(n, contigs[n]) for n in names]], [ninja_clusters], subcluster=subcluster)[0]
 
 
 def _library_hits(ctx, names, contigs):
@@ -1003,7 +1031,8 @@ def _stretch_hits(q, s, qs, qe, ss, se, lens, seqs):
     return qs, qe, ss, se
 
 
-def deredundant_for_LTR_v5(redundant_ltr, work_dir, threads, type, coverage_threshold, debug, device=0, ctx=None, stages=None):
+def deredundant_for_LTR_v5(redundant_ltr, work_dir, threads, type, coverage_threshold, debug, device=0, ctx=None, stages=None,
+                           subcluster=None):
     """deredundant_for_LTR_v5 (Util.py:12202-12337, the library de-duplication of panHiTE, config C5), same arguments.
     Reference: blastn all-vs-all of the library -> chunked fragment chaining (process_blast_results_in_chunks +
     FMEA_new1_parallel_large) -> greedy clusters (cluster_sequences_from_chunks) -> per cluster generate_cons_v1 (mafft ->
@@ -1011,13 +1040,16 @@ def deredundant_for_LTR_v5(redundant_ltr, work_dir, threads, type, coverage_thre
     against itself by hite_seed_allvsall (where the reference runs blastn; libraries of >= 65 000 sequences in blocks),
     chaining / clustering / consensus are the pinned device stages (hite_lib_chain, hite_lib_cluster, hite_msa_consensus),
     the alignments are star alignments (where the reference runs mafft), the sub-clusters come from ninja_stand_in (where it
-    runs Ninja); a cluster above 10 000 members is cut in file order into pieces of <= 10 000, the fall-back the reference
+    runs Ninja; with subcluster="gpu" / HITE_SUBCLUSTER=gpu from hite_msa_subcluster, the same clustering on the device); a cluster above 10 000 members is cut in file order into pieces of <= 10 000, the fall-back the reference
     itself takes when its cd-hit-est pre-reduction does not get a cluster below that size (:12252-12299; the pre-reduction
     itself needs the external tool); cd-hit-est after the consensus step runs when it is installed.  Sequences longer than
     the aligner's 32 767-base windows pass unclustered.
     Writes <redundant_ltr>.tmp.cons and <redundant_ltr>.cons, returns the former like the reference.
     ctx: the context to run on (default: the process-wide one of `device`); stages: a dict that receives the intermediate
-    results ('hits', 'clusters': lists of names) -- what the parity tests compare between two runs."""
+    results ('hits', 'clusters': lists of names) -- what the parity tests compare between two runs -- and 'seconds': the wall
+    seconds of the steps (hits, stretch, chain, cluster, align_first, subcluster, align_second, consensus, redundancy)."""
+    clock = time.perf_counter
+    secs = dict.fromkeys(("hits", "stretch", "chain", "cluster", "align_first", "subcluster", "align_second", "consensus", "redundancy"), 0.0)
     names, contigs = read_fasta(redundant_ltr)
     cons_path, final_path = redundant_ltr + ".tmp.cons", redundant_ltr + ".cons"
     if not names:
@@ -1029,29 +1061,38 @@ def deredundant_for_LTR_v5(redundant_ltr, work_dir, threads, type, coverage_thre
     work = [n for n in names if 0 < len(contigs[n]) <= STAR_MAX_LEN]       # the rest passes unchanged
     all_cons, clustered = {}, set()
     if work:
+        t0 = clock()
         q, s, qs, qe, ss, se = _library_hits(ctx, work, contigs)
+        t1 = clock()
         lens = [len(contigs[n]) for n in work]
         qs, qe, ss, se = _stretch_hits(q, s, qs, qe, ss, se, lens, [contigs[n].upper() for n in work])
+        t2 = clock()
         recs = ctx.lib_chain(q, s, qs, qe, ss, se, lens, coverage_threshold, 5_000_000)
+        t3 = clock()
         clusters = [cl for cl in ctx.lib_cluster(recs, lens, coverage_threshold) if len(cl) >= 1]
         clusters = [cl[a:a + CLUSTER_CLEAN_THRESHOLD] for cl in clusters for a in range(0, len(cl), CLUSTER_CLEAN_THRESHOLD)]
+        secs.update(hits=t1 - t0, stretch=t2 - t1, chain=t3 - t2, cluster=clock() - t3)
         if stages is not None:
             stages["hits"] = len(q)
             stages["clusters"] = [[work[i] for i in cl] for cl in clusters]
         batch = [[(work[i], contigs[work[i]]) for i in cl] for cl in clusters]
-        for cl, cons in zip(clusters, _generate_cons_batch(ctx, batch) if batch else []):
+        for cl, cons in zip(clusters, _generate_cons_batch(ctx, batch, subcluster=subcluster, seconds=secs) if batch else []):
             clustered.update(work[i] for i in cl)
             all_cons.update(cons)
     for n in names:      # sequences outside every cluster (and the over-long ones) pass unchanged
         if n not in clustered:
             all_cons[n] = contigs[n]
     store_fasta(all_cons, cons_path)
+    t0 = clock()
     if shutil.which("cd-hit-est"):
         subprocess.run("cd-hit-est -aS 0.95 -aL 0.95 -c %s -G 0 -g 1 -A 80 -i %s -o %s -T 0 -M 0 > /dev/null 2>&1" %
                        (coverage_threshold, cons_path, final_path), shell=True, check=False)
     else:
         # the build's stand-in, never a plain copy; -c takes effect with HITE_CLUSTER_IDENTITY=gpu
         remove_redundant_sequences(cons_path, final_path, 0.95, 0.95, device=device, ctx=ctx, c=coverage_threshold)
+    secs["redundancy"] = clock() - t0
+    if stages is not None:
+        stages["seconds"] = secs
     return cons_path
 
 

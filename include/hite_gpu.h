@@ -242,6 +242,28 @@ int hite_lib_cluster(int64_t nrec, const int32_t *chunk, const int32_t *q, const
  * that count > rows[a] / 2.  Consensus a is written at cons + out_off[a] (reserve cols[a] bytes), length cons_len[a]. */
 int hite_msa_consensus(hite_ctx *ctx, int32_t nmat, const int32_t *rows, const int64_t *cols, const int64_t *mat_off,
                        const uint8_t *mats, const int64_t *out_off, uint8_t *cons, int64_t *cons_len);
+/* hite_msa_subcluster: sub-clusters of an alignment, the step between the two alignments of generate_cons_v1 (Util.py:12467-12476,
+ * where the reference runs `Ninja --corr_type m --cluster_cutoff 0.2`).  The tool is not pinned: what is computed is the leader
+ * clustering below (util.ninja_stand_in; twin tests/subcluster_twin.py), not Ninja's neighbour-joining tree.
+ *  - An alignment is R rows x C columns of bytes.  A gap is byte 45 and nothing else; bytes compare as bytes ('a' != 'A').
+ *  - For two rows x, y: n = columns where x or y is not a gap; diff = columns where x != y (a column where both are gaps has x == y).
+ *    x matches y when n > 0 and (double)diff <= cutoff * (double)n, evaluated in binary64 as written.
+ *  - Rows are visited in order: row r joins the FIRST leader, in leader order, that it matches; if it matches none it becomes the
+ *    next leader.  Membership is never transitive: a row that matches only a non-leader member founds its own sub-cluster.
+ *  - Output per row: the index of its sub-cluster, counted in order of the leaders' appearance.
+ * Batch layout as hite_msa_consensus: alignment a = rows[a] x cols[a] bytes, row-major, at mats + mat_off[a]; mat_off and row_off
+ * have nmat + 1 ascending entries (mat_off[a+1] - mat_off[a] >= rows[a] * cols[a], row_off[a+1] - row_off[a] >= rows[a]); the
+ * alignments may start at any byte offset; mats is readable 16 bytes past its end.  sub_of_row + row_off[a] receives rows[a]
+ * indices, n_sub[a] the number of sub-clusters.  nmat = 0 is valid; rows[a] = 0 gives n_sub[a] = 0; with cols[a] = 0 every row is
+ * its own sub-cluster (n = 0).  HITE_EINVAL for a negative count, a missing buffer, descending offsets, cols[a] > 65 535 and a
+ * cutoff that is NaN or outside [0, 1].  The alignments go to the device in batches of bounded bytes (one alignment larger than a
+ * batch runs alone); the work is on the context's stream and scratch.
+ * Rows are taken in chunks of HITE_SUBCLUSTER_CHUNK (hite_subcluster.hip); $HITE_SUBCLUSTER_CHUNK_ROWS = 1 .. HITE_SUBCLUSTER_CHUNK,
+ * read by hite_ctx_create, sets a smaller chunk (a test knob: small inputs then take the chunked path; never changes a result), as
+ * $HITE_SUBCLUSTER_BATCH_BYTES sets the bytes of a batch (default 256 MiB). */
+#define HITE_SUBCLUSTER_CHUNK 64
+int hite_msa_subcluster(hite_ctx *ctx, int32_t nmat, const int32_t *rows, const int64_t *cols, const int64_t *mat_off,
+                        const uint8_t *mats, double cutoff, const int64_t *row_off, int32_t *sub_of_row, int32_t *n_sub);
 
 /* ---- LTR frames of the vendored FiLTR --- get_both_ends_frame  bin/FiLTR-main/src/Util.py:1401-1497 (+ :1341-1399) -----
  * Batch of alignments (rows[a] x cols[a] bytes at msa + msa_off[a], upper case) with the terminal sequence of each
