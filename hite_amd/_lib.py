@@ -26,6 +26,10 @@ class HiteCall(C.Structure):
 CALL_DTYPE = np.dtype([("is_te", "<i4"), ("info", "<i4"), ("row_num", "<i4"), ("bstart", "<i4"), ("bend", "<i4"),
                        ("cons_len", "<i4"), ("cons_off", "<i8")])
 assert CALL_DTYPE.itemsize == 32 and C.sizeof(HiteCall) == 32
+# hite_lcv (include/hite_gpu.h): a compiled HelitronScanner pattern; two bits per body position in `body` (A 0 C 1 G 2 T 3) and `care` (3 / 0)
+LCV_DTYPE = np.dtype([("body", "<u8"), ("care", "<u8"), ("gap_min", "u1"), ("gap_max", "u1"), ("body_len", "u1"), ("pad", "u1", (5,))])
+assert LCV_DTYPE.itemsize == 24
+HELITRON_MAX_BODY, HELITRON_MAX_GAP = 32, 63
 
 _lib = None
 
@@ -446,6 +450,46 @@ class Context:
                                                 _p(_arr(pr[:, 2], np.int64)), _p(bi), _p(_arr(pr[:, 4], np.int64)), _p(_arr(pr[:, 5], np.int64)),
                                                 _p(_arr(pr[:, 6] != 0, np.uint8)), C.c_int32(int(band)), _p(cost), _p(mat)), "hite_pair_identity")
         out[:, 0], out[:, 1] = cost, mat
+        return out
+
+    # ---- Helitron candidate scan (multi_process_helitronscanner, Util.py:263: HelitronScanner.jar) ---------------------------
+    def _helitron_args(self, seqs, head_patterns, tail_patterns):
+        buf, off = self._csr(seqs)
+        hp, tp = _arr(head_patterns, LCV_DTYPE).reshape(-1), _arr(tail_patterns, LCV_DTYPE).reshape(-1)
+        return buf, off, [C.c_int64(len(off) - 1), _p(buf), _p(off), C.c_int32(len(hp)), _p(hp), C.c_int32(len(tp)), _p(tp)], (hp, tp)
+
+    def helitron_scan(self, seqs, head_patterns, tail_patterns, head_threshold=1, tail_threshold=1, len_range=(200, 20000), stats=None,
+                      cap=1 << 16):
+        """seqs: str / bytes; patterns: LCV_DTYPE records (util.parse_lcvs) -> int32 [n, 6]: (seq, start, end, strand, head score,
+        tail score) of the Helitron candidate scan that include/hite_gpu.h defines, ordered by (seq, strand, start, end); start / end
+        are 0-based, half-open, on the forward strand.  A result beyond `cap` records is asked again with the room it reported.
+        stats (a dict): anchors, heads, tails, pairs of this call."""
+        buf, off, args, keep = self._helitron_args(seqs, head_patterns, tail_patterns)
+        room = int(cap)
+        while True:
+            out = np.zeros((5, max(room, 1)), dtype=np.int32)
+            strand = np.zeros(max(room, 1), dtype=np.uint8)
+            n_out = C.c_int64(0)
+            st = np.zeros(4, dtype=np.int64)
+            rc = self.lib.hite_helitron_scan(self.h, *args, C.c_int32(int(head_threshold)), C.c_int32(int(tail_threshold)),
+                                             C.c_int32(int(len_range[0])), C.c_int32(int(len_range[1])), C.c_int64(out.shape[1]),
+                                             _p(out[0]), _p(out[1]), _p(out[2]), _p(strand), _p(out[3]), _p(out[4]), C.byref(n_out), _p(st))
+            if rc == -4 and n_out.value > out.shape[1]:       # HITE_ECAP: now the room is known
+                room = n_out.value
+                continue
+            self._check(rc, "hite_helitron_scan")
+            break
+        k = n_out.value
+        if stats is not None:
+            stats.update(zip(("anchors", "heads", "tails", "pairs"), (int(v) for v in st)))
+        return np.ascontiguousarray(np.stack([out[0, :k], out[1, :k], out[2, :k], strand[:k].astype(np.int32), out[3, :k], out[4, :k]], axis=1))
+
+    def helitron_scores(self, seqs, head_patterns, tail_patterns):
+        """-> int32 [4, total bytes]: the head / tail scores of every position (rows: plus heads, plus tails, minus heads, minus tails;
+        the minus rows in the coordinates of the reverse complement), sequence k at columns sum(len(seqs[:k])) ..."""
+        buf, off, args, keep = self._helitron_args(seqs, head_patterns, tail_patterns)
+        out = np.zeros((4, int(off[-1])), dtype=np.int32)
+        self._check(self.lib.hite_helitron_scores(self.h, *args, _p(out)), "hite_helitron_scores")
         return out
 
     # ---- translated protein search (get_domain_info, Util.py:4571: blastx -evalue 1e-20 -outfmt 6) -------------------

@@ -2,13 +2,18 @@
 """Drop-in for HiTE's module/judge_Helitron_transposons.py (same argv and output files,
 /root/reference/module/judge_Helitron_transposons.py:20-144): <tmp_output_dir>/confident_helitron_{i}.fa.
 
-Candidates: the reference obtains them from HelitronScanner / EAHelitron on the flanked repeats (external Java / Perl
-tools, :33-76).  Here `--candidates <fa>` (extension of this build) passes that candidate consensus file; without it
-the script looks for <tmp_output_dir>/candidate_helitron_{i}.cons.fa, the file the reference's own front half writes.
+Candidates: the reference obtains them from HelitronScanner on the flanked repeats (an external Java tool; the EAHelitron
+block is commented out, :27-76).  Here `--candidates <fa>` (extension of this build) passes a candidate consensus file; without
+it the script looks for <tmp_output_dir>/candidate_helitron_{i}.cons.fa.  With neither, and when HelitronScanner's pattern lists
+are found (--HSDIR, $HITE_HSDIR, <HiTE>/bin/HelitronScanner/TrainingSet: util.helitron_lcv_dir), it follows the reference's front
+half: the in-tree candidate scan of --seqs (util.multi_process_helitronscanner; the definition is in include/hite_gpu.h, parity
+with the tool is unpinned) into candidate_helitron_{i}.HelitronScanner.fa and candidate_helitron_{i}.fa, cd-hit-est -c 0.8 into
+candidate_helitron_{i}.fa.cons.
 GPU: three refinement iterations of flank_region_align_v5 with judge_boundary_v6 (copy finding, window gather, star
 alignment, sparse columns, mode-anchored boundary search, ATC / CTRRT motif rules)."""
 import argparse
 import os
+import shutil
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +36,20 @@ def build_parser():
     return p
 
 
+def scan_candidates(a, out_dir):
+    """the reference's front half (:24-76): HelitronScanner on the flanked repeats -> candidate_helitron_{i}.HelitronScanner.fa ->
+    candidate_helitron_{i}.fa -> (cd-hit-est) candidate_helitron_{i}.fa.cons, whose path is returned"""
+    stem = os.path.join(out_dir, "candidate_helitron_%s" % a.ref_index)
+    cand, cons = stem + ".fa", stem + ".fa.cons"
+    if not a.recover or not util.file_exist(cand):
+        temp = os.path.join(out_dir, "HS_temp")
+        util.multi_process_helitronscanner(a.seqs, stem + ".HelitronScanner.fa", a.sh_dir, temp, a.HSDIR, a.HSJAR, a.t, a.debug)
+        shutil.copyfile(stem + ".HelitronScanner.fa", cand)
+    if not a.recover or not util.file_exist(cons):
+        _stage.run_cd_hit(cand, cons, a.t)
+    return cons
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     out_dir = os.path.abspath(a.tmp_output_dir or os.getcwd())
@@ -40,8 +59,10 @@ def main(argv=None):
         return 0
     cand = a.candidates or os.path.join(out_dir, "candidate_helitron_%s.cons.fa" % a.ref_index)
     if not os.path.exists(cand):
-        sys.stderr.write("judge_Helitron_transposons (MI355X path): no candidate file (%s); HelitronScanner / EAHelitron are external\n" % cand)
-        return 2
+        if a.candidates or not a.seqs or not os.path.exists(a.seqs) or util.helitron_lcv_dir(a.HSDIR) is None:
+            sys.stderr.write("judge_Helitron_transposons (MI355X path): no candidate file (%s); HelitronScanner / EAHelitron are external\n" % cand)
+            return 2
+        cand = scan_candidates(a, out_dir)
     low = a.all_low_copy_helitron or os.path.join(out_dir, "helitron_low_copy.fa")
     util.set_reference(a.r)
     last = _stage.refine("helitron", cand, out_dir, "confident_helitron", a.ref_index, a.r, a.split_ref_dir, a.t, 1, a.debug, low, 3)

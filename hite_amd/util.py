@@ -1750,3 +1750,89 @@ def bucket_results(TE_type, results):
 def valid_filename(query_name):
     """Util.py:8127"""
     return re.sub(r'[<>:"/\\|?*]', "-", query_name)
+
+
+# ---- Helitron candidate scan (multi_process_helitronscanner Util.py:263: HelitronScanner.jar scanHead / scanTail / pairends / draw) ----
+_LCV_GAP = r"(?:\.\{(\d+)(?:,(\d+))?\})?"
+_LCV_BODY = r"([ACGT](?:[ACGT.]*[ACGT])?)"
+_LCV_RE = {"head": re.compile(r"^TC" + _LCV_GAP + _LCV_BODY + r"$"), "tail": re.compile(r"^" + _LCV_BODY + _LCV_GAP + r"CT\[AG\]\{2\}$")}
+
+
+def parse_lcvs(lines, side):
+    """HelitronScanner's LCV lines (TrainingSet/head.lcvs: side "head", tail.lcvs: side "tail") -> LCV_DTYPE records, the compiled
+    patterns hite_helitron_scan takes (include/hite_gpu.h).  head: `TC`, an optional gap `.{n}` / `.{a,b}`, a body of letters ACGT and
+    single `.` that starts and ends with a letter; tail: a body, an optional gap, `CT[AG]{2}`.  Blank lines and lines that start
+    with # are skipped, a repeated line stays (each counts).  A line outside this grammar, a body of more than 32 positions or a gap
+    of more than 63 raises ValueError naming the line."""
+    from ._lib import HELITRON_MAX_BODY, HELITRON_MAX_GAP, LCV_DTYPE
+
+    if side not in _LCV_RE:
+        raise ValueError("parse_lcvs: side is 'head' or 'tail', not %r" % (side,))
+    recs = []
+    for no, raw in enumerate(lines, 1):
+        line = raw.strip()
+        if not line or line.startswith("#"):
+            continue
+        m = _LCV_RE[side].match(line)
+        if not m:
+            raise ValueError("parse_lcvs: line %d is no %s LCV pattern: %r" % (no, side, line))
+        ga, gb, body = (m.group(1), m.group(2), m.group(3)) if side == "head" else (m.group(2), m.group(3), m.group(1))
+        gmin = int(ga) if ga is not None else 0
+        gmax = int(gb) if gb is not None else gmin
+        if gmin > gmax or gmax > HELITRON_MAX_GAP:
+            raise ValueError("parse_lcvs: line %d: gap %d..%d is descending or beyond %d: %r" % (no, gmin, gmax, HELITRON_MAX_GAP, line))
+        if len(body) > HELITRON_MAX_BODY:
+            raise ValueError("parse_lcvs: line %d: body of %d positions, the limit is %d: %r" % (no, len(body), HELITRON_MAX_BODY, line))
+        bits = care = 0
+        for j, ch in enumerate(body):
+            if ch != ".":
+                bits |= "ACGT".index(ch) << (2 * j)
+                care |= 3 << (2 * j)
+        recs.append((bits, care, gmin, gmax, len(body), (0,) * 5))
+    return np.array(recs, dtype=LCV_DTYPE) if recs else np.zeros(0, dtype=LCV_DTYPE)
+
+
+def lcv_line(rec, side):
+    """the LCV line of a compiled record (a single gap prints as `.{n}`, none as nothing): parse_lcvs(lcv_line(r)) == r"""
+    body = "".join("ACGT"[(int(rec["body"]) >> (2 * j)) & 3] if (int(rec["care"]) >> (2 * j)) & 3 else "." for j in range(int(rec["body_len"])))
+    a, b = int(rec["gap_min"]), int(rec["gap_max"])
+    gap = "" if a == b == 0 else (".{%d}" % a if a == b else ".{%d,%d}" % (a, b))
+    return "TC" + gap + body if side == "head" else body + gap + "CT[AG]{2}"
+
+
+def helitron_lcv_dir(HSDIR=None):
+    """where head.lcvs and tail.lcvs are: --HSDIR, then $HITE_HSDIR, then <HiTE>/bin/HelitronScanner/TrainingSet beside the package (the
+    reference's default, judge_Helitron_transposons.py:18).  The lists are HiTE's data; this build does not ship them.  -> the first
+    of these directories that holds both files, or None."""
+    beside = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bin", "HelitronScanner", "TrainingSet")
+    for d in (HSDIR, os.environ.get("HITE_HSDIR"), beside):
+        if d and os.path.isfile(os.path.join(d, "head.lcvs")) and os.path.isfile(os.path.join(d, "tail.lcvs")):
+            return d
+    return None
+
+
+def multi_process_helitronscanner(candidate_file, output, sh_dir, temp_dir, HSDIR, HSJAR, threads, debug, ctx=None, device=0,
+                                  head_threshold=1, tail_threshold=1, len_range=(200, 20000)):
+    """multi_process_helitronscanner (Util.py:263-318; the reference runs bin/run_helitron_scanner.sh per 50 kb part: HelitronScanner's
+    scanHead, scanTail, pairends and draw -pure_helitron on both strands, 30 minutes per part) as ONE batched call of the in-tree
+    stage (Context.helitron_scan; the definition is in include/hite_gpu.h, parity with the tool is unpinned).  The thresholds and the
+    length range are the tool's defaults, which the reference leaves alone.  Every record is written as the pure element -- its
+    bases, reverse-complemented on the minus strand -- under the name <source name>_<start+1>_<end>_<+|->.  sh_dir, temp_dir, HSJAR,
+    threads and debug are the reference's arguments and are not used.  -> the number of records."""
+    lcv_dir = helitron_lcv_dir(HSDIR)
+    if lcv_dir is None:
+        raise FileNotFoundError("multi_process_helitronscanner: head.lcvs / tail.lcvs not found (HSDIR %r, $HITE_HSDIR, "
+                                "<HiTE>/bin/HelitronScanner/TrainingSet)" % (HSDIR,))
+    with open(os.path.join(lcv_dir, "head.lcvs")) as f:
+        head = parse_lcvs(f, "head")
+    with open(os.path.join(lcv_dir, "tail.lcvs")) as f:
+        tail = parse_lcvs(f, "tail")
+    names, contigs = read_fasta(candidate_file)
+    rec = np.zeros((0, 6), dtype=np.int32)
+    if names:
+        rec = (ctx or get_ctx(device)).helitron_scan([contigs[n] for n in names], head, tail, head_threshold, tail_threshold, len_range)
+    with open(output, "w") as f:
+        for q, start, end, strand, _hs, _ts in rec.tolist():
+            seq = contigs[names[q]][start:end]
+            f.write(">%s_%d_%d_%s\n%s\n" % (names[q], start + 1, end, "-" if strand else "+", getReverseSequence(seq) if strand else seq))
+    return len(rec)

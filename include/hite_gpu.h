@@ -415,6 +415,63 @@ int hite_pair_identity(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs, const 
                        const int32_t *b_id, const int64_t *b_start, const int64_t *b_end,
                        const uint8_t *strand, int32_t band, int32_t *cost_out, int32_t *match_out);
 
+/* ---- Helitron candidate scan --- multi_process_helitronscanner  Util.py:263 (third-party HelitronScanner.jar: scanHead, scanTail,
+ * pairends, draw -pure_helitron per 50 kb part of longest_repeats_{i}.flanked.fa; judge_Helitron_transposons.py:27-34) -------------
+ * In-tree stage, not pinned to the tool (no machine of the project runs it, and the tool's pairing rule and the tie-breaks of its
+ * regex engine are not reproduced): the definition below, its CPU twin tests/helitron_twin.py, HIP == twin record for record and
+ * score for score.
+ *
+ * Patterns are the tool's "LCV" lines (TrainingSet/head.lcvs, tail.lcvs; HiTE's data, read at run time, util.parse_lcvs):
+ *  - head: the literal `TC`, an optional gap `.{n}` / `.{a,b}`, a body of letters ACGT and single `.`;
+ *  - tail: a body, an optional gap, the literal `CT[AG]{2}`.
+ * A compiled pattern (hite_lcv, 24 bytes) holds the gap range, the body length and, per body position j in the order of the line,
+ * two bits at 2 j of `body` (A 0, C 1, G 2, T 3; 0 under a `.`) and of `care` (3 under a letter, 0 under a `.`).
+ * Limits: body_len 1 .. HITE_HELITRON_MAX_BODY, gap_min <= gap_max <= HITE_HELITRON_MAX_GAP, at most HITE_HELITRON_MAX_PATTERNS
+ * patterns per side, sequences shorter than 2^31 bytes, fewer than 2^31 anchors per call.
+ *
+ * The input is a CSR batch of sequences, as bytes.
+ *  - A letter of a pattern matches only the same upper-case byte; `.` and a gap position match any byte (N, lower case);
+ *    `[AG]` matches A or G.  Nothing matches across a sequence end.
+ *  - Head score at p, the 0-based index of the T of `TC`: the number of head patterns with s[p:p+2] == "TC" whose body matches at
+ *    p + 2 + g for at least one g in [gap_min, gap_max].  A pattern adds at most 1 per position; a repeated line counts again.
+ *  - Tail score at q, the index of the last base of `CT[AG][AG]`: the number of tail patterns with s[q-3:q+1] matching the literal
+ *    whose body ends at q - 4 - g for at least one such g.
+ *  - Pairing, per sequence and strand: heads are the positions with score >= head_threshold; each pairs with the nearest q >= p +
+ *    len_min - 1 that has tail score >= tail_threshold, if q - p + 1 <= len_max; a head without such a tail gives nothing.  Two heads
+ *    may share a tail.  One record per paired head: (seq, start = p, end = q + 1, strand, head score, tail score).
+ *  - Minus strand: the same on the reverse complement (A<->T, C<->G, every other byte N); start and end are reported on the forward
+ *    strand (start = L - 1 - q, end = L - p), strand = 1.
+ *  - Order: (seq, strand, start, end).
+ * The tool's defaults, which the reference leaves alone: thresholds 1, length range 200 .. 20000 (the caller passes them).
+ *
+ * HITE_EINVAL for a negative count, descending offsets, a missing buffer, a pattern beyond a limit or malformed (care pairs other
+ * than 0 / 3, bits beyond body_len, body bits under a `.`), a threshold or len_min below 1 (every base would be a head), len_min >
+ * len_max.  n = 0 and zero patterns on a side are valid calls (no records).  Parallel output arrays of `cap` entries; *n_out = the
+ * number of records, HITE_ECAP when it exceeds cap (the first cap are written).  stats (may be NULL): anchors tested, heads, tails,
+ * pairs.  The _dev form takes the sequences on the device (d_seqs = the byte of seq_off[0]; the offsets and the outputs stay on the
+ * host), works on `stream` and returns after it has drained. */
+#define HITE_HELITRON_MAX_BODY 32
+#define HITE_HELITRON_MAX_GAP 63
+#define HITE_HELITRON_MAX_PATTERNS 1024
+typedef struct hite_lcv {
+    uint64_t body;
+    uint64_t care;
+    uint8_t gap_min, gap_max, body_len, pad[5];
+} hite_lcv;
+int hite_helitron_scan(hite_ctx *ctx, int64_t n, const uint8_t *seqs, const int64_t *seq_off, int32_t n_head, const hite_lcv *head,
+                       int32_t n_tail, const hite_lcv *tail, int32_t head_threshold, int32_t tail_threshold, int32_t len_min,
+                       int32_t len_max, int64_t cap, int32_t *seq_out, int32_t *start_out, int32_t *end_out, uint8_t *strand_out,
+                       int32_t *hscore_out, int32_t *tscore_out, int64_t *n_out, int64_t *stats);
+int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d_seqs, const int64_t *seq_off, int32_t n_head, const hite_lcv *head,
+                           int32_t n_tail, const hite_lcv *tail, int32_t head_threshold, int32_t tail_threshold, int32_t len_min,
+                           int32_t len_max, int64_t cap, int32_t *seq_out, int32_t *start_out, int32_t *end_out, uint8_t *strand_out,
+                           int32_t *hscore_out, int32_t *tscore_out, int64_t *n_out, int64_t *stats, void *stream);
+/* the scores alone, for every position of both strands: scores_out = four rows of seq_off[n] - seq_off[0] entries, each in its
+ * strand's own coordinates at (offset of the sequence) + position: plus heads at p, plus tails at q, minus heads, minus tails (the
+ * positions of the reverse complement).  0 where there is no anchor. */
+int hite_helitron_scores(hite_ctx *ctx, int64_t n, const uint8_t *seqs, const int64_t *seq_off, int32_t n_head, const hite_lcv *head,
+                         int32_t n_tail, const hite_lcv *tail, int32_t *scores_out);
+
 /* ---- copy finding: this build's GPU-native stage where the reference runs the external
  * `minimap2 -ax map-ont -N 300 -p 0.2` + SAM filtering (get_full_length_copies_minimap2, Util.py:7933-8030;
  * third-party, unpinned -> parity is pinned against the build's own CPU twin, oracle/hite_oracle_copies.c,
