@@ -802,6 +802,37 @@ class Context:
             out.append(groups)
         return out
 
+    def frame_cluster(self, groups, ident, cov_short=0.0, cov_long=0.0, min_cov=0, min_len=10, both_strands=True):
+        """batch of groups (each a list of short sequences, str or bytes, gap-free) -> per group its clusters in order of creation,
+        each a list of row indices (the representative, then the rows that joined it, in the order they joined), or None for a group
+        beyond HITE_FRAMECLUSTER_MAX_ROWS / HITE_FRAMECLUSTER_MAX_LEN: the greedy clustering include/hite_gpu.h defines
+        (hite_frame_cluster; where FiLTR runs `cd-hit-est -c ident -aS cov_short -aL cov_long -A min_cov -l min_len`).  Rows of
+        length <= min_len are in no cluster."""
+        ng = len(groups)
+        flat = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for g in groups for r in g]
+        roff = np.zeros(ng + 1, dtype=np.int64)
+        np.cumsum([len(g) for g in groups], out=roff[1:])
+        soff = np.zeros(len(flat) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in flat], out=soff[1:])
+        buf = np.frombuffer(b"".join(flat) + b"\0" * 16, dtype=np.uint8)
+        cl = np.zeros(len(flat) + 1, dtype=np.int32)
+        ncl = np.zeros(ng + 1, dtype=np.int32)
+        self._check(self.lib.hite_frame_cluster(self.h, C.c_int64(ng), _p(roff), _p(buf), _p(soff), C.c_double(ident), C.c_double(cov_short),
+                                                C.c_double(cov_long), C.c_int32(min_cov), C.c_int32(min_len), C.c_int32(int(bool(both_strands))),
+                                                _p(cl), _p(ncl)), "hite_frame_cluster")
+        cl, lens, at, out = cl.tolist(), np.diff(soff).tolist(), roff.tolist(), []
+        for g, k in enumerate(ncl[:ng].tolist()):
+            if k < 0:
+                out.append(None)
+                continue
+            cls = [[] for _ in range(k)]
+            r0 = at[g]
+            for r in sorted(range(at[g + 1] - r0), key=lambda r: (-lens[r0 + r], r)):
+                if cl[r0 + r] >= 0:
+                    cls[cl[r0 + r]].append(r)
+            out.append(cls)
+        return out
+
     def ltr_both_ends(self, alignments, cur_seqs, flank):
         """FiLTR get_both_ends_frame on a batch: alignments = lists of equal-length rows, cur_seqs = terminal sequences ->
         per alignment None (boundary not found) or (frames [(left, right)], full rows, new_start, new_end)"""

@@ -34,6 +34,10 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
         const long long v = strtoll(e, nullptr, 10);
         if (v >= 1) c->subcluster_batch_bytes = (int64_t)v;
     }
+    if (const char *e = getenv("HITE_FRAMECLUSTER_BATCH_BYTES")) {      // test knob of hite_frame_cluster (hite_framecluster.hip)
+        const long long v = strtoll(e, nullptr, 10);
+        if (v >= 1 && v <= ((long long)1 << 30)) c->framecluster_batch_bytes = (int64_t)v;
+    }
     if (hipSetDevice(device_id) != hipSuccess) { free(c); return HITE_EHIP; }
     *out = c;
     return HITE_OK;

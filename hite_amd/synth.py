@@ -219,3 +219,44 @@ def make_workload(genome_bp=100_000_000, n_tir=500, n_ltr=0, cands_per_family=10
                              start=(pos - contig_off[chrom])[ok], length=lens[ok],
                              minus=np.array([m[1] for m in meta], dtype=bool)[ok], full=np.array([m[2] for m in meta], dtype=bool)[ok],
                              div=np.array(divs, dtype=np.float64)[ok]))
+
+
+def make_ltr_flank_genome(plan, genome_bp=450_000, chrom_bp=150_000, seed=1, term_len=300, homo_len=150, div=0.03):
+    """A genome for the LTR flank filter (util.ltr_flank_filter; tests and tools/ltr_filter_bench.py): plan = [(kind, copies), ...],
+    one family of `copies` copies of a term_len-base terminal sequence per entry --
+      "ltr"    every copy sits in random flanks (a true LTR terminal);
+      "inner"  the terminal is the middle of a longer repeat: homo_len homologous bases on both sides of every copy;
+      "left" / "right"  one flank homologous, the other random (in the orientation of the terminal sequence).
+    Copies diverge by `div` (substitutions, a few indels), lie on either strand, and keep more than 100 bases from each other and
+    from the contig ends.  -> dict(contigs [str], names [str], terminals {name: sequence of copy 0}, kind {name}, copies {name})"""
+    rng = np.random.default_rng(seed)
+    n_chr = max(1, genome_bp // chrom_bp)
+    genome = [ASCII[_rand_codes(rng, chrom_bp)] for _ in range(n_chr)]
+    slot = term_len + 2 * homo_len + 300
+    per_chr = chrom_bp // slot - 2
+    total = sum(n for _k, n in plan)
+    if total > n_chr * per_chr:
+        raise ValueError("planted copies do not fit the genome")
+    slots = rng.permutation(n_chr * per_chr)[:total]
+    names, terminals, kind, copies = [], {}, {}, {}
+    at = 0
+    for f, (k, n) in enumerate(plan):
+        term, hl, hr = _rand_codes(rng, term_len), _rand_codes(rng, homo_len), _rand_codes(rng, homo_len)
+        name = "%s_%d_%d" % (k, n, f)
+        names.append(name)
+        terminals[name] = ASCII[term].tobytes().decode()
+        kind[name], copies[name] = k, n
+        for c in range(n):
+            ci, si = divmod(int(slots[at]), per_chr)
+            at += 1
+            parts = [_mutate_copy(rng, hl, div, 0.002)] if k in ("inner", "left") else []
+            parts.append(_mutate_copy(rng, term, div, 0.002) if c else term)
+            if k in ("inner", "right"):
+                parts.append(_mutate_copy(rng, hr, div, 0.002))
+            unit = np.concatenate(parts)
+            lead = len(parts[0]) if k in ("inner", "left") else 0      # the terminal starts at the same place of its slot
+            if rng.integers(0, 2):
+                unit, lead = COMP[unit[::-1]], len(unit) - lead - len(parts[1 if k in ("inner", "left") else 0])
+            pos = (si + 1) * slot + homo_len + 150 - lead
+            genome[ci][pos:pos + len(unit)] = ASCII[unit]
+    return dict(contigs=[g.tobytes().decode() for g in genome], names=names, terminals=terminals, kind=kind, copies=copies)

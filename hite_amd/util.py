@@ -12,6 +12,8 @@ the build's own translated search (protein_search_outfmt6: six-frame translation
 definition is in include/hite_gpu.h) takes its place with search="gpu" / domain_search="gpu" or HITE_DOMAIN_SEARCH=gpu.
 The clustering that stands in for `cd-hit-est` (remove_redundant_sequences) works on chain coverage alone by default; with
 identity="gpu" or HITE_CLUSTER_IDENTITY=gpu its -c / -A rest on the pairwise identity of include/hite_gpu.h (Context.pair_identity).
+The flank filter of LTR terminal sequences (ltr_flank_filter: step 3 of the vendored FiLTR, bin/FiLTR-main/src/LTR_filter.py:44-170)
+runs its three `cd-hit-est` calls per candidate as batched calls of the build's own clustering of frames (Context.frame_cluster).
 """
 import itertools
 import math
@@ -1836,3 +1838,269 @@ def multi_process_helitronscanner(candidate_file, output, sh_dir, temp_dir, HSDI
             seq = contigs[names[q]][start:end]
             f.write(">%s_%d_%d_%s\n%s\n" % (names[q], start + 1, end, "-" if strand else "+", getReverseSequence(seq) if strand else seq))
     return len(rec)
+
+
+# ---- FiLTR step 3: the flank filter of LTR terminal sequences (bin/FiLTR-main/src/LTR_filter.py:44-170) ---------------------------
+# The three `cd-hit-est` calls of the step run as Context.frame_cluster (the definition is in include/hite_gpu.h, "clusters of a
+# group of frames"; parity with the tool is unpinned), the copies come from the build's copy finder, the alignment from the star
+# alignment, the frames and the frame vote from hite_ltr_both_ends / hite_ltr_frame.  ltr_flank_filter is the batched in-memory
+# driver; the functions under the reference's names are wrappers over its parts that keep the `.matrix` directory contract.
+LTR_SORT_OPTIONS = dict(ident=0.8, cov_short=0.3, cov_long=0.0, min_cov=20, min_len=10, both_strands=True)        # data_util.py:2883
+LTR_JOINED_OPTIONS = dict(ident=0.95, cov_short=0.95, cov_long=0.95, min_cov=50, min_len=10, both_strands=True)   # Util.py:10947
+
+
+def ltr_sort_rule(frames, left_clusters, right_clusters):
+    """generate_sort_matrix (bin/FiLTR-main/utils/data_util.py:2833-2870) after its two clusterings: frames = the (left, right) rows
+    of a `.matrix`, left_clusters / right_clusters = the clusters of the gap-free left / right frames (lists of row indices; rows of
+    10 bases or fewer are in none).  -> the kept matrix, rewritten in the LEFT side's order (rows of clusters of several rows first,
+    then the single rows, each in cluster order), or None when the candidate is dropped: a side with one row or none, or with too
+    many homologous rows (0.8 of the rows under 20 rows, else 0.9)."""
+    sides = []
+    for clusters in (left_clusters, right_clusters):
+        homo = [r for cl in clusters if len(cl) > 1 for r in cl]
+        total = homo + [cl[0] for cl in clusters if len(cl) == 1]
+        sides.append((homo, total, 0.8 if len(total) < 20 else 0.9))
+    (lh, lt, l_thr), (rh, rt, r_thr) = sides
+    if len(lt) > 1 and len(rt) > 1 and float(len(lh)) / len(lt) < l_thr and float(len(rh)) / len(rt) < r_thr:
+        return [frames[r] for r in lt]
+    return None
+
+
+def ltr_flank_cluster_rule(clusters):
+    """filter_ltr_by_flanking_cluster_sub (bin/FiLTR-main/src/Util.py:10966-10978) after its clustering of the joined frames: kept
+    when fewer rows are in clusters of several rows than alone"""
+    homo = sum(len(cl) for cl in clusters if len(cl) > 1)
+    return not homo >= sum(1 for cl in clusters if len(cl) == 1)
+
+
+def _ltr_clusters(cluster, groups, options, what):
+    res = cluster(groups, **options)
+    if any(r is None for r in res):
+        raise ValueError("%s: a matrix beyond the limits of frame_cluster (HITE_FRAMECLUSTER_MAX_ROWS rows of HITE_FRAMECLUSTER_MAX_LEN bases)" % what)
+    return res
+
+
+def _ltr_sort_batch(mats, cluster, seconds=None):
+    """the sort rule on a batch of matrices: TWO clustering calls, all left frames and all right frames"""
+    t0 = time.perf_counter()
+    left = _ltr_clusters(cluster, [[l.replace("-", "") for l, _r in m] for m in mats], LTR_SORT_OPTIONS, "sort_matrix_dir")
+    t1 = time.perf_counter()
+    right = _ltr_clusters(cluster, [[r.replace("-", "") for _l, r in m] for m in mats], LTR_SORT_OPTIONS, "sort_matrix_dir")
+    if seconds is not None:
+        seconds["cluster_left"] = t1 - t0
+        seconds["cluster_right"] = time.perf_counter() - t1
+    return [ltr_sort_rule(m, lc, rc) for m, lc, rc in zip(mats, left, right)]
+
+
+def _ltr_joined_batch(mats, cluster, seconds=None):
+    """the joined-flank rule on a batch of matrices: ONE clustering call"""
+    t0 = time.perf_counter()
+    res = _ltr_clusters(cluster, [[(l + r).replace("-", "").replace("\t", "") for l, r in m] for m in mats], LTR_JOINED_OPTIONS,
+                        "filter_ltr_by_flanking_cluster")
+    if seconds is not None:
+        seconds["cluster_joined"] = time.perf_counter() - t0
+    return [ltr_flank_cluster_rule(cl) for cl in res]
+
+
+def _ltr_vote_batch(mats, flanking_len, window, frame_vote):
+    """judge_both_ends_frame (bin/FiLTR-main/src/Util.py:10696-10709) on a batch: the frame vote on either side, one call per side;
+    a matrix of one row or none passes (as judge_left_frame_LTR / judge_right_frame_LTR above)"""
+    idx = [k for k, m in enumerate(mats) if len(m) > 1]
+    ok = [True] * len(mats)
+    for side, col in (("left", 0), ("right", 1)):
+        votes = frame_vote([[row[col] for row in mats[k]] for k in idx], flanking_len, window, side) if idx else []
+        for k, (is_ltr, _b) in zip(idx, votes):
+            ok[k] = ok[k] and bool(is_ltr)
+    return ok
+
+
+def ltr_flank_decide(matrices, flanking_len=100, ctx=None, cluster=None, frame_vote=None, copy_num_threshold=5, sliding_window_size=20,
+                     seconds=None):
+    """The decision rules of FiLTR's step 3 on `.matrix` contents, batched over all candidates: matrices = {name: [(left frame, right
+    frame), ...]}.  In the reference's order: the sort rule (sort_matrix_dir), the joined-flank rule (filter_ltr_by_flanking_cluster),
+    the split at copy_num_threshold rows (get_low_copy_LTR / get_high_copy_LTR; LTR_filter.py passes 5) and the frame vote on both
+    sides (judge_ltr_from_both_ends_frame), merged as alter_deep_learning_results does without a deep-learning table: the homology
+    rule alone.  cluster(groups, **options) and frame_vote(matrices, flank, window, side) default to ctx.frame_cluster and
+    ctx.ltr_frame (the CPU suite passes the twins).
+    -> ({name: (is_ltr, "low" | "high" | None, dropped_by)}, {name: kept matrix of every high-copy candidate}); dropped_by is None
+    for a true LTR, else "sort", "flank_cluster" or "frame_vote"."""
+    if cluster is None or frame_vote is None:
+        ctx = ctx or get_ctx()
+    cluster, frame_vote = cluster or ctx.frame_cluster, frame_vote or ctx.ltr_frame
+    names = list(matrices)
+    table = {}
+    kept = _ltr_sort_batch([matrices[n] for n in names], cluster, seconds) if names else []
+    table.update((n, (False, None, "sort")) for n, m in zip(names, kept) if m is None)
+    names, mats = [n for n, m in zip(names, kept) if m is not None], [m for m in kept if m is not None]
+    keep = _ltr_joined_batch(mats, cluster, seconds) if names else []
+    table.update((n, (False, None, "flank_cluster")) for n, k in zip(names, keep) if not k)
+    names, mats = [n for n, k in zip(names, keep) if k], [m for m, k in zip(mats, keep) if k]
+    t0 = time.perf_counter()
+    votes = _ltr_vote_batch(mats, flanking_len, sliding_window_size, frame_vote) if names else []
+    if seconds is not None:
+        seconds["frame_vote"] = time.perf_counter() - t0
+    high = {}
+    for n, m, ok in zip(names, mats, votes):
+        label = "low" if len(m) <= copy_num_threshold else "high"
+        table[n] = (bool(ok), label, None if ok else "frame_vote")
+        if label == "high":
+            high[n] = m
+    return table, high
+
+
+def ltr_terminal_frames(terminals, reference, flanking_len=100, max_copy_num=100, ctx=None, seconds=None):
+    """generate_both_ends_frame_from_seq_minimap2 (bin/FiLTR-main/src/Util.py:956-1042) in memory, batched: terminals = {name:
+    sequence}; the copies of every terminal sequence from the build's copy finder on the resident genome (where the reference runs
+    minimap2; ctx, when given, holds `reference` packed in file order), the windows +- flanking_len (:978-1018: a window that leaves
+    its contig or has fewer than 100 bases is skipped, the minus strand is reverse-complemented; when a candidate has windows of
+    more than 1 000 bases only those are aligned, as their first 500 + last 500 bases), the first 100 members in copy order
+    (extract_copies, :1305: the first max_num records of the file, not the longest), ONE star alignment and ONE frame call for all
+    candidates; the anchor sequence is the first member without its flanks (generate_msa, :1315-1338).  max_copy_num is the
+    reference's argument (its minimap2 -N is three times that; the copy finder keeps up to 300 copies) and steers nothing here.
+    -> ({name: [(left frame, right frame), ...]}, {name: full-length rows}) for the candidates whose boundary was found."""
+    t = [time.perf_counter()]
+    lap = lambda key: (t.append(time.perf_counter()), seconds is not None and seconds.__setitem__(key, t[-1] - t[-2]))  # noqa: E731
+    ctx = ctx or set_reference(reference)
+    ref_names, ref_contigs = read_fasta(reference)
+    names = list(terminals)
+    tab = ctx.find_copies([terminals[n] for n in names]) if names else []
+    lap("copies")
+    q_names, groups, anchors = [], [], []
+    for n, copies in zip(names, tab):
+        extend, trunc = {}, {}
+        for contig, start1, end1, minus, _anchors in copies:
+            seq = ref_contigs[ref_names[contig]]
+            if start1 - 1 - flanking_len < 0 or end1 + flanking_len > len(seq):
+                continue
+            win = seq[start1 - 1 - flanking_len:end1 + flanking_len]
+            if minus:
+                win = getReverseSequence(win)
+            if len(win) < 100:
+                continue
+            key = (contig, start1, end1, bool(minus))
+            extend[key] = win
+            if len(win) > 1000:
+                trunc[key] = win[:500] + win[-500:]
+        members = list((trunc or extend).values())[:100]
+        if members:
+            q_names.append(n)
+            groups.append(members)
+            anchors.append(members[0][flanking_len:-flanking_len])
+    lap("windows")
+    msas = ctx.star_msa(groups) if groups else []
+    lap("msa")
+    ok = [k for k, m in enumerate(msas) if m is not None]
+    ends = ctx.ltr_both_ends([[bytes(r) for r in msas[k]] for k in ok], [anchors[k] for k in ok], flanking_len) if ok else []
+    lap("both_ends")
+    frames, full = {}, {}
+    for k, res in zip(ok, ends):
+        if res is not None:
+            frames[q_names[k]], full[q_names[k]] = res[0], res[1]
+    return frames, full
+
+
+def ltr_flank_filter(terminals, reference, flanking_len=100, max_copy_num=100, ctx=None, cluster=None, frame_vote=None, seconds=None):
+    """FiLTR's "Step 3: filter out false positive sequences based on the flanking regions of the terminal sequences"
+    (bin/FiLTR-main/src/LTR_filter.py:44-170) for a set of LTR terminal sequences (a FASTA path or {name: sequence}) against
+    `reference`, without the deep model: ltr_terminal_frames, then ltr_flank_decide.  A true LTR is a candidate whose copies' flanks
+    are mostly not alike.  seconds: a dict that receives the wall seconds of every step.
+    -> ({name: (is_ltr, "low" | "high" | None, dropped_by)}, {name: kept high-copy matrix}); dropped_by "frames" = no copy window
+    or no boundary in the alignment (the reference writes no `.matrix` for such a candidate), else as ltr_flank_decide."""
+    if not isinstance(terminals, dict):
+        t_names, t_contigs = read_fasta(terminals)
+        terminals = {n: t_contigs[n] for n in t_names}
+    frames, _full = ltr_terminal_frames(terminals, reference, flanking_len, max_copy_num, ctx, seconds)
+    table, high = ltr_flank_decide(frames, flanking_len, ctx or get_ctx(), cluster, frame_vote, seconds=seconds)
+    return {n: table.get(n, (False, None, "frames")) for n in terminals}, high
+
+
+def _read_matrix_dir(matrix_dir):
+    """{name: [(left, right), ...]} of every `.matrix` under matrix_dir (find_files_recursively), by path"""
+    out = {}
+    for root, _dirs, files in sorted(os.walk(matrix_dir)):
+        for f in sorted(files):
+            if f.endswith(".matrix"):
+                with open(os.path.join(root, f)) as fh:
+                    out[f.split(".")[0]] = [tuple((line.replace("\n", "").split("\t") + [""])[:2]) for line in fh]
+    return out
+
+
+def _write_matrix(path, rows):
+    with open(path, "w") as f:
+        for left, right in rows:
+            f.write(left + "\t" + right + "\n")
+
+
+def generate_both_ends_frame_from_seq_minimap2(candidate_sequence_path, reference, flanking_len, threads, temp_dir, output_dir,
+                                               full_length_output_dir, max_copy_num, ctx=None):
+    """bin/FiLTR-main/src/Util.py:956: <output_dir>/<name>.matrix and <full_length_output_dir>/<name>.matrix of every terminal
+    sequence with a boundary, from ONE batched call (ltr_terminal_frames); threads and temp_dir have nothing to steer here"""
+    for d in (output_dir, full_length_output_dir):
+        if os.path.exists(d):
+            shutil.rmtree(d)
+        os.makedirs(d, exist_ok=True)
+    names, contigs = read_fasta(candidate_sequence_path)
+    frames, full = ltr_terminal_frames({n: contigs[n] for n in names}, reference, flanking_len, max_copy_num, ctx)
+    for n, rows in frames.items():
+        _write_matrix(os.path.join(output_dir, n + ".matrix"), rows)
+        with open(os.path.join(full_length_output_dir, n + ".matrix"), "w") as f:
+            for row in full[n]:
+                f.write(row + "\n")
+
+
+def sort_matrix_dir(source_dir, target_dir, temp_dir, threads, ctx=None, cluster=None):
+    """bin/FiLTR-main/utils/data_util.py:2792: the kept matrices of source_dir, rewritten, in target_dir -> (input_num, keep_num)"""
+    os.makedirs(target_dir, exist_ok=True)
+    mats = _read_matrix_dir(source_dir)
+    kept = _ltr_sort_batch(list(mats.values()), cluster or (ctx or get_ctx()).frame_cluster) if mats else []
+    for n, rows in zip(mats, kept):
+        if rows is not None:
+            _write_matrix(os.path.join(target_dir, n + ".matrix"), rows)
+    return len(mats), sum(1 for rows in kept if rows is not None)
+
+
+def filter_ltr_by_flanking_cluster(output_dir, target_dir, temp_dir, threads, log, ctx=None, cluster=None):
+    """bin/FiLTR-main/src/Util.py:10985: the matrices of output_dir that pass the joined-flank rule are copied to target_dir"""
+    shutil.rmtree(target_dir, ignore_errors=True)
+    os.makedirs(target_dir, exist_ok=True)
+    mats = _read_matrix_dir(output_dir)
+    keep = _ltr_joined_batch(list(mats.values()), cluster or (ctx or get_ctx()).frame_cluster) if mats else []
+    for (n, rows), k in zip(mats.items(), keep):
+        if k:
+            _write_matrix(os.path.join(target_dir, n + ".matrix"), rows)
+    if log is not None:
+        log.logger.debug("Input LTR num: " + str(len(mats)) + ", keep LTR num: " + str(sum(keep)))
+
+
+def _copy_matrices_by_rows(output_dir, target_dir, want):
+    shutil.rmtree(target_dir, ignore_errors=True)
+    os.makedirs(target_dir)
+    for name in sorted(os.listdir(output_dir)):
+        path = os.path.join(output_dir, name)
+        with open(path) as f:
+            rows = sum(1 for _line in f)
+        if want(rows):
+            shutil.copy(path, target_dir)
+
+
+def get_low_copy_LTR(output_dir, low_copy_output_dir, threads, copy_num_threshold=3):
+    """bin/FiLTR-main/src/Util.py:10368: the matrices of at most copy_num_threshold rows"""
+    _copy_matrices_by_rows(output_dir, low_copy_output_dir, lambda rows: rows <= copy_num_threshold)
+
+
+def get_high_copy_LTR(output_dir, high_copy_output_dir, threads, copy_num_threshold=3):
+    """bin/FiLTR-main/src/Util.py:10406: the matrices of more than copy_num_threshold rows"""
+    _copy_matrices_by_rows(output_dir, high_copy_output_dir, lambda rows: rows > copy_num_threshold)
+
+
+def judge_ltr_from_both_ends_frame(output_dir, output_path, threads, type, flanking_len, log, sliding_window_size=20, ctx=None,
+                                   frame_vote=None):
+    """bin/FiLTR-main/src/Util.py:10477: 'name\\t0|1' per matrix of output_dir, from two batched frame votes"""
+    mats = _read_matrix_dir(output_dir)
+    votes = _ltr_vote_batch(list(mats.values()), flanking_len, sliding_window_size, frame_vote or (ctx or get_ctx()).ltr_frame) if mats else []
+    if log is not None:
+        log.logger.debug(type + " LTR num: " + str(len(mats)) + ", LTR Homo filter LTR num: " + str(len(votes) - sum(votes)) +
+                         ", remain LTR num: " + str(sum(votes)))
+    with open(output_path, "w") as f_save:
+        for n, ok in zip(mats, votes):
+            f_save.write(n + "\t" + str(1 if ok else 0) + "\n")

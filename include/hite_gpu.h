@@ -265,6 +265,41 @@ int hite_msa_consensus(hite_ctx *ctx, int32_t nmat, const int32_t *rows, const i
 int hite_msa_subcluster(hite_ctx *ctx, int32_t nmat, const int32_t *rows, const int64_t *cols, const int64_t *mat_off,
                         const uint8_t *mats, double cutoff, const int64_t *row_off, int32_t *sub_of_row, int32_t *n_sub);
 
+/* ---- clusters of a group of frames --- the three `cd-hit-est` calls of FiLTR's step 3 (bin/FiLTR-main/utils/data_util.py:2872-2920
+ * sort_frame, `-aS 0.3 -c 0.8 -G 0 -g 1 -A 20` on the left and on the right frames of a candidate's copies;
+ * bin/FiLTR-main/src/Util.py:10938-10983 filter_ltr_by_flanking_cluster_sub, `-aS 0.95 -aL 0.95 -c 0.95 -G 0 -g 1 -A 50` on the
+ * joined frames).  The tool is not pinned: what is computed is the definition below (twin tests/framecluster_twin.py), not the
+ * tool's word filter, banded affine alignment or `-g 1` choice of the best cluster.
+ *  - Bytes: letters count in either case; anything outside ACGT is N, and N matches nothing, not even N.  Callers strip '-' first.
+ *  - Pair value R(A, B): a value is a tuple (score, matches, columns, bases of A, bases of B), compared lexicographically;
+ *    E = (0, 0, 0, 0, 0).  V(i, 0) = V(0, j) = E.  For i, j >= 1, V(i, j) is the largest of
+ *        V(i-1, j-1) + (+2, 1, 1, 1, 1) when A[i] = B[j] and both are in ACGT, else V(i-1, j-1) + (-2, 0, 1, 1, 1);
+ *        V(i-1, j)   + (-3, 0, 1, 1, 0);
+ *        V(i, j-1)   + (-3, 0, 1, 0, 1);
+ *    replaced by E when its score is <= 0.  R(A, B) is the largest V over all cells (E when a sequence is empty).  It is this
+ *    recurrence, not a claim of optimality over alignment paths.  With both_strands, R is the larger of R(A, B) and
+ *    R(A, revcomp(B)).  (The fields fit 10 + 9 + 10 + 9 + 9 bits: one 64-bit integer maximum is the whole rule.)
+ *  - Similar(A, B), A the earlier row in cluster order and B the later, R = (s, k, c, a, b): c > 0, and
+ *    (double)k >= ident * (double)c, and a >= min_cov and b >= min_cov, and (double)a >= cov_long * (double)|A|, and
+ *    (double)b >= cov_short * (double)|B|; every compare in binary64 exactly as written.
+ *  - A group: rows with length <= min_len are dropped (cluster_of_row = -1; they count nowhere; cd-hit's `-l`, callers pass 10).
+ *    The others are taken by length descending, ties by ascending row index.  A row joins the FIRST representative, in order of
+ *    creation, that it is similar to; otherwise it becomes the next representative.  cluster_of_row = the cluster's creation
+ *    index, n_cluster[g] = the number of clusters.
+ * Layout: the rows of group g are row_off[g] .. row_off[g+1] (n_group + 1 ascending entries, row_off[0] >= 0); row r is the bytes
+ * seqs + seq_off[r] .. seq_off[r+1] (ascending; any byte offset).  A group of more than HITE_FRAMECLUSTER_MAX_ROWS rows, or holding
+ * a row longer than HITE_FRAMECLUSTER_MAX_LEN, gets n_cluster[g] = -1 and -1 on all its rows; the other groups are unaffected.
+ * n_group = 0, empty groups and empty rows are valid.  HITE_EINVAL for a negative count (n_group, min_cov, min_len), a missing
+ * buffer, descending offsets and a threshold (ident, cov_short, cov_long) that is NaN or outside [0, 1]; the context stays usable.
+ * The groups go to the device in batches of bounded sequence bytes ($HITE_FRAMECLUSTER_BATCH_BYTES, read by hite_ctx_create, sets a
+ * smaller batch: a test knob that never changes a result; default 64 MiB); the work is on the context's stream and scratch. */
+#define HITE_FRAMECLUSTER_MAX_ROWS 128
+#define HITE_FRAMECLUSTER_MAX_LEN  256
+int hite_frame_cluster(hite_ctx *ctx, int64_t n_group, const int64_t *row_off /* n_group + 1 */,
+                       const uint8_t *seqs, const int64_t *seq_off /* rows + 1 */,
+                       double ident, double cov_short, double cov_long, int32_t min_cov, int32_t min_len,
+                       int32_t both_strands, int32_t *cluster_of_row, int32_t *n_cluster);
+
 /* ---- LTR frames of the vendored FiLTR --- get_both_ends_frame  bin/FiLTR-main/src/Util.py:1401-1497 (+ :1341-1399) -----
  * Batch of alignments (rows[a] x cols[a] bytes at msa + msa_off[a], upper case) with the terminal sequence of each
  * (cand + cand_off[a] .. cand_off[a+1]).  Per alignment: anchors from the first row carrying both 20-mers within two
