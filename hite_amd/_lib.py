@@ -452,6 +452,39 @@ class Context:
         out[:, 0], out[:, 1] = cost, mat
         return out
 
+    # ---- local alignments of pairs of intervals (the `blastn -query .. -subject .. -outfmt 6` of FiLTR's steps 1 and 2) -----
+    def pair_hsps(self, seqs, pairs, diag_min=None):
+        """seqs: str / bytes; pairs: rows (a_id, a_start, a_end, b_id, b_start, b_end), intervals 0-based and half-open -> per pair
+        None (beyond HITE_PAIRHSP_MAX_LEN, empty, or outside its sequences) or the list of its HSPs, each the 7-tuple (q_start, q_end,
+        s_start, s_end, score, matches, columns) with 1-based inclusive coordinates inside the intervals, in the order
+        include/hite_gpu.h defines ("local alignments of pairs of intervals"; hite_pair_hsps).  Plus strand only; diag_min: only
+        word hits and cells with s - q >= diag_min count (None: no limit)."""
+        pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 6)
+        n = len(pr)
+        if n == 0:
+            self._check(self.lib.hite_pair_hsps(self.h, C.c_int64(0), None, None, C.c_int64(0), None, None, None, None, None, None, C.c_int32(0),
+                                                C.c_int64(0), None, None, None, None), "hite_pair_hsps")
+            return []
+        buf, off = self._csr(seqs)
+        ai, bi = _arr(pr[:, 0], np.int32), _arr(pr[:, 3], np.int32)
+        if (ai != pr[:, 0]).any() or (bi != pr[:, 3]).any():
+            raise HiteError("pair_hsps: a sequence id does not fit 32 bits")
+        cols = [_arr(pr[:, k], np.int64) for k in (1, 2, 4, 5)]
+        dm = -2 ** 31 if diag_min is None else int(diag_min)
+        status, first, n_out = np.zeros(n, dtype=np.int32), np.zeros(n + 1, dtype=np.int64), C.c_int64(0)
+        cap = 2 * n + 16
+        while True:
+            recs = np.zeros((cap, 7), dtype=np.int32)
+            rc = self.lib.hite_pair_hsps(self.h, C.c_int64(len(off) - 1), _p(buf), _p(off), C.c_int64(n), _p(ai), _p(cols[0]), _p(cols[1]), _p(bi),
+                                         _p(cols[2]), _p(cols[3]), C.c_int32(dm), C.c_int64(cap), _p(status), _p(first), _p(recs), C.byref(n_out))
+            if rc == -4 and n_out.value > cap:       # HITE_ECAP: now the room is known
+                cap = n_out.value
+                continue
+            self._check(rc, "hite_pair_hsps")
+            break
+        rows, at = recs[:n_out.value].tolist(), first.tolist()
+        return [None if status[p] < 0 else [tuple(r) for r in rows[at[p]:at[p + 1]]] for p in range(n)]
+
     # ---- Helitron candidate scan (multi_process_helitronscanner, Util.py:263: HelitronScanner.jar) ---------------------------
     def _helitron_args(self, seqs, head_patterns, tail_patterns):
         buf, off = self._csr(seqs)

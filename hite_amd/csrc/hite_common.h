@@ -87,6 +87,7 @@ struct hite_ctx {
     int32_t subcluster_chunk;       // rows per chunk of hite_msa_subcluster: HITE_SUBCLUSTER_CHUNK or $HITE_SUBCLUSTER_CHUNK_ROWS (hite_ctx_create)
     int64_t subcluster_batch_bytes; // alignment bytes it sends up at a time ($HITE_SUBCLUSTER_BATCH_BYTES; 0: its default)
     int64_t framecluster_batch_bytes; // sequence bytes hite_frame_cluster sends up at a time ($HITE_FRAMECLUSTER_BATCH_BYTES; 0: its default)
+    int64_t pairhsp_batch_pairs;      // pairs hite_pair_hsps sends up at a time ($HITE_PAIRHSP_BATCH_PAIRS; 0: its default)
 };
 void hite_fmea_release(hite_ctx *ctx);
 int hite_aux_streams(hite_ctx *ctx, int k, hipStream_t *st, hipEvent_t *fork_ev, hipEvent_t *join_ev);

@@ -260,3 +260,168 @@ def make_ltr_flank_genome(plan, genome_bp=450_000, chrom_bp=150_000, seed=1, ter
             pos = (si + 1) * slot + homo_len + 150 - lead
             genome[ci][pos:pos + len(unit)] = ASCII[unit]
     return dict(contigs=[g.tobytes().decode() for g in genome], names=names, terminals=terminals, kind=kind, copies=copies)
+
+
+LTR_ELEMENT_KINDS = ("clean", "recomb", "nested", "overhang", "shifted", "dirty", "dup")
+_LTR_SLOT = 10_000          # bases of chromosome per planted element (the longest is 2 x 1 200 + 6 000 and its guards)
+_LTR_GUARD = 12             # bases outside a terminal that cannot match the other terminal's (disjoint alphabets)
+_LTR_CLEAN_END = 20         # bases at both ends of a terminal that its second copy keeps unchanged
+
+
+def _diverged_terminal(rng, term, div, n_indel):
+    """the second copy of a terminal: substitutions at rate div and n_indel indels of 1 .. 3 bases, its two ends left as they are"""
+    s = term.copy()
+    L = len(s)
+    m = rng.random(L) < div
+    m[:_LTR_CLEAN_END] = False
+    m[L - _LTR_CLEAN_END:] = False
+    if m.any():
+        s[m] = (s[m] + rng.integers(1, 4, size=int(m.sum())).astype(np.uint8)) & 3
+    for _ in range(n_indel):
+        pos = int(rng.integers(2 * _LTR_CLEAN_END, len(s) - 2 * _LTR_CLEAN_END))
+        k = int(rng.integers(1, 4))
+        s = np.delete(s, np.arange(pos, pos + k)) if rng.integers(0, 2) else np.insert(s, pos, rng.integers(0, 4, size=k).astype(np.uint8))
+    return s
+
+
+def _ltr_element(rng, kind, term_len, int_len):
+    """one planted element -> (codes of the element and its guards, dict of 0-based half-open intervals inside them: left, right and,
+    by kind, repeat (start of the first copy, end of the second) / inner (another element's intervals))"""
+    term = _rand_codes(rng, term_len)
+    right = _diverged_terminal(rng, term, float(rng.uniform(0.01, 0.08)), int(rng.integers(0, 4)))
+    inner = None
+    if kind == "recomb":        # a third copy of the terminal inside the internal sequence
+        a = int_len // 3
+        internal = np.concatenate([_rand_codes(rng, a), _diverged_terminal(rng, term, 0.02, 0), _rand_codes(rng, max(200, int_len - a - term_len))])
+    elif kind == "nested":      # a direct repeat of >= 400 bases, more than 500 apart, inside the internal sequence
+        rep = _rand_codes(rng, int(rng.integers(400, 601)))
+        gap = int(rng.integers(600, 1201))
+        a = int(rng.integers(150, 400))
+        internal = np.concatenate([_rand_codes(rng, a), rep, _rand_codes(rng, gap), _diverged_terminal(rng, rep, 0.02, 0),
+                                   _rand_codes(rng, max(150, int_len - a - 2 * len(rep) - gap))])
+        inner = ("repeat", a, a + 2 * len(rep) + gap)
+    elif kind == "dirty":       # a whole element of its own family inside the internal sequence
+        sub, sub_iv = _ltr_element(rng, "clean", int(rng.integers(150, 301)), int(rng.integers(1500, 2001)))
+        a = int(rng.integers(300, 600))
+        internal = np.concatenate([_rand_codes(rng, a), sub, _rand_codes(rng, int(rng.integers(300, 600)))])
+        inner = ("inner", a, sub_iv)
+    else:
+        internal = _rand_codes(rng, int_len)
+    over = 120 if kind == "overhang" else 0       # the annotated terminals are the middle of a longer duplicated segment
+    if over:
+        ol, orr = _rand_codes(rng, over), _rand_codes(rng, over)
+        left_unit = np.concatenate([ol, term, orr])
+        right_unit = np.concatenate([_diverged_terminal(rng, ol, 0.02, 0), right, _diverged_terminal(rng, orr, 0.02, 0)])
+    else:
+        left_unit, right_unit = term, right
+    # guards: what lies next to the left unit is drawn from {A, C}, next to the right unit from {G, T}
+    g = lambda pair: np.array(pair, dtype=np.uint8)[rng.integers(0, 2, size=_LTR_GUARD)]  # noqa: E731
+    parts = [g((0, 1)), left_unit, g((0, 1)), internal, g((2, 3)), right_unit, g((2, 3))]
+    at = np.cumsum([0] + [len(p) for p in parts])
+    iv = dict(left=(int(at[1]) + over, int(at[2]) - over), right=(int(at[5]) + over, int(at[6]) - over))
+    if inner is not None and inner[0] == "repeat":
+        iv["repeat"] = (int(at[3]) + inner[1], int(at[3]) + inner[2])
+    if inner is not None and inner[0] == "inner":
+        iv["inner"] = {k: (int(at[3]) + inner[1] + v[0], int(at[3]) + inner[1] + v[1]) for k, v in inner[2].items()}
+    return np.concatenate(parts), iv
+
+
+def _scn_line(left, right, seq_id, chr_name, shift=(0, 0)):
+    """the twelve space-separated fields of a candidate line from 0-based half-open terminal intervals; shift moves the annotated
+    starts and ends"""
+    ls, le, rs, re_ = left[0] + 1 + shift[0], left[1] + shift[1], right[0] + 1 + shift[0], right[1] + shift[1]
+    return " ".join(str(x) for x in (ls, re_, re_ - ls + 1, ls, le, le - ls + 1, rs, re_, re_ - rs + 1, "95.00", seq_id, chr_name))
+
+
+def make_ltr_element_genome(plan, seed=1, chrom_elements=12):
+    """A genome of whole LTR elements for the `.scn` filters (util.ltr_scn_filter; tests and tools/ltr_scn_bench.py): plan = [(kind,
+    count), ...] with the kinds
+      "clean"     two terminals (150 .. 1 200 bases, the second 1 .. 8 % diverged with up to three short indels) around a random
+                  internal sequence (1 500 .. 6 000 bases), annotated exactly;
+      "recomb"    a third copy of the terminal inside the internal sequence;
+      "nested"    a direct repeat of 400 .. 600 bases at 98 % identity, more than 500 apart, inside the internal sequence;
+      "overhang"  the annotated terminals are the middle of a longer duplicated segment (120 more bases on both sides);
+      "shifted"   annotated starts 5 bases late and ends 4 bases early;
+      "dirty"     a whole smaller element (terminals of at most 300 bases) inside the internal sequence, with its own line;
+      "dup"       a clean element whose line is there twice.
+    Elements lie in random sequence, chrom_elements to a chromosome, in random order; the bases next to the two terminals are drawn
+    from disjoint alphabets, so an alignment of the terminals ends at their boundary.
+    -> dict(contigs {name: sequence}, scn (the text of the candidate table, sorted by chromosome and start), truth [dict(kind, id,
+    line, name (chr-start-end of the left terminal), and by kind adjusted (the line with the true boundaries) / repeat ((start of the
+    first copy, end of the second), 1-based) / inner (id of the element inside)])"""
+    rng = np.random.default_rng(seed)
+    kinds = [k for k, n in plan for _ in range(n)]
+    for k in kinds:
+        if k not in LTR_ELEMENT_KINDS:
+            raise ValueError("unknown kind " + k)
+    kinds = [kinds[i] for i in rng.permutation(len(kinds))]
+    contigs, lines, truth = {}, [], []
+    for c0 in range(0, len(kinds), chrom_elements):
+        chr_name = "chr%d" % (c0 // chrom_elements + 1)
+        chunk = kinds[c0:c0 + chrom_elements]
+        seq = _rand_codes(rng, _LTR_SLOT * len(chunk) + 1000)
+        for e, kind in enumerate(chunk):
+            unit, iv = _ltr_element(rng, kind, int(rng.integers(150, 1201)), int(rng.integers(1500, 6001)))
+            pos = 500 + e * _LTR_SLOT + int(rng.integers(0, 300))
+            seq[pos:pos + len(unit)] = unit
+            mv = lambda t: (t[0] + pos, t[1] + pos)  # noqa: E731
+            seq_id = len(truth)
+            left, right = mv(iv["left"]), mv(iv["right"])
+            line = _scn_line(left, right, seq_id, chr_name, (5, -4) if kind == "shifted" else (0, 0))
+            parts = line.split(" ")
+            t = dict(kind=kind, id=seq_id, line=line, name="%s-%s-%s" % (chr_name, parts[3], parts[4]))
+            if kind == "shifted":
+                t["adjusted"] = _scn_line(left, right, seq_id, chr_name)
+                # (the adjusted line keeps the annotated fields 0 .. 2: the reference rewrites fields 3 .. 8 only)
+                t["adjusted"] = " ".join(parts[:3] + t["adjusted"].split(" ")[3:])
+            if kind == "nested":
+                t["repeat"] = (iv["repeat"][0] + pos + 1, iv["repeat"][1] + pos)
+            truth.append(t)
+            lines.append((chr_name, int(parts[0]), line))
+            if kind == "dup":
+                lines.append((chr_name, int(parts[0]), line))
+            if kind == "dirty":
+                sub = {k: mv(v) for k, v in iv["inner"].items()}
+                sub_id = len(truth)
+                sub_line = _scn_line(sub["left"], sub["right"], sub_id, chr_name)
+                sp = sub_line.split(" ")
+                t["inner"] = sub_id
+                truth.append(dict(kind="inner", id=sub_id, line=sub_line, name="%s-%s-%s" % (chr_name, sp[3], sp[4])))
+                lines.append((chr_name, int(sp[0]), sub_line))
+        contigs[chr_name] = ASCII[seq].tobytes().decode()
+    order = sorted(range(len(lines)), key=lambda k: (int(lines[k][0][3:]), lines[k][1]))
+    scn = "# planted LTR elements: start end len lLTR_start lLTR_end lLTR_len rLTR_start rLTR_end rLTR_len similarity seq_id chr\n" + \
+        "".join(lines[k][2] + "\n" for k in order)
+    return dict(contigs=contigs, scn=scn, truth=truth)
+
+
+def ltr_element_decisions(truth, recomb_lines, final_lines, dirty_dicts):
+    """what util.ltr_scn_filter did with the elements of make_ltr_element_genome against what was planted: recomb_lines / final_lines =
+    the lines of remove_recomb.scn / filter_terminal_align.scn.  -> {kind: [as planted, elements]} and the ids that are not"""
+    final, recomb = {}, {}
+    for dst, src in ((final, final_lines), (recomb, recomb_lines)):
+        for line in src:
+            dst.setdefault(int(line.split(" ")[10]), []).append(line)
+    table, wrong = {}, []
+    for t in truth:
+        f, r = final.get(t["id"], []), recomb.get(t["id"], [])
+        kind = t["kind"]
+        if kind == "recomb":
+            ok = not r and not f
+        elif kind == "overhang":
+            ok = r == [t["line"]] and not f
+        elif kind == "shifted":
+            ok = f == [t["line"], t["adjusted"]]
+        elif kind == "nested":
+            extra = [x.split(" ") for x in f if x != t["line"]]
+            ok = t["line"] in f and any(abs(int(x[3]) - t["repeat"][0]) <= 5 and abs(int(x[7]) - t["repeat"][1]) <= 5 for x in extra)
+        else:       # clean, dup, dirty, inner: the line once, nothing else
+            ok = f == [t["line"]]
+        # (the new line of a nested element lies inside its internal sequence, so remove_dirty_LTR names that element too)
+        ok = ok and ((t["name"] in dirty_dicts) == (kind in ("dirty", "nested")))
+        n = table.setdefault(kind, [0, 0])
+        n[0] += bool(ok)
+        n[1] += 1
+        if not ok:
+            wrong.append(t["id"])
+    return table, wrong

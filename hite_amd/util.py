@@ -16,6 +16,7 @@ The flank filter of LTR terminal sequences (ltr_flank_filter: step 3 of the vend
 runs its three `cd-hit-est` calls per candidate as batched calls of the build's own clustering of frames (Context.frame_cluster).
 """
 import itertools
+import json
 import math
 import os
 import re
@@ -2104,3 +2105,317 @@ def judge_ltr_from_both_ends_frame(output_dir, output_path, threads, type, flank
     with open(output_path, "w") as f_save:
         for n, ok in zip(mats, votes):
             f_save.write(n + "\t" + str(1 if ok else 0) + "\n")
+
+
+# ---- FiLTR steps 1 and 2: the filters on the lines of the `.scn` candidate table (bin/FiLTR-main/src/LTR_filter.py:542-589) -------
+# Where the reference writes two FASTA files and starts one `blastn -query .. -subject .. -outfmt 6` process per candidate line, every
+# function here makes ONE batched call of Context.pair_hsps (the definition is in include/hite_gpu.h, "local alignments of pairs of
+# intervals"; parity with blastn is unpinned: plus strand only, no e-value, bands of 192 diagonals, no X-drop).  The rules around the
+# search are the reference's.  hsps= replaces the search (the signature of Context.pair_hsps; the CPU tests pass the twin).  A pair
+# the search refuses (an interval beyond HITE_PAIRHSP_MAX_LEN) is treated as the reference treats a failed blastn process.
+def _scn_log(log, level, msg):
+    if log is not None:
+        getattr(log.logger, level)(msg)
+
+
+def _py_slice(seq_len, start, stop):
+    """the interval seq[start:stop] covers, as Python slices (a negative index counts from the end): (begin, end), end >= begin"""
+    a, b, _ = slice(start, stop).indices(seq_len)
+    return a, max(a, b)
+
+
+def _contig_ids(ref_contigs):
+    names = list(ref_contigs)
+    return [ref_contigs[n] for n in names], {n: k for k, n in enumerate(names)}
+
+
+def read_scn(scn_file, log, remove_dup=False):
+    """bin/FiLTR-main/src/Util.py:182 -> ({index: (chr_name, left_ltr_start, left_ltr_end, right_ltr_start, right_ltr_end)}, {index:
+    line}); remove_dup drops a line whose (parts[0], parts[1], chr_name) was seen before"""
+    ltr_candidates, ltr_lines = {}, {}
+    existing_records = set()
+    remove_count = total_lines = candidate_index = 0
+    with open(scn_file, "r") as f_r:
+        for line in f_r:
+            if line.startswith("#") or line.strip() == "":
+                continue
+            line = line.replace("\n", "")
+            parts = line.split(" ")
+            chr_name = parts[11]
+            total_lines += 1
+            if remove_dup:
+                cur_record = (int(parts[0]), int(parts[1]), chr_name)
+                if cur_record in existing_records:
+                    remove_count += 1
+                    continue
+                existing_records.add(cur_record)
+            ltr_candidates[candidate_index] = (chr_name, int(parts[3]), int(parts[4]), int(parts[6]), int(parts[7]))
+            ltr_lines[candidate_index] = line
+            candidate_index += 1
+    if remove_dup:
+        _scn_log(log, "debug", "Total LTR num: " + str(total_lines))
+        _scn_log(log, "debug", "Remove " + str(remove_count) + " replicate LTR in scn file, remaining LTR num: " + str(len(ltr_candidates)))
+    return ltr_candidates, ltr_lines
+
+
+def store_scn(confident_lines, confident_scn):
+    """bin/FiLTR-main/src/Util.py:219"""
+    with open(confident_scn, "w") as f_save:
+        for line in confident_lines:
+            f_save.write(line + "\n")
+
+
+def get_recombination_ltr(ltr_candidates, ref_contigs, threads, temp_dir, log, ctx=None, hsps=None):
+    """FiLTR step 1a (bin/FiLTR-main/src/Util.py:7099, is_recombination :5923): the left terminal against the candidate's own
+    internal sequence ref_seq[left_ltr_end : right_ltr_start - 1]; a candidate is recombinant when some HSP covers 95 % of the
+    terminal ((q_end - q_start + 1) / query_len >= 0.95).  One batched search; threads and temp_dir are the reference's arguments
+    and steer nothing.  -> the recombinant candidate indices, in candidate order (the reference's order is that of its processes)"""
+    _scn_log(log, "info", "Start get recombination ltr")
+    seqs, ids = _contig_ids(ref_contigs)
+    jobs, pairs = [], []
+    for candidate_index, (chr_name, left_ltr_start, left_ltr_end, right_ltr_start, _right_ltr_end) in ltr_candidates.items():
+        if chr_name not in ref_contigs:
+            raise ValueError("Chromosome names in the SCN file do not match the input genome names: " + chr_name)
+        n = len(ref_contigs[chr_name])
+        q0, q1 = _py_slice(n, left_ltr_start - 1, left_ltr_end)
+        s0, s1 = _py_slice(n, left_ltr_end, right_ltr_start - 1)
+        if q1 > q0 and s1 > s0:
+            jobs.append((candidate_index, q1 - q0))
+            pairs.append((ids[chr_name], q0, q1, ids[chr_name], s0, s1))
+    res = (hsps or (ctx or get_ctx()).pair_hsps)(seqs, pairs) if pairs else []
+    refused = sum(r is None for r in res)
+    if refused:
+        _scn_log(log, "debug", "get_recombination_ltr: " + str(refused) + " pairs beyond the limits of the search, taken as not recombinant")
+    return [ci for (ci, query_len), r in zip(jobs, res) if r is not None and any((abs(h[1] - h[0]) + 1) / query_len >= 0.95 for h in r)]
+
+
+def blast6_identity(matches, columns):
+    """the third column of a blast6 line as the reference parses it: percent identity with three decimals"""
+    return float("%.3f" % (100.0 * matches / columns))
+
+
+def ltr_lines_from_hsps(line, lLTR_end, chr_name, seq_id, hsp_list):
+    """get_ltr_from_line (bin/FiLTR-main/src/Util.py:11170-11223) after its search: the candidate's line and one new line per direct
+    repeat inside its internal sequence (identity > 95, both sides > 300 bases, more than 500 apart), then the redundancy pass"""
+    new_lines = [line.split(" ")]
+    for q_start, q_end, s_start, s_end, _score, matches, columns in hsp_list:
+        q_len, s_len = abs(q_end - q_start), abs(s_end - s_start)
+        identity = blast6_identity(matches, columns)
+        if identity > 95 and q_len > 300 and s_len > 300 and q_end > q_start and s_end > s_start and s_start - q_end > 500:
+            new_lLTR_start, new_lLTR_end = lLTR_end + q_start, lLTR_end + q_end
+            new_rLTR_start, new_rLTR_end = lLTR_end + s_start, lLTR_end + s_end
+            new_lines.append([new_lLTR_start, new_rLTR_end, new_rLTR_end - new_lLTR_start + 1,
+                              new_lLTR_start, new_lLTR_end, new_lLTR_end - new_lLTR_start + 1,
+                              new_rLTR_start, new_rLTR_end, new_rLTR_end - new_rLTR_start + 1, identity, seq_id, chr_name])
+    new_lines.sort(key=lambda x: (int(x[0]), -int(x[1])))
+    filtered_new_lines = []
+    for i in range(len(new_lines) - 1, -1, -1):
+        cur_item = new_lines[i]
+        cur_lLTR_start, cur_rLTR_end, cur_LTR_len = int(cur_item[0]), int(cur_item[1]), int(cur_item[2])
+        is_redundant = False
+        for j in range(i - 1, -1, -1):
+            next_item = new_lines[j]
+            overlap_length = min(cur_rLTR_end, int(next_item[1])) - max(cur_lLTR_start, int(next_item[0])) + 1
+            if overlap_length >= 0.95 * cur_LTR_len and overlap_length >= 0.95 * int(next_item[2]):
+                is_redundant = True
+                break
+        if not is_redundant:
+            filtered_new_lines.append(cur_item)
+    return [" ".join(map(str, x)) for x in reversed(filtered_new_lines)]
+
+
+def get_all_potential_ltr_lines(confident_lines, reference, threads, temp_path, temp_dir, log, ctx=None, hsps=None):
+    """FiLTR step 1b (bin/FiLTR-main/src/Util.py:11227, get_ltr_from_line :11149): the internal sequence ref_seq[lLTR_end :
+    rLTR_start] of every line against itself (diag_min = 500: only what lies more than 500 diagonals off the main one can pass the
+    reference's `s_start - q_end > 500`); direct repeats inside it become further candidate lines.  reference: a FASTA path or
+    {name: sequence}.  A line with an empty internal sequence, or whose search is refused, gives no line at all (the reference has no
+    entry for it).  Writes the JSON side file temp_path as the reference does.  -> the lines, in line order"""
+    _scn_log(log, "info", "Start get all potential ltr lines")
+    ref_contigs = reference if isinstance(reference, dict) else read_fasta(reference)[1]
+    seqs, ids = _contig_ids(ref_contigs)
+    jobs, pairs = [], []
+    for cur_line in confident_lines:
+        parts = cur_line.split(" ")
+        chr_name, seq_id, lLTR_end, rLTR_start = parts[11], parts[10], int(parts[4]), int(parts[6])
+        s0, s1 = _py_slice(len(ref_contigs[chr_name]), lLTR_end, rLTR_start)
+        if s1 > s0:
+            jobs.append((lLTR_end, chr_name, seq_id, cur_line))
+            pairs.append((ids[chr_name], s0, s1, ids[chr_name], s0, s1))
+    res = (hsps or (ctx or get_ctx()).pair_hsps)(seqs, pairs, diag_min=500) if pairs else []
+    refused = sum(r is None for r in res)
+    if refused:
+        _scn_log(log, "debug", "get_all_potential_ltr_lines: " + str(refused) + " internal sequences beyond the limits of the search, their lines are dropped")
+    all_lines = {}
+    for candidate_index, ((lLTR_end, chr_name, seq_id, cur_line), r) in enumerate(zip(jobs, res)):
+        if r is not None:
+            all_lines[candidate_index] = ltr_lines_from_hsps(cur_line, lLTR_end, chr_name, seq_id, r)
+    temp_lines = {ci: lines for ci, lines in all_lines.items() if len(lines) > 1}
+    with open(temp_path, "w", encoding="utf-8") as f:
+        json.dump(temp_lines, f, ensure_ascii=False, indent=4)
+    new_confident_lines = [cur_line for lines in all_lines.values() for cur_line in lines]
+    _scn_log(log, "info", "Find all potential LTR, raw ltr num:" + str(len(confident_lines)) + ", current ltr num:" + str(len(new_confident_lines)))
+    return new_confident_lines
+
+
+def remove_dirty_LTR(confident_lines, log):
+    """bin/FiLTR-main/src/Util.py:7140 (host only): {chr-start-end: 1} of the lines whose internal sequence holds a whole later
+    candidate of the same chromosome (both its left start and its right end strictly inside)"""
+    _scn_log(log, "info", "Start remove dirty LTR")
+    dirty_dicts = {}
+    rows = []
+    for cur_line in confident_lines:
+        parts = cur_line.split(" ")
+        rows.append((parts[11], int(parts[3]), int(parts[4]), int(parts[6]), int(parts[7])))
+    for i, (cur_chr, cur_ls, cur_le, cur_rs, cur_re) in enumerate(rows):
+        for next_chr, next_ls, _next_le, _next_rs, next_re in rows[i + 1:]:
+            if cur_chr != next_chr:
+                break
+            if cur_le < next_ls < cur_rs and cur_le < next_re < cur_rs:
+                dirty_dicts[cur_chr + "-" + str(cur_ls) + "-" + str(cur_le)] = 1
+                break
+            if next_ls > cur_re:
+                break
+    return dirty_dicts
+
+
+def merge_intervals(intervals):
+    """bin/FiLTR-main/src/Util.py:4181: sorts `intervals` in place by start and joins those that touch or overlap"""
+    if not intervals:
+        return []
+    intervals.sort(key=lambda x: x[0])
+    merged = [intervals[0]]
+    for current in intervals:
+        last = merged[-1]
+        if current[0] <= last[1]:
+            merged[-1] = (last[0], max(last[1], current[1]))
+        else:
+            merged.append(current)
+    return merged
+
+
+def judge_flank_hsps(hsp_list, lLTR_len, rLTR_len, lLTR_start, lLTR_end, rLTR_start, rLTR_end, extend_len=50, error_region_len=10):
+    """judge_scn_line_by_flank_seq_v2 (bin/FiLTR-main/src/Util.py:10783-10836) after its search of the left terminal +- extend_len
+    against the right one: an alignment that begins within error_region_len of both left boundaries, or ends within it of both right
+    boundaries, is a boundary alignment; the candidate is an LTR when the merged boundary alignments cover 90 % of the left terminal.
+    -> (is_ltr, None or the adjusted (lLTR_start, lLTR_end, rLTR_start, rLTR_end))"""
+    q_start_offset = q_end_offset = s_start_offset = s_end_offset = 0
+    precise_boundary_alignments = []
+    for q_start, q_end, s_start, s_end in (h[:4] for h in hsp_list):
+        if ((extend_len - error_region_len) <= q_start <= (extend_len + error_region_len)
+                and q_end <= (extend_len + lLTR_len + error_region_len)
+                and (extend_len - error_region_len) <= s_start <= (extend_len + error_region_len)
+                and s_end <= (extend_len + rLTR_len + error_region_len)):
+            q_start_offset = q_start - extend_len
+            s_start_offset = s_start - extend_len
+            precise_boundary_alignments.append((q_start, q_end))
+        if ((extend_len - error_region_len) <= q_start
+                and (extend_len + lLTR_len - error_region_len) <= q_end <= (extend_len + lLTR_len + error_region_len)
+                and (extend_len - error_region_len) <= s_start
+                and (extend_len + rLTR_len - error_region_len) <= s_end <= (extend_len + rLTR_len + error_region_len)):
+            q_end_offset = q_end + 1 - (lLTR_len + extend_len)
+            s_end_offset = s_end + 1 - (rLTR_len + extend_len)
+            precise_boundary_alignments.append((q_start, q_end))
+    cover_len = sum(end - start for start, end in merge_intervals(precise_boundary_alignments))
+    if float(cover_len) / lLTR_len >= 0.9:
+        adjusted = (lLTR_start + q_start_offset, lLTR_end + q_end_offset, rLTR_start + s_start_offset, rLTR_end + s_end_offset)
+        moved = q_start_offset != 0 or q_end_offset != 0 or s_start_offset != 0 or s_end_offset != 0
+        return 1, adjusted if moved else None
+    return 0, None
+
+
+def filter_ltr_by_flank_seq_v2(scn_file, filter_scn, reference, threads, temp_dir, log, ctx=None, hsps=None):
+    """FiLTR step 2 (bin/FiLTR-main/src/Util.py:10839): the left terminal +- 50 bases of every line of scn_file against the right
+    one; judge_flank_hsps decides, and a line whose boundary moved is followed by its adjusted copy.  reference: a FASTA path or
+    {name: sequence}.  A line whose windows are empty, or whose search is refused, has no result and is not kept.  Writes
+    filter_scn; -> its lines"""
+    ref_contigs = reference if isinstance(reference, dict) else read_fasta(reference)[1]
+    _ltr_candidates, ltr_lines = read_scn(scn_file, log)
+    seqs, ids = _contig_ids(ref_contigs)
+    extend_len = 50
+    jobs, pairs = [], []
+    for candidate_index, line in ltr_lines.items():
+        parts = line.split(" ")
+        chr_name = parts[11]
+        n = len(ref_contigs[chr_name])
+        lLTR_start, lLTR_end, lLTR_len = int(parts[3]), int(parts[4]), int(parts[5])
+        rLTR_start, rLTR_end, rLTR_len = int(parts[6]), int(parts[7]), int(parts[8])
+        q0, q1 = _py_slice(n, lLTR_start - extend_len, lLTR_end + extend_len)
+        s0, s1 = _py_slice(n, rLTR_start - extend_len, rLTR_end + extend_len)
+        if q1 > q0 and s1 > s0:
+            jobs.append((candidate_index, lLTR_len, rLTR_len, lLTR_start, lLTR_end, rLTR_start, rLTR_end))
+            pairs.append((ids[chr_name], q0, q1, ids[chr_name], s0, s1))
+    res = (hsps or (ctx or get_ctx()).pair_hsps)(seqs, pairs) if pairs else []
+    refused = sum(r is None for r in res)
+    if refused:
+        _scn_log(log, "debug", "filter_ltr_by_flank_seq_v2: " + str(refused) + " pairs beyond the limits of the search, their lines are not kept")
+    confident_lines = []
+    fp_count = 0
+    for job, r in zip(jobs, res):
+        if r is None:
+            continue
+        is_ltr, adjust_boundary = judge_flank_hsps(r, *job[1:])
+        if is_ltr == 0:
+            fp_count += 1
+            continue
+        line = ltr_lines[job[0]]
+        confident_lines.append(line)
+        if adjust_boundary is not None:
+            parts = line.split(" ")
+            parts[3], parts[4] = str(adjust_boundary[0]), str(adjust_boundary[1])
+            parts[5] = str(adjust_boundary[1] - adjust_boundary[0] + 1)
+            parts[6], parts[7] = str(adjust_boundary[2]), str(adjust_boundary[3])
+            parts[8] = str(adjust_boundary[3] - adjust_boundary[2] + 1)
+            confident_lines.append(" ".join(parts))
+    store_scn(confident_lines, filter_scn)
+    _scn_log(log, "debug", "Remove False Positive LTR terminal: " + str(fp_count) + ", remaining LTR num: " + str(len(confident_lines)))
+    return confident_lines
+
+
+def left_ltr_terminals(scn_file, ref_contigs, log=None):
+    """bin/FiLTR-main/src/LTR_filter.py:594-615: {chr-start-end: left terminal sequence} of the lines of scn_file (a name seen before
+    gets -rep1, -rep2, ...; a terminal of N only is left out) and {name: candidate index}"""
+    ltr_candidates, _ltr_lines = read_scn(scn_file, log)
+    left_LTR_contigs, leftLtr2Candidates = {}, {}
+    for candidate_index, (chr_name, left_ltr_start, left_ltr_end, _rs, _re) in ltr_candidates.items():
+        if chr_name not in ref_contigs:
+            raise ValueError("Chromosome names in the SCN file do not match the input genome names: " + chr_name)
+        left_ltr_name = original_name = chr_name + "-" + str(left_ltr_start) + "-" + str(left_ltr_end)
+        left_ltr_seq = ref_contigs[chr_name][left_ltr_start - 1: left_ltr_end]
+        if all(char == "N" for char in left_ltr_seq):
+            continue
+        counter = 1
+        while left_ltr_name in left_LTR_contigs:
+            left_ltr_name = "%s-rep%d" % (original_name, counter)
+            counter += 1
+        left_LTR_contigs[left_ltr_name] = left_ltr_seq
+        leftLtr2Candidates[left_ltr_name] = candidate_index
+    return left_LTR_contigs, leftLtr2Candidates
+
+
+def ltr_scn_filter(scn_file, reference, out_dir, ctx=None, hsps=None, seconds=None, log=None):
+    """FiLTR from the `.scn` candidate table to the left terminal sequences (bin/FiLTR-main/src/LTR_filter.py:542-615): step 1
+    (get_recombination_ltr, get_all_potential_ltr_lines, remove_dirty_LTR -> out_dir/remove_recomb.scn) and step 2
+    (filter_ltr_by_flank_seq_v2 -> out_dir/filter_terminal_align.scn), three batched searches in all.  seconds: a dict that receives
+    the wall seconds of `recombination`, `potential_lines`, `flank_align`.
+    -> (path of the final scn, dirty_dicts, {chr-start-end: left terminal sequence}); the third value is what ltr_flank_filter takes"""
+    t = [time.perf_counter()]
+    lap = lambda key: (t.append(time.perf_counter()), seconds is not None and seconds.__setitem__(key, t[-1] - t[-2]))  # noqa: E731
+    os.makedirs(out_dir, exist_ok=True)
+    hsps = hsps or (ctx or get_ctx()).pair_hsps
+    _ref_names, ref_contigs = read_fasta(reference)
+    ltr_candidates, ltr_lines = read_scn(scn_file, log, remove_dup=True)
+    lap("read")
+    recombination_candidates = set(get_recombination_ltr(ltr_candidates, ref_contigs, 1, out_dir, log, hsps=hsps))
+    confident_lines = [ltr_lines[ci] for ci in ltr_candidates if ci not in recombination_candidates]
+    lap("recombination")
+    confident_lines = get_all_potential_ltr_lines(confident_lines, ref_contigs, 1, os.path.join(out_dir, "all_potential_ltr.json"), out_dir, log,
+                                                  hsps=hsps)
+    dirty_dicts = remove_dirty_LTR(confident_lines, log)
+    remove_recomb_scn = os.path.join(out_dir, "remove_recomb.scn")
+    store_scn(confident_lines, remove_recomb_scn)
+    lap("potential_lines")
+    filter_terminal_align_scn = os.path.join(out_dir, "filter_terminal_align.scn")
+    filter_ltr_by_flank_seq_v2(remove_recomb_scn, filter_terminal_align_scn, ref_contigs, 1, out_dir, log, hsps=hsps)
+    lap("flank_align")
+    left_LTR_contigs, _map = left_ltr_terminals(filter_terminal_align_scn, ref_contigs, log)
+    return filter_terminal_align_scn, dirty_dicts, left_LTR_contigs

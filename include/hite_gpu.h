@@ -450,6 +450,71 @@ int hite_pair_identity(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs, const 
                        const int32_t *b_id, const int64_t *b_start, const int64_t *b_end,
                        const uint8_t *strand, int32_t band, int32_t *cost_out, int32_t *match_out);
 
+/* ---- local alignments of pairs of intervals --- the one `blastn -query Q -subject S -outfmt 6` process FiLTR starts per candidate
+ * line in its steps 1 and 2 (is_recombination bin/FiLTR-main/src/Util.py:5923, get_ltr_from_line :11149,
+ * judge_scn_line_by_flank_seq_v2 :10759).  In-tree stage, NOT blastn and not pinned to it (no machine of the project has the tool):
+ * what is computed is the definition below, its CPU twin tests/pairhsp_twin.py + tests/pairhsp_twin.c, HIP == twin record for
+ * record.  Stated deviations: the plus strand only; no e-value; alignments live in bands of 192 diagonals; there is no X-drop, so
+ * an HSP can bridge what megablast would split.  The arithmetic is megablast's default scoring times two.
+ *
+ * For a pair (Q, S): m = |Q|, n = |S|; diag_min is one integer per call (INT32_MIN: none).  Bytes are read as A C G T in either
+ * case; anything else matches nothing and is in no word.
+ *  1. Limits.  m or n is 0 or above HITE_PAIRHSP_MAX_LEN, or an id or interval outside its sequence: status -1, no HSPs; the
+ *     other pairs of the call are unaffected.
+ *  2. Word hits.  A hit is (i, j), 0-based, with Q[i, i+12) = S[j, j+12), all twelve bases in ACGT, and j - i >= diag_min.  A word
+ *     that occurs more than HITE_PAIRHSP_MAX_OCC times in Q casts no hit.  The diagonal index is k = j - i + m - 1, and vote[b] is
+ *     the number of hits with k >> HITE_PAIRHSP_BIN_SHIFT = b.
+ *  3. Windows.  w(b) = vote[b] + vote[b+1].  Up to HITE_PAIRHSP_MAX_WINDOWS times the b with the largest w(b) >=
+ *     HITE_PAIRHSP_MIN_VOTES is taken, the lowest b on ties, skipping every b with |b - b'| < 2 for a b' already taken.  The band of
+ *     a taken b is the diagonals 64 b - HITE_PAIRHSP_BAND_BELOW <= k < 64 b + HITE_PAIRHSP_BAND_ABOVE, further cut by
+ *     j - i >= diag_min.
+ *  4. Banded local alignment, within a band and a rectangle of rows r0 .. r1 of Q and columns c0 .. c1 of S (1-based).  A cell value
+ *     is the tuple (score, matches, columns, q_start, s_start); V(i, j) is the best of
+ *        V(i-1, j-1) + (+2, 1, 1) when Q[i] = S[j] and both are in ACGT, else V(i-1, j-1) + (-4, 0, 1);
+ *        V(i-1, j)   + (-5, 0, 1);
+ *        V(i, j-1)   + (-5, 0, 1).
+ *     A neighbour outside the band or the rectangle is the empty value; a path that leaves the empty value at (i, j) has
+ *     q_start = i, s_start = j; a value whose score is <= 0 is the empty value.  "Best" is lexicographic: larger score, then larger
+ *     matches, then larger columns, then smaller q_start, then smaller s_start.  The result is the best cell of the rectangle, on
+ *     equal values the one with the smallest i, then the smallest j; q_end = i, s_end = j.  It is an HSP only at score >=
+ *     HITE_PAIRHSP_MIN_SCORE.  It is this recurrence, not a claim of optimality over alignment paths.
+ *  5. HSPs per band.  The first is the result on [1, m] x [1, n].  If there is one, one more is taken from the rectangle before it
+ *     (rows < q_start, columns < s_start) and one from the rectangle after it (rows > q_end, columns > s_end); a rectangle with
+ *     fewer than HITE_PAIRHSP_MIN_RECT rows or columns is skipped.  No further recursion: at most 3 per band,
+ *     HITE_PAIRHSP_MAX_HSPS per pair.
+ *  6. Order and duplicates.  The HSPs of a pair are ordered by (score descending, q_start, s_start, q_end, s_end); equal keys stay
+ *     in the order they were found (windows in the order taken; first, before, after).  An HSP is dropped when an earlier kept one
+ *     contains both of its intervals.
+ *  7. Record.  Seven int32: q_start, q_end, s_start, s_end (1-based, inclusive, relative to the intervals, as blast6 columns 7-10),
+ *     score, matches, columns.
+ *
+ * Caller-owned host buffers; seqs + seq_off[n_seq + 1] is the CSR batch; the pair arrays hold n_pair entries, intervals 0-based and
+ * half-open.  status[p] is the number of records of pair p or -1; its records are recs[7 * first[p]] .. recs[7 * first[p+1]]
+ * (first holds n_pair + 1 entries).  *n_out is the number of records of the call: HITE_ECAP when cap is smaller, with status, first
+ * and *n_out still filled and the first cap records written.  n_pair = 0 is a valid call and returns 0.  HITE_EINVAL for a negative
+ * count, a missing buffer or descending offsets.  The pairs go to the device in batches of bounded size
+ * ($HITE_PAIRHSP_BATCH_PAIRS, read by hite_ctx_create, sets a smaller batch: a test knob that never changes a result; default
+ * 8 192 pairs and 64 MiB of interval bytes); the work is on the context's stream and scratch. */
+#define HITE_PAIRHSP_MAX_LEN     32768
+#define HITE_PAIRHSP_WORD        12
+#define HITE_PAIRHSP_MAX_OCC     8
+#define HITE_PAIRHSP_BIN_SHIFT   6
+#define HITE_PAIRHSP_MIN_VOTES   8
+#define HITE_PAIRHSP_MAX_WINDOWS 4
+#define HITE_PAIRHSP_BAND_BELOW  32
+#define HITE_PAIRHSP_BAND_ABOVE  160
+#define HITE_PAIRHSP_MATCH       2
+#define HITE_PAIRHSP_MISMATCH    (-4)
+#define HITE_PAIRHSP_GAP         (-5)
+#define HITE_PAIRHSP_MIN_SCORE   56
+#define HITE_PAIRHSP_MIN_RECT    28
+#define HITE_PAIRHSP_MAX_HSPS    12
+int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs, const int64_t *seq_off, int64_t n_pair,
+                   const int32_t *a_id, const int64_t *a_start, const int64_t *a_end,
+                   const int32_t *b_id, const int64_t *b_start, const int64_t *b_end,
+                   int32_t diag_min, int64_t cap, int32_t *status /* n_pair: count or -1 */, int64_t *first /* n_pair + 1 */,
+                   int32_t *recs /* cap x 7 */, int64_t *n_out);
+
 /* ---- Helitron candidate scan --- multi_process_helitronscanner  Util.py:263 (third-party HelitronScanner.jar: scanHead, scanTail,
  * pairends, draw -pure_helitron per 50 kb part of longest_repeats_{i}.flanked.fa; judge_Helitron_transposons.py:27-34) -------------
  * In-tree stage, not pinned to the tool (no machine of the project runs it, and the tool's pairing rule and the tie-breaks of its
