@@ -72,11 +72,13 @@ __device__ __forceinline__ unsigned hs_from_code(unsigned x) {
     if (hs >= 0xfffffffeu) hs -= 2;
     return hs;
 }
-__device__ __forceinline__ int contig_of(const int64_t *__restrict__ coff, int nc, int64_t g) {
+template <class P>
+__device__ __forceinline__ int contig_of_in(P coff, int nc, int64_t g) {
     int lo = 0, hi = nc;
     while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (coff[mid] <= g) lo = mid; else hi = mid; }
     return lo;
 }
+__device__ __forceinline__ int contig_of(const int64_t *__restrict__ coff, int nc, int64_t g) { return contig_of_in(coff, nc, g); }
 // hs of the genome k-mer starting at global position g (contig [cb, ce))
 __device__ __forceinline__ unsigned genome_hs(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, int64_t g,
                                               int64_t ce) {
@@ -590,11 +592,13 @@ __global__ void hit_hist_kernel(int n_cand, const int64_t *__restrict__ q_first,
 // the candidate's chains from the sorted range where it lies (hs_chains) -- one global read of 8 bytes per hit and 24 bytes
 // written per chain, where the global radix sort of round 3 made five passes (5 x 16 B + histograms) and the cluster kernels
 // behind it four more over the hits.  Four classes by hits per candidate (C3: <= 2048: 75 % of the candidates, 51 % of the hits;
-// <= 4096: 19 % / 31 %; <= 8192: 5 % / 14 %; above: 0.6 % / 3.6 %, profiles of round 3): 2 x 16, 2 x 32, 2 x 64 KB of LDS (the
+// <= 4096: 19 % / 31 %; <= 8192: 5 % / 14 %; above: 0.6 % / 3.6 %, profiles of round 3, the first class then ending at 2048): 2 x 15.5, 2 x 32, 2 x 64 KB of LDS (the
 // last one holds a CU by itself), and global ping-pong buffers (the range against the sorter's spare array) for the rest.  Stable, like the global passes it replaces: the table is
 // the same, hit for hit.  (Packed 8-byte hits only; the 12-byte form keeps the global sort.)
+// The first class ends at 1984 hits, not 2048: with 2 x 1984 x 8 B beside the 8 KB of counters and the 0.9 KB of the rest a
+// workgroup takes 39.8 of the 160 KiB, and FOUR of them share a compute unit (2048 hits: 40.1 KiB with no table at all, three).
 // ---------------------------------------------------------------------------------------------
-#define HS_SMALL 2048
+#define HS_SMALL 1984
 #define HS_MID 4096
 #define HS_MEDIUM 8192
 #define HS_NCLS 4
@@ -623,27 +627,131 @@ __global__ void hit_sort_classify_kernel(int n_cand, const int64_t *__restrict__
 }
 // one stable pass on digit (key >> shift) & 15 from src to dst (n elements, all NT threads of the block); CT = counter type
 // (uint16_t while n < 65536: half the LDS)
-template <int NT, class CT, class PS, class PD>
-__device__ __forceinline__ void hs_pass(PS src, PD dst, int n, int shift, CT *s_cnt /* 16 x NT */, int *s_scan) {
-    const int t = threadIdx.x;
-    // a thread's chunk: contiguous (stability), of ODD length (consecutive lanes then start 2 E dwords apart: all banks, where an
-    // even length would put the 64 lanes of an 8-byte read on a handful of them)
-    const int E = ((n + NT - 1) / NT) | 1, b = t * E < n ? t * E : n, e = b + E < n ? b + E : n;
-    for (int k = 0; k < 16; k++) s_cnt[k * NT + t] = (CT)0;
-    for (int i = b; i < e; i++) s_cnt[(int)((src[i] >> shift) & 15ull) * NT + t]++;
+//
+// No key waits for an LDS round trip of the key before it: a thread reads a batch of its chunk back to back, and the digit of a
+// key and its rank among the EARLIER keys of the batch with the same digit are register arithmetic -- the 16 counts of a batch
+// are 8-bit fields of two 64-bit words (HsCnt; a batch has at most HS_BATCH_MAX keys.  The top passes put a thread's whole
+// chunk into ONE digit, all hits of a region sharing the high diagonal bits, so a field must hold the batch, not batch / 16).
+// The scatter reads one offset per key, dst[s_cnt[digit][t] + rank], all of a batch together.  Ranks follow chunk order and the
+// chunks are contiguous per thread: stable, as the loop of a read-modify-write per key it replaces.
+#define HS_BATCH_MAX 255
+#define HS_BATCH_GLOBAL 16      // keys per batch of the global class (the LDS classes: the whole chunk, kept in registers)
+struct HsCnt { unsigned long long lo = 0ull, hi = 0ull; };
+// counts the digit; -> digit | rank << 4
+__device__ __forceinline__ unsigned hs_rank(HsCnt &c, unsigned d) {
+    const int sh = (int)(d & 7u) * 8;
+    const bool up = (d & 8u) != 0u;
+    const unsigned r = (unsigned)((up ? c.hi : c.lo) >> sh) & 0xffu;
+    const unsigned long long inc = 1ull << sh;
+    c.lo += up ? 0ull : inc;
+    c.hi += up ? inc : 0ull;
+    return d | (r << 4);
+}
+__device__ __forceinline__ unsigned hs_field(const HsCnt &c, int k) { return (unsigned)((k < 8 ? c.lo : c.hi) >> ((k & 7) * 8)) & 0xffu; }
+// inclusive scan over the 64 lanes of a wavefront (all of them active): Hillis-Steele inside the rows of 16 lanes on DPP row
+// shifts (a lane whose source lies outside its row adds 0), then the totals of the rows before the lane's own -- no LDS round trip
+__device__ __forceinline__ int hs_wave_incl_scan(int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);      // row_shr:1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);      // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);      // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);      // row_shr:8
+    const int r0 = __builtin_amdgcn_readlane(x, 15), r1 = __builtin_amdgcn_readlane(x, 31), r2 = __builtin_amdgcn_readlane(x, 47);
+    const int row = (int)(threadIdx.x & 63u) >> 4;
+    return x + (row > 0 ? r0 : 0) + (row > 1 ? r1 : 0) + (row > 2 ? r2 : 0);
+}
+// exclusive scan of the 16 NT counters in (digit, thread) order: a thread takes 16 consecutive ones (between two barriers, one
+// inside: s_scan[] is written a barrier after its last reader, the one that ends the scan before)
+template <int NT, class CT>
+__device__ __forceinline__ void hs_scan_counts(CT *s_cnt, int *s_scan) {
+    const int t = threadIdx.x, w = t >> 6;
     __syncthreads();
-    // exclusive scan of the 16 NT counters in (digit, thread) order: a thread takes 16 consecutive ones
     unsigned v[16], sum = 0u;
 #pragma unroll
     for (int k = 0; k < 16; k++) { v[k] = s_cnt[t * 16 + k]; sum += v[k]; }
-    int tot;
-    unsigned run = (unsigned)block_excl_scan((int)sum, s_scan, &tot);
+    const int incl = hs_wave_incl_scan((int)sum);
+    if ((t & 63) == 63) s_scan[w] = incl;
+    __syncthreads();
+    unsigned run = (unsigned)incl - sum;
+#pragma unroll
+    for (int q = 0; q < NT / 64; q++) { const int x = s_scan[q]; run += q < w ? (unsigned)x : 0u; }
 #pragma unroll
     for (int k = 0; k < 16; k++) { const unsigned x = v[k]; s_cnt[t * 16 + k] = (CT)run; run += x; }
     __syncthreads();
-    for (int i = b; i < e; i++) {
-        const unsigned long long x = src[i];
-        dst[s_cnt[(int)((x >> shift) & 15ull) * NT + t]++] = x;
+}
+// the LDS classes: a chunk has at most EMAX keys (a compile-time bound of the class), which stay in registers from the count to
+// the scatter.  Keys past the chunk's end (k >= m) are neither read nor counted nor stored (every step is predicated on k < m).
+template <int NT, int EMAX, class CT, class PS, class PD>
+__device__ __forceinline__ void hs_pass(PS src, PD dst, int n, int shift, CT *s_cnt /* 16 x NT */, int *s_scan) {
+    static_assert(EMAX <= HS_BATCH_MAX, "a count field holds a whole chunk");
+    const int t = threadIdx.x;
+    // a thread's chunk: contiguous (stability), of ODD length (consecutive lanes then start 2 E dwords apart: all banks, where an
+    // even length would put the 64 lanes of an 8-byte read on a handful of them)
+    const int E = ((n + NT - 1) / NT) | 1, b = t * E < n ? t * E : n, m = (b + E < n ? b + E : n) - b;
+    unsigned long long key[EMAX];
+    unsigned rk[(EMAX + 3) / 4];         // the ranks, a byte each (the digit is taken from the key again)
+#pragma unroll
+    for (int k = 0; k < (EMAX + 3) / 4; k++) rk[k] = 0u;
+#pragma unroll
+    for (int k = 0; k < EMAX; k++)
+        if (k < m) key[k] = src[b + k];
+    HsCnt c;
+#pragma unroll
+    for (int k = 0; k < EMAX; k++)
+        if (k < m) rk[k >> 2] |= (hs_rank(c, (unsigned)(key[k] >> shift) & 15u) >> 4) << ((k & 3) * 8);
+#pragma unroll
+    for (int k = 0; k < 16; k++) s_cnt[k * NT + t] = (CT)hs_field(c, k);
+    hs_scan_counts<NT, CT>(s_cnt, s_scan);
+    unsigned off[EMAX];
+#pragma unroll
+    for (int k = 0; k < EMAX; k++)
+        if (k < m) off[k] = (unsigned)s_cnt[(int)((unsigned)(key[k] >> shift) & 15u) * NT + t] + ((rk[k >> 2] >> ((k & 3) * 8)) & 0xffu);
+#pragma unroll
+    for (int k = 0; k < EMAX; k++)
+        if (k < m) dst[off[k]] = key[k];
+    __syncthreads();
+}
+// the global class: chunks of any length, taken in batches of EB keys that are read again for the scatter; the counts of the
+// batches add up in registers, and the scatter advances the thread's own 16 offsets by the batch's counts (no other thread
+// reads them)
+template <int NT, int EB, class PS, class PD>
+__device__ __forceinline__ void hs_pass_batched(PS src, PD dst, int n, int shift, unsigned *s_cnt /* 16 x NT */, int *s_scan) {
+    static_assert(EB <= HS_BATCH_MAX, "a count field holds a whole batch");
+    const int t = threadIdx.x;
+    const int E = ((n + NT - 1) / NT) | 1, b = t * E < n ? t * E : n, e = b + E < n ? b + E : n;
+    unsigned cnt[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) cnt[k] = 0u;
+    for (int i = b; i < e; i += EB) {
+        const int m = e - i < EB ? e - i : EB;
+        unsigned long long key[EB];
+#pragma unroll
+        for (int k = 0; k < EB; k++) key[k] = src[i + k < n ? i + k : n - 1];
+        HsCnt c;
+#pragma unroll
+        for (int k = 0; k < EB; k++)
+            if (k < m) hs_rank(c, (unsigned)(key[k] >> shift) & 15u);
+#pragma unroll
+        for (int k = 0; k < 16; k++) cnt[k] += hs_field(c, k);
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) s_cnt[k * NT + t] = cnt[k];
+    hs_scan_counts<NT, unsigned>(s_cnt, s_scan);
+    for (int i = b; i < e; i += EB) {
+        const int m = e - i < EB ? e - i : EB;
+        unsigned long long key[EB];
+        unsigned dr[EB], off[EB];
+#pragma unroll
+        for (int k = 0; k < EB; k++) key[k] = src[i + k < n ? i + k : n - 1];
+        HsCnt c;
+#pragma unroll
+        for (int k = 0; k < EB; k++) { dr[k] = 0u; if (k < m) dr[k] = hs_rank(c, (unsigned)(key[k] >> shift) & 15u); }
+#pragma unroll
+        for (int k = 0; k < EB; k++) off[k] = s_cnt[(int)(dr[k] & 15u) * NT + t] + (dr[k] >> 4);
+#pragma unroll
+        for (int k = 0; k < EB; k++)
+            if (k < m) dst[off[k]] = key[k];
+#pragma unroll
+        for (int k = 0; k < 16; k++) s_cnt[k * NT + t] += hs_field(c, k);
     }
     __syncthreads();
 }
@@ -680,6 +788,11 @@ __device__ __forceinline__ int chain_class(int na, unsigned long long lo, unsign
 // candidate.  The scratch is the buffer that does not hold the sorted range: 20 (n / 3) + 40 ceil(n / 64)
 // bytes <= 8 n from n = 57 on, and <= 8 CAP for every n <= CAP of the LDS classes.
 typedef __attribute__((address_space(3))) unsigned *hs_lptr32;
+// The contig test of a hit that continues a run searches the contig offsets: from LDS when the genome's nc + 1 offsets fit
+// HS_NCTG entries (staged once per workgroup, before its first candidate; 768 B keep the workgroups per CU of every class:
+// 4 x 39.8, 2 x 72.8, 1 x 144.8 and, in the global class, 4 x 32.8 KiB of 160), from global memory for genomes with more contigs.
+#define HS_NCTG 96
+typedef const __attribute__((address_space(3))) int64_t *hs_lcoff;
 template <class S64, class S32>
 __device__ __forceinline__ void hs_chain_stage(int na, unsigned long long lo, unsigned long long hi, unsigned rel, long long Lq, int maxch,
                                                S64 st_lo, S64 st_hi, S32 st_cr, int *s_n) {
@@ -690,7 +803,7 @@ __device__ __forceinline__ void hs_chain_stage(int na, unsigned long long lo, un
 }
 template <int NT, class P64, class S64, class S32>
 __device__ __forceinline__ void hs_chains(P64 r, int n, S64 scr, unsigned c, const HitFmt &F, long long Lq, const int64_t *__restrict__ coff,
-                                          int nc, ChainRec *__restrict__ tab, unsigned long long cap, unsigned long long *__restrict__ counters,
+                                          hs_lcoff s_coff /* the nc + 1 offsets in LDS, if coff_lds */, bool coff_lds, int nc, ChainRec *__restrict__ tab, unsigned long long cap, unsigned long long *__restrict__ counters,
                                           int *s_n /* [0..1] zero on entry and on return; [2] += the candidate's clusters */,
                                           unsigned long long *s_base /* [2] */) {
     const int lane = threadIdx.x & 63;
@@ -714,7 +827,10 @@ __device__ __forceinline__ void hs_chains(P64 r, int n, S64 scr, unsigned c, con
                 const unsigned long long a = r[i - 1];
                 const long long da = hit_dbias(F, a), ga = da - DBIAS + hit_qo(F, a, 0);
                 head = hit_strand_key(F, a) != hit_strand_key(F, b) || db - da > C_TD;
-                if (!head) { const int ca = contig_of(coff, nc, ga); head = gb < coff[ca] || gb >= coff[ca + 1]; }
+                if (!head) {
+                    if (coff_lds) { const int ca = contig_of_in(s_coff, nc, ga); head = gb < s_coff[ca] || gb >= s_coff[ca + 1]; }
+                    else { const int ca = contig_of(coff, nc, ga); head = gb < coff[ca] || gb >= coff[ca + 1]; }
+                }
             }
         }
         const unsigned long long headmask = __ballot(have && head);
@@ -777,8 +893,11 @@ __device__ __forceinline__ void hs_chains(P64 r, int n, S64 scr, unsigned c, con
     if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
     __syncthreads();
 }
+// amdgpu_waves_per_eu(4) holds every instantiation to 128 VGPRs: LDS, not registers, limits the workgroups per CU here, so without it
+// the compiler spends registers freely (up to 156 in the classes of 17 keys per thread, measured), which the first and the global
+// class, at four wavefronts per SIMD, cannot afford; under it 31 to 79 SGPRs are spilled into VGPR lanes, nothing into scratch.
 template <int CAP /* elements per LDS buffer; 0: global ping-pong */, int NT /* threads */>
-__global__ void __launch_bounds__(NT) hit_segsort_kernel(const unsigned *__restrict__ count, const int32_t *__restrict__ list,
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) hit_segsort_kernel(const unsigned *__restrict__ count, const int32_t *__restrict__ list,
                                                          const int64_t *__restrict__ q_first, const int64_t *__restrict__ hit_off,
                                                          unsigned long long *__restrict__ hkey, unsigned long long *__restrict__ spare,
                                                          int shift0, int bits, const int64_t *__restrict__ cand_off,
@@ -790,37 +909,57 @@ __global__ void __launch_bounds__(NT) hit_segsort_kernel(const unsigned *__restr
     __shared__ int s_scan[16];
     __shared__ int s_n[3];
     __shared__ unsigned long long s_base[2];
+    __shared__ int64_t s_coff[HS_NCTG];
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_dyn[];
+    // The first class runs FOUR workgroups per CU with no slack: LDS is handed out in granules of 1280 B, the 9056 B above plus
+    // 2 x 1984 x 8 B are 40800 B = 32 granules, and 4 x 32 granules are the CU's 160 KiB.  One more __shared__ word, a larger
+    // HS_NCTG or a longer first class drops it to three (16 B allowed for the alignment of s_base and s_coff).
+    static_assert(CAP != HS_SMALL || sizeof(s_cnt) + sizeof(s_scan) + sizeof(s_n) + sizeof(s_base) + sizeof(s_coff) + 16 + 2 * (size_t)CAP * 8 <= 160 * 1024 / 4,
+                  "the first class no longer fits four workgroups per CU");
+    constexpr int EMAX = CAP > 0 ? (((CAP + NT - 1) / NT) | 1) : 1;      // keys per thread of the largest range of an LDS class
+    const bool coff_lds = nc + 1 <= HS_NCTG;
+    const hs_lcoff l_coff = (hs_lcoff)s_coff;
+    if (coff_lds) for (int i = threadIdx.x; i <= nc; i += NT) s_coff[i] = coff[i];
     const unsigned cnt = *count;
     const int passes = (bits + 3) / 4;
     HitFmt F;                              // (packed hits only)
     F.qbits = shift0; F.dbits = bits - 1; F.hval = nullptr;
     if (threadIdx.x < 3) s_n[threadIdx.x] = 0;
     __syncthreads();
-    for (unsigned it = blockIdx.x; it < cnt; it += gridDim.x) {
-        const int c = list[it];
-        const int64_t o = hit_off[q_first[c]];
-        const int n = (int)(hit_off[q_first[c + 1]] - o);
+    // a candidate's range lies three dependent reads away (list -> q_first -> hit_off): the first two are taken one and two
+    // candidates ahead, beside the work on the current one
+    const unsigned gs = gridDim.x;
+    unsigned it = blockIdx.x;
+    int c = it < cnt ? list[it] : 0, c_next = it + gs < cnt ? list[it + gs] : 0;
+    int64_t qa = 0, qb = 0;
+    if (it < cnt) { qa = q_first[c]; qb = q_first[c + 1]; }
+    for (; it < cnt; it += gs) {
+        const int64_t o = hit_off[qa];
+        const int n = (int)(hit_off[qb] - o);
         const long long Lq = cand_off[c + 1] - cand_off[c];
+        const int c_next2 = it + 2 * gs < cnt ? list[it + 2 * gs] : 0;
+        int64_t qa_next = 0, qb_next = 0;
+        if (it + gs < cnt) { qa_next = q_first[c_next]; qb_next = q_first[c_next + 1]; }
         unsigned long long *g = hkey + o;
         // the sorted range is read by the epilogue alone and is not written back
-        if (CAP > 0) {
+        if constexpr (CAP > 0) {
             hs_lptr a = (hs_lptr)s_dyn, bq = (hs_lptr)s_dyn + CAP;
-            for (int i = threadIdx.x; i < n; i += NT) a[i] = g[i];
-            __syncthreads();
-            for (int ps = 0; ps < passes; ps++) {
-                if (ps & 1) hs_pass<NT, CT>(bq, a, n, shift0 + 4 * ps, s_cnt, s_scan); else hs_pass<NT, CT>(a, bq, n, shift0 + 4 * ps, s_cnt, s_scan);
+            // the first pass takes the range from global memory, a thread its own chunk, all its reads in flight together
+            hs_pass<NT, EMAX, CT>(g, a, n, shift0, s_cnt, s_scan);
+            for (int ps = 1; ps < passes; ps++) {
+                if (ps & 1) hs_pass<NT, EMAX, CT>(a, bq, n, shift0 + 4 * ps, s_cnt, s_scan); else hs_pass<NT, EMAX, CT>(bq, a, n, shift0 + 4 * ps, s_cnt, s_scan);
             }
-            if (passes & 1) hs_chains<NT, hs_lptr, hs_lptr, hs_lptr32>(bq, n, a, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
-            else hs_chains<NT, hs_lptr, hs_lptr, hs_lptr32>(a, n, bq, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
+            if (passes & 1) hs_chains<NT, hs_lptr, hs_lptr, hs_lptr32>(a, n, bq, (unsigned)c, F, Lq, coff, l_coff, coff_lds, nc, tab, cap, counters, s_n, s_base);
+            else hs_chains<NT, hs_lptr, hs_lptr, hs_lptr32>(bq, n, a, (unsigned)c, F, Lq, coff, l_coff, coff_lds, nc, tab, cap, counters, s_n, s_base);
         } else {
             unsigned long long *h = spare + o;
             for (int ps = 0; ps < passes; ps++) {
-                if (ps & 1) hs_pass<NT, CT>(h, g, n, shift0 + 4 * ps, s_cnt, s_scan); else hs_pass<NT, CT>(g, h, n, shift0 + 4 * ps, s_cnt, s_scan);
+                if (ps & 1) hs_pass_batched<NT, HS_BATCH_GLOBAL>(h, g, n, shift0 + 4 * ps, s_cnt, s_scan); else hs_pass_batched<NT, HS_BATCH_GLOBAL>(g, h, n, shift0 + 4 * ps, s_cnt, s_scan);
             }
-            if (passes & 1) hs_chains<NT, unsigned long long *, unsigned long long *, unsigned *>(h, n, g, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
-            else hs_chains<NT, unsigned long long *, unsigned long long *, unsigned *>(g, n, h, (unsigned)c, F, Lq, coff, nc, tab, cap, counters, s_n, s_base);
+            if (passes & 1) hs_chains<NT, unsigned long long *, unsigned long long *, unsigned *>(h, n, g, (unsigned)c, F, Lq, coff, l_coff, coff_lds, nc, tab, cap, counters, s_n, s_base);
+            else hs_chains<NT, unsigned long long *, unsigned long long *, unsigned *>(g, n, h, (unsigned)c, F, Lq, coff, l_coff, coff_lds, nc, tab, cap, counters, s_n, s_base);
         }
+        c = c_next; c_next = c_next2; qa = qa_next; qb = qb_next;
     }
     // the clusters of all the candidates this workgroup took: ONE atomic per workgroup (the last hs_chains ended with a barrier)
     if (threadIdx.x == 0 && s_n[2]) atomicAdd(n_clusters, (unsigned long long)s_n[2]);
