@@ -365,6 +365,53 @@ class Context:
                                              _p(_arr([t[3] for t in flat], np.uint8)), _p(out)), "hite_clip_probe")
         return [[int(x) for x in out[cf[i]:cf[i + 1]]] for i in range(n)]
 
+    def fine_rows(self, cands, copies, flank=50, rows_pass=0):
+        """the rows one pass of the fine stage hands to the alignment (hite_fine_rows: the stage's own row selection and window
+        gather): cands / copies as for flank_region_align (6-tuples carry their clip words, shorter ones are probed); rows_pass
+        0 = pass A, 1 = pass B as if every first500 + last500 form had passed
+        -> (per candidate list of (copy_index_within_candidate, window_bytes, trunc), totals = [rows, window bytes, longest row, 0])"""
+        n = len(cands)
+        cb = [c.encode() if isinstance(c, str) else bytes(c) for c in cands]
+        coff = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(c) for c in cb], out=coff[1:])
+        cbuf = np.frombuffer(b"".join(cb) + b"\0" * 16, dtype=np.uint8)
+        cf = np.zeros(n + 1, dtype=np.int32)
+        np.cumsum([len(c) for c in copies], out=cf[1:])
+        flat = [t for c in copies for t in c]
+        has = [len(t) > 5 for t in flat]
+        if any(has) and not all(has):
+            raise ValueError("fine_rows: copy tuples with and without a clip field in one table")
+        clip = _arr([t[5] for t in flat], np.uint32) if flat and all(has) else None
+        args = (_p(_arr([t[0] for t in flat], np.int32)), _p(_arr([t[1] for t in flat], np.int64)), _p(_arr([t[2] for t in flat], np.int64)),
+                _p(_arr([t[3] for t in flat], np.uint8)))
+        nrows = np.zeros(n + 1, dtype=np.int32)
+        totals = np.zeros(4, dtype=np.int64)
+        row_cap = win_cap = 0
+        for _attempt in range(2):
+            row_copy = np.zeros(row_cap + 1, dtype=np.int32)
+            row_len = np.zeros(row_cap + 1, dtype=np.int32)
+            row_trunc = np.zeros(row_cap + 1, dtype=np.uint8)
+            win_off = np.zeros(row_cap + 2, dtype=np.int64)
+            win = np.zeros(win_cap + 16, dtype=np.uint8)
+            rc = self.lib.hite_fine_rows(self.h, n, _p(cbuf), _p(coff), _p(cf), C.c_int64(len(flat)), *args,
+                                         _p(clip) if clip is not None else None, int(flank), int(rows_pass), _p(nrows), C.c_int64(row_cap),
+                                         _p(row_copy), _p(row_len), _p(row_trunc), _p(win_off), C.c_int64(win_cap), _p(win), _p(totals))
+            if rc == -4 and (totals[0] > row_cap or totals[1] > win_cap):      # HITE_ECAP: totals say what is needed
+                row_cap, win_cap = int(totals[0]), int(totals[1])
+                continue
+            break
+        self._check(rc, "hite_fine_rows")
+        out, r = [], 0
+        for i in range(n):
+            rows = []
+            for _k in range(int(nrows[i])):
+                o = int(win_off[r])
+                rows.append((int(row_copy[r]) - int(cf[i]), win[o:o + int(row_len[r])].tobytes(), bool(row_trunc[r])))
+                r += 1
+            out.append(rows)
+        assert r == int(totals[0]) and int(win_off[r]) == int(totals[1])
+        return out, [int(x) for x in totals]
+
     # device-resident variant: every argument is a raw device pointer (e.g. torch tensor .data_ptr())
     def flank_region_align_dev(self, te_type, plant, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_start1,
                                d_end1, d_minus, flank, d_calls, d_cons, cons_cap, stream=0, d_clip=0):

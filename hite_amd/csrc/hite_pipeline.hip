@@ -416,15 +416,25 @@ static int read_scalars(hite_ctx *ctx, PipeState *S, hipStream_t st, int count) 
 
 #define ACHK(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
-static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, const uint8_t *d_cand,
-                    const int64_t *d_cand_off, const int32_t *d_copy_first, const int32_t *d_contig,
-                    const int64_t *d_s1, const int64_t *d_e1, const uint8_t *d_minus, const uint32_t *d_clip, int flank, const int64_t *d_len,
-                    const int32_t *d_mode, PassOut *out, int64_t *stats /* rows, win_bytes, msa_bytes, align_bytes */,
-                    int64_t *extra /* steps */, int64_t *cols_acc /* cleaned columns, both passes */, bool pass_b, hipStream_t st) {
+// The front of a pass: the rows of every candidate (select_rows_kernel), their place in the batch (scan), what each row is
+// (row_meta_kernel), where its window lies (scan), and the windows themselves (row_gather_kernel) -- with the sizes of the
+// alignment's ops the stage needs next.  Shared by run_pass and by hite_fine_rows (the rows of a pass by themselves), so that the
+// diagnostic entry runs the launches of the stage and not a copy of them.  calls_out (may be NULL): the keep-arena records of the
+// pass, zeroed where run_pass always zeroed them.  total_rows == 0: nothing behind the first scan is allocated or launched.
+struct PassFront {
+    int32_t *nrows = nullptr, *sel = nullptr, *row_first32 = nullptr, *row_copy = nullptr, *row_len = nullptr, *row_pad = nullptr, *row_cp0 = nullptr;
+    int64_t *row_first = nullptr, *win_off = nullptr, *ops_base = nullptr;
+    uint8_t *row_trunc = nullptr, *win = nullptr;
+    int64_t total_rows = 0, win_bytes = 0, ops_elems = 0, align_bytes = 0, steps = 0;
+    int max_len = 0;
+};
+static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_first, const int32_t *d_contig, const int64_t *d_s1,
+                      const int64_t *d_e1, const uint8_t *d_minus, const uint32_t *d_clip, int flank, const int64_t *d_len,
+                      const int32_t *d_mode, hite_call **calls_out, PassFront &F, hipStream_t st) {
     Arena &T = S->tmp, &K = S->keep;
-    int32_t *nrows, *sel, *row_first32, *row_copy, *row_len, *row_pad, *cols, *status, *eff, *new_cols;
-    int64_t *row_first, *win_off, *ops_cnt, *ops_base, *msa_bytes, *msa_off, *col_off2;
-    uint8_t *row_trunc, *win, *clean;
+    int32_t *nrows, *sel, *row_first32, *row_copy, *row_len, *row_pad;
+    int64_t *row_first, *win_off, *ops_cnt, *ops_base;
+    uint8_t *row_trunc, *win;
     void *p;
     ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); nrows = (int32_t *)p;
     ACHK(arena_alloc(ctx, T, (size_t)n * MAXROWS * 4, &p)); sel = (int32_t *)p;
@@ -437,10 +447,12 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, row_first + n, 8, hipMemcpyDeviceToDevice, st));
     ACHK(read_scalars(ctx, S, st, 1));
     const int64_t total_rows = S->h_pin[0];
-    stats[0] += total_rows;
-    ACHK(arena_alloc(ctx, K, sizeof(hite_call) * (size_t)n, &p)); out->calls = (hite_call *)p;
-    HITE_CHECK(ctx, hipMemsetAsync(out->calls, 0, sizeof(hite_call) * (size_t)n, st));
-    if (total_rows == 0) { ACHK(arena_alloc(ctx, K, 256, &p)); out->cons = (uint8_t *)p; return HITE_OK; }
+    F.nrows = nrows; F.sel = sel; F.row_first = row_first; F.total_rows = total_rows;
+    if (calls_out) {
+        ACHK(arena_alloc(ctx, K, sizeof(hite_call) * (size_t)n, &p)); *calls_out = (hite_call *)p;
+        HITE_CHECK(ctx, hipMemsetAsync(*calls_out, 0, sizeof(hite_call) * (size_t)n, st));
+    }
+    if (total_rows == 0) return HITE_OK;
     if (total_rows > 0x7fffffff) return HITE_EINVAL;
 
     ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 4, &p)); row_first32 = (int32_t *)p;
@@ -463,11 +475,11 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, win_off + total_rows, 8, hipMemcpyDeviceToDevice, st));
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 1, ops_base + n, 8, hipMemcpyDeviceToDevice, st));
     ACHK(read_scalars(ctx, S, st, 6));
-    const int64_t win_bytes = S->h_pin[0], ops_elems = S->h_pin[1];
-    const int max_len = (int)(((int32_t *)(S->h_pin + 2))[0]);
-    stats[1] += win_bytes;
-    stats[3] += S->h_pin[4];  // alignment algorithmic bytes
-    extra[0] += S->h_pin[5];  // anti-diagonal steps
+    const int64_t win_bytes = S->h_pin[0];
+    F.win_bytes = win_bytes; F.ops_elems = S->h_pin[1];
+    F.max_len = (int)(((int32_t *)(S->h_pin + 2))[0]);
+    F.align_bytes = S->h_pin[4];  // alignment algorithmic bytes
+    F.steps = S->h_pin[5];        // anti-diagonal steps
 
     ACHK(arena_alloc(ctx, T, (size_t)win_bytes + 64, &p)); win = (uint8_t *)p;
     tk = hite_prof_begin(ctx, "row_gather_kernel", st);
@@ -476,6 +488,35 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
                        flank, win_off, win, d_clip, row_cp0);
     hite_prof_end(ctx, tk, st);
     HITE_CHECK(ctx, hipGetLastError());
+    F.row_first32 = row_first32; F.row_copy = row_copy; F.row_len = row_len; F.row_pad = row_pad; F.row_cp0 = row_cp0;
+    F.win_off = win_off; F.ops_base = ops_base; F.row_trunc = row_trunc; F.win = win;
+    return HITE_OK;
+}
+
+static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, const uint8_t *d_cand,
+                    const int64_t *d_cand_off, const int32_t *d_copy_first, const int32_t *d_contig,
+                    const int64_t *d_s1, const int64_t *d_e1, const uint8_t *d_minus, const uint32_t *d_clip, int flank, const int64_t *d_len,
+                    const int32_t *d_mode, PassOut *out, int64_t *stats /* rows, win_bytes, msa_bytes, align_bytes */,
+                    int64_t *extra /* steps */, int64_t *cols_acc /* cleaned columns, both passes */, bool pass_b, hipStream_t st) {
+    Arena &T = S->tmp, &K = S->keep;
+    int32_t *cols, *status, *eff, *new_cols;
+    int64_t *msa_bytes, *msa_off, *col_off2;
+    uint8_t *clean;
+    void *p;
+    PassFront F;
+    ACHK(pass_front(ctx, S, n, d_copy_first, d_contig, d_s1, d_e1, d_minus, d_clip, flank, d_len, d_mode, &out->calls, F, st));
+    const int64_t total_rows = F.total_rows;
+    stats[0] += total_rows;
+    if (total_rows == 0) { ACHK(arena_alloc(ctx, K, 256, &p)); out->cons = (uint8_t *)p; return HITE_OK; }
+    stats[1] += F.win_bytes;
+    stats[3] += F.align_bytes;
+    extra[0] += F.steps;
+    const int64_t ops_elems = F.ops_elems;
+    const int max_len = F.max_len;
+    int32_t *const row_first32 = F.row_first32, *const row_len = F.row_len;
+    int64_t *const win_off = F.win_off, *const ops_base = F.ops_base;
+    uint8_t *const win = F.win;
+    int tk;
 
     ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); cols = (int32_t *)p;
     ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); status = (int32_t *)p;
@@ -628,6 +669,35 @@ __global__ void __launch_bounds__(256) clip_probe_kernel(const uint32_t *__restr
     clip_out[2 * cp + ((right != 0) != mn ? 1 : 0)] = (uint16_t)clip;
 }
 
+// What both passes go by: the window length of every copy (len, n_copies + 1 entries of the keep arena), the clip words where the
+// table carries none (*d_clip_io == NULL: probed into the keep arena), and the modes of pass A.  Shared by the stage and by
+// hite_fine_rows.
+static int stage_tables(hite_ctx *ctx, PipeState *S, int32_t n_cand, const uint8_t *d_cand, const int64_t *d_cand_off,
+                        const int32_t *d_copy_first, int64_t n_copies, const int32_t *d_contig, const int64_t *d_start1,
+                        const int64_t *d_end1, const uint8_t *d_minus, const uint32_t **d_clip_io, int32_t flank, int64_t *len,
+                        int32_t *mode_a, hipStream_t st) {
+    void *p;
+    if (n_copies > 0)
+        hipLaunchKernelGGL(flank_sizes_kernel, dim3((unsigned)((n_copies + 255) / 256)), dim3(256), 0, st, ctx->d_contig_off,
+                           ctx->n_contigs, n_copies, d_contig, d_start1, d_end1, flank, len, (int64_t *)nullptr);
+    if (!*d_clip_io && n_copies > 0) {
+        // a table without clip words (the reference's own tuples; never inferred from where the caller's arrays live): the probe
+        // supplies them, so that the rows are padded as the copy finder's own records are -- bare aligned windows, aligned globally
+        // against a longer centre, cost a fifth of the calls (profiles/r05_scale_tests.txt)
+        uint16_t *est;
+        ACHK(arena_alloc(ctx, S->keep, (size_t)n_copies * 4 + 16, &p)); est = (uint16_t *)p;
+        const int tkp = hite_prof_begin(ctx, "clip_probe_kernel", st);
+        hipLaunchKernelGGL(clip_probe_kernel, dim3((unsigned)((2 * n_copies + 255) / 256)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
+                           ctx->d_contig_off, ctx->n_contigs, n_copies, n_cand, d_copy_first, d_cand, d_cand_off, d_contig, d_start1, d_end1,
+                           d_minus, est);
+        hite_prof_end(ctx, tkp, st);
+        *d_clip_io = reinterpret_cast<const uint32_t *>(est);
+    }
+    hipLaunchKernelGGL(mode_a_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, d_copy_first, len, mode_a);
+    HITE_CHECK(ctx, hipGetLastError());
+    return HITE_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // public entry: the fine stage for one batch of candidates
 // ---------------------------------------------------------------------------------------------
@@ -661,24 +731,8 @@ extern "C" int hite_flank_region_align_clip_dev(hite_ctx *ctx, void **state_io, 
     ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); src_pass = (int32_t *)p;
     ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 8, &p)); keep_len = (int64_t *)p;
     ACHK(arena_alloc(ctx, S->keep, (size_t)(n_cand + 1) * 8, &p)); out_off = (int64_t *)p;
-    if (n_copies > 0)
-        hipLaunchKernelGGL(flank_sizes_kernel, dim3((unsigned)((n_copies + 255) / 256)), dim3(256), 0, st, ctx->d_contig_off,
-                           ctx->n_contigs, n_copies, d_contig, d_start1, d_end1, flank, len, (int64_t *)nullptr);
-    if (!d_clip && n_copies > 0) {
-        // a table without clip words (the reference's own tuples; never inferred from where the caller's arrays live): the probe
-        // supplies them, so that the rows are padded as the copy finder's own records are -- bare aligned windows, aligned globally
-        // against a longer centre, cost a fifth of the calls (profiles/r05_scale_tests.txt)
-        uint16_t *est;
-        ACHK(arena_alloc(ctx, S->keep, (size_t)n_copies * 4 + 16, &p)); est = (uint16_t *)p;
-        const int tkp = hite_prof_begin(ctx, "clip_probe_kernel", st);
-        hipLaunchKernelGGL(clip_probe_kernel, dim3((unsigned)((2 * n_copies + 255) / 256)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
-                           ctx->d_contig_off, ctx->n_contigs, n_copies, n_cand, d_copy_first, d_cand, d_cand_off, d_contig, d_start1, d_end1,
-                           d_minus, est);
-        hite_prof_end(ctx, tkp, st);
-        d_clip = reinterpret_cast<const uint32_t *>(est);
-    }
-    hipLaunchKernelGGL(mode_a_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, d_copy_first, len, mode_a);
-    HITE_CHECK(ctx, hipGetLastError());
+    ACHK(stage_tables(ctx, S, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_start1, d_end1, d_minus, &d_clip, flank, len,
+                      mode_a, st));
     PassOut A, B;
     ACHK(run_pass(ctx, S, te_type, plant, n_cand, d_cand, d_cand_off, d_copy_first, d_contig, d_start1, d_end1, d_minus, d_clip, flank,
                   len, mode_a, &A, stats, stats + 8, stats + 11, false, st));
@@ -801,4 +855,82 @@ extern "C" int hite_flank_region_align(hite_ctx *ctx, int32_t te_type, int32_t p
                                        int64_t *stats_out) {
     return hite_flank_region_align_clip(ctx, te_type, plant, n_cand, cand, cand_off, copy_first, n_copies, contig, start1, end1, minus,
                                         nullptr, flank, calls, cons, cons_cap, stats_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the rows of one pass by themselves, host buffers (parity tests, diagnostics): what the stage hands to the alignment -- stage_tables
+// and pass_front, the launches of the stage itself, on the modes of pass A (pass = 0) or on those of pass B as if every first500 + last500 form had
+// passed (pass = 1)
+// ---------------------------------------------------------------------------------------------
+__global__ void mode_full_kernel(int n, const int32_t *__restrict__ mode_a, int32_t *__restrict__ mode) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    mode[c] = mode_a[c] == 2 ? 1 : 0;
+}
+
+static int fine_rows_dev(hite_ctx *ctx, PipeState *S, int32_t n_cand, const uint8_t *d_cand, const int64_t *d_cand_off,
+                         const int32_t *d_copy_first, int64_t n_copies, const int32_t *d_contig, const int64_t *d_s1, const int64_t *d_e1,
+                         const uint8_t *d_minus, const uint32_t *d_clip, int32_t flank, int32_t pass, int32_t *nrows, int64_t row_cap,
+                         int32_t *row_copy, int32_t *row_len, uint8_t *row_trunc, int64_t *win_off, int64_t win_cap, uint8_t *win,
+                         int64_t *totals) {
+    hipStream_t st = nullptr;
+    void *p;
+    int64_t *len;
+    int32_t *mode_a, *mode;
+    ACHK(arena_alloc(ctx, S->keep, (size_t)(n_copies + 1) * 8, &p)); len = (int64_t *)p;
+    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); mode_a = (int32_t *)p;
+    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); mode = (int32_t *)p;
+    ACHK(stage_tables(ctx, S, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_s1, d_e1, d_minus, &d_clip, flank, len, mode_a, st));
+    if (pass) hipLaunchKernelGGL(mode_full_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, mode_a, mode);
+    HITE_CHECK(ctx, hipGetLastError());
+    PassFront F;
+    ACHK(pass_front(ctx, S, n_cand, d_copy_first, d_contig, d_s1, d_e1, d_minus, d_clip, flank, len, pass ? mode : mode_a, nullptr, F, st));
+    totals[0] = F.total_rows; totals[1] = F.win_bytes; totals[2] = F.max_len; totals[3] = 0;
+    HITE_CHECK(ctx, hipMemcpy(nrows, F.nrows, (size_t)n_cand * 4, hipMemcpyDeviceToHost));
+    if (F.total_rows > row_cap || F.win_bytes > win_cap) return HITE_ECAP;
+    win_off[0] = 0;
+    if (F.total_rows == 0) return HITE_OK;
+    HITE_CHECK(ctx, hipMemcpy(row_copy, F.row_copy, (size_t)F.total_rows * 4, hipMemcpyDeviceToHost));
+    HITE_CHECK(ctx, hipMemcpy(row_len, F.row_len, (size_t)F.total_rows * 4, hipMemcpyDeviceToHost));
+    HITE_CHECK(ctx, hipMemcpy(row_trunc, F.row_trunc, (size_t)F.total_rows, hipMemcpyDeviceToHost));
+    HITE_CHECK(ctx, hipMemcpy(win_off, F.win_off, (size_t)(F.total_rows + 1) * 8, hipMemcpyDeviceToHost));
+    HITE_CHECK(ctx, hipMemcpy(win, F.win, (size_t)F.win_bytes, hipMemcpyDeviceToHost));
+    return HITE_OK;
+}
+
+extern "C" int hite_fine_rows(hite_ctx *ctx, int32_t n_cand, const uint8_t *cand, const int64_t *cand_off, const int32_t *copy_first,
+                              int64_t n_copies, const int32_t *contig, const int64_t *start1, const int64_t *end1, const uint8_t *minus,
+                              const uint32_t *clip /* per copy, or NULL */, int32_t flank, int32_t pass, int32_t *nrows, int64_t row_cap,
+                              int32_t *row_copy, int32_t *row_len, uint8_t *row_trunc, int64_t *win_off /* row_cap + 1 */, int64_t win_cap,
+                              uint8_t *win, int64_t *totals /* 4 */) {
+    if (!ctx || !ctx->d_bases || n_cand < 0 || n_copies < 0 || pass < 0 || pass > 1 || row_cap < 0 || win_cap < 0 || !totals) return HITE_EINVAL;
+    totals[0] = totals[1] = totals[2] = totals[3] = 0;
+    if (n_cand == 0) return HITE_OK;
+    if (!cand || !cand_off || !copy_first || !nrows || !win_off) return HITE_EINVAL;
+    if (n_copies > 0 && (!contig || !start1 || !end1 || !minus)) return HITE_EINVAL;
+    if (row_cap > 0 && (!row_copy || !row_len || !row_trunc)) return HITE_EINVAL;
+    if (win_cap > 0 && !win) return HITE_EINVAL;
+    if ((int64_t)copy_first[n_cand] != n_copies) return HITE_EINVAL;
+    HITE_CHECK(ctx, hipSetDevice(ctx->device));
+    PBuf dc, dco, dcf, dct, ds, de, dm, dcl;
+    hipError_t e;
+    e = dc.up(cand, cand_off[n_cand]); if (e == hipSuccess) e = dco.up(cand_off, (n_cand + 1) * 8);
+    if (e == hipSuccess) e = dcf.up(copy_first, (n_cand + 1) * 4); if (e == hipSuccess) e = dct.up(contig, n_copies * 4);
+    if (e == hipSuccess) e = ds.up(start1, n_copies * 8); if (e == hipSuccess) e = de.up(end1, n_copies * 8);
+    if (e == hipSuccess) e = dm.up(minus, n_copies);
+    if (e == hipSuccess && clip) e = dcl.up(clip, n_copies * 4);
+    HITE_CHECK(ctx, e);
+    hipLaunchKernelGGL(fold_bytes_kernel, dim3(256), dim3(256), 0, nullptr, (uint8_t *)dc.p, cand_off[n_cand]);
+    PipeState *S = new PipeState();
+    int rc = HITE_OK;
+    if (hipHostMalloc((void **)&S->h_pin, 64 * sizeof(int64_t)) != hipSuccess || hipMalloc((void **)&S->d_scal, 64 * sizeof(int64_t)) != hipSuccess)
+        rc = HITE_EHIP;
+    if (rc == HITE_OK)
+        rc = fine_rows_dev(ctx, S, n_cand, (uint8_t *)dc.p, (int64_t *)dco.p, (int32_t *)dcf.p, n_copies, (int32_t *)dct.p, (int64_t *)ds.p,
+                           (int64_t *)de.p, (uint8_t *)dm.p, clip ? (const uint32_t *)dcl.p : nullptr, flank, pass, nrows, row_cap, row_copy,
+                           row_len, row_trunc, win_off, win_cap, win, totals);
+    hipError_t es = hipDeviceSynchronize();
+    hite_pipeline_release(S);
+    if (rc == HITE_OK && es != hipSuccess) return HITE_EHIP;
+    return rc;
 }

@@ -776,6 +776,18 @@ int hite_flank_region_align_dev(hite_ctx *ctx, void **state_io, int32_t te_type,
 int hite_clip_probe(hite_ctx *ctx, int32_t n_cand, const uint8_t *cand, const int64_t *cand_off, const int32_t *copy_first,
                     int64_t n_copies, const int32_t *contig, const int64_t *start1, const int64_t *end1, const uint8_t *minus,
                     uint32_t *clip_out);
+/* the rows of one pass by themselves (host buffers; parity tests, diagnostics): the table arguments of hite_flank_region_align_clip
+ * (clip == NULL: probed, as the stage does), run through the stage's own row selection, row records and window gather.  pass = 0: the
+ * modes of pass A (a candidate with a window > 1000 gives the first500 + last500 forms of those windows only); pass = 1: the modes
+ * of pass B as if every such form had passed (full windows of the candidates that have a window > 1000, no row for the others).
+ * nrows[n_cand]; per row (candidate after candidate, input order within one) row_copy = index into the table, row_len = bytes of
+ * the (padded) window, row_trunc = 1 for a first500 + last500 form; row r's bytes are win[win_off[r] .. win_off[r] + row_len[r])
+ * (slots are multiples of 16 bytes; win_off has rows + 1 entries).  totals[4] = rows, window bytes, longest row_len, 0 -- filled,
+ * like nrows, also when HITE_ECAP is returned because rows > row_cap or window bytes > win_cap (nothing else is written then). */
+int hite_fine_rows(hite_ctx *ctx, int32_t n_cand, const uint8_t *cand, const int64_t *cand_off, const int32_t *copy_first,
+                   int64_t n_copies, const int32_t *contig, const int64_t *start1, const int64_t *end1, const uint8_t *minus,
+                   const uint32_t *clip, int32_t flank, int32_t pass, int32_t *nrows, int64_t row_cap, int32_t *row_copy,
+                   int32_t *row_len, uint8_t *row_trunc, int64_t *win_off, int64_t win_cap, uint8_t *win, int64_t *totals);
 int hite_flank_region_align_clip(hite_ctx *ctx, int32_t te_type, int32_t plant, int32_t n_cand, const uint8_t *cand,
                                  const int64_t *cand_off, const int32_t *copy_first, int64_t n_copies, const int32_t *contig,
                                  const int64_t *start1, const int64_t *end1, const uint8_t *minus, const uint32_t *clip, int32_t flank,

@@ -109,15 +109,15 @@ def _padded(w, clip, minus, centre, centre_clip=0, centre_minus=False):
     return front + w + back
 
 
-def fine_stage_candidate(te_type, cand, copies, contigs, plant=1, flank=50, contig_names=None, keep_msa=None):
-    """copies: (contig_index, start1, end1, minus[, anchors, clip]) -> [is_TE, info, cons, row_num]; keep_msa: a list that receives
-    the cleaned alignment of every pass that was judged.  clip (find_copies(..., clips=True); non-zero only for records in the
-    reference's coordinates): hite_flank_region_align_clip -- the rows (never the centre, the first row kept) are padded by the clipped
-    bases (_padded); the rows are chosen by the length of the genome window; the first500 + last500 form is cut from the padded window.
-    A tuple WITHOUT the clip field (the reference's own 5-tuple): the clip word is estimated as hite_flank_region_align does (O.clip_probe)"""
-    full, trunc = [], []            # (window, name, clip, minus) per pass, in input order
-    for cp in copies:
+def pass_records(cand, copies, contigs, flank=50, contig_names=None):
+    """the windows that exist (Util.py:8102-8109), in input order: (index into copies, window, name, clip word in the orientation of
+    the genome, minus, has a first500 + last500 form).  A tuple WITHOUT the clip field (the reference's own 5-tuple): the clip word
+    is estimated as hite_flank_region_align does (O.clip_probe); a contig index out of range: no window"""
+    recs = []
+    for idx, cp in enumerate(copies):
         (ci, s, e, mn) = cp[:4]
+        if not 0 <= ci < len(contigs):
+            continue
         w, t = O.flank_window(contigs[ci], s, e, "-" if mn else "+", flank)
         if w is None:
             continue
@@ -127,34 +127,53 @@ def fine_stage_candidate(te_type, cand, copies, contigs, plant=1, flank=50, cont
             # a record without a clip word (the reference's own tuples): estimated from the sequences, hite_flank_region_align's rule
             pr = O.clip_probe(cand, _interval(contigs[ci], s, e, mn))
             clip = ((pr >> 16) | ((pr & 0xffff) << 16)) if mn else pr      # (kept in the orientation of the genome)
-        rec = (w, window_name(cp, contig_names), clip, bool(mn))
-        full.append(rec)
-        if t is not None:
-            trunc.append(rec)
-    if not full:
+        recs.append((idx, w, window_name(cp, contig_names), clip, bool(mn), t is not None))
+    return recs
+
+
+def pass_rows(cand, copies, contigs, flank=50, contig_names=None, cut=False, recs=None):
+    """the rows of one pass of the fine stage -> (keep, wins): the indices into `copies` of the rows kept, in input order, and their
+    windows as the alignment gets them.  cut: the pass on the first500 + last500 forms, of the windows > 1000 only (all 1000 long:
+    the name alone picks the 100); else the full windows.  The rows (never the centre, the first row kept) are padded by the clipped
+    bases (_padded); they are chosen by the length of the genome window; the first500 + last500 form is cut from the padded window.
+    Twin of hite_fine_rows (select_rows_kernel -> row_meta_kernel -> row_gather_kernel).  recs: pass_records(...) when the caller
+    has them"""
+    if recs is None:
+        recs = pass_records(cand, copies, contigs, flank, contig_names)
+    if cut:
+        recs = [r for r in recs if r[5]]
+    if not recs:
+        return [], []
+    lens = [1000 if cut else len(r[1]) for r in recs]
+    keep = select_rows(lens, [r[2] for r in recs])
+    _i0, centre, _n0, clip0, mn0, _t0 = recs[keep[0]]
+    padded = any(r[3] for r in recs)
+    wins = []
+    for k, i in enumerate(keep):
+        _idx, w, _nm, clip, mn, _t = recs[i]
+        if padded and k > 0 and clip:
+            w = _padded(w, clip, mn, centre, clip0, mn0)
+        wins.append(w[:500] + w[-500:] if cut else w)
+    return [recs[i][0] for i in keep], wins
+
+
+def fine_stage_candidate(te_type, cand, copies, contigs, plant=1, flank=50, contig_names=None, keep_msa=None):
+    """copies: (contig_index, start1, end1, minus[, anchors, clip]) -> [is_TE, info, cons, row_num]; keep_msa: a list that receives
+    the cleaned alignment of every pass that was judged.  The rows of each pass: pass_rows (clip words given --
+    find_copies(..., clips=True), hite_flank_region_align_clip -- or estimated, O.clip_probe)"""
+    recs = pass_records(cand, copies, contigs, flank, contig_names)
+    if not recs:
         return [False, "", "", 0]
 
-    def run(recs, cut):
-        lens = [1000 if cut else len(r[0]) for r in recs]
-        names = [r[1] for r in recs]
-        if not any(r[2] for r in recs):
-            wins = [r[0][:500] + r[0][-500:] if cut else r[0] for r in recs]
-            return judge_windows(te_type, cand, wins, plant, names, keep_msa, lens=lens)
-        keep = select_rows(lens, names)
-        centre, _n0, clip0, mn0 = recs[keep[0]]
-        wins = []
-        for k, i in enumerate(keep):
-            w, _nm, clip, mn = recs[i]
-            if k > 0 and clip:
-                w = _padded(w, clip, mn, centre, clip0, mn0)
-            wins.append(w[:500] + w[-500:] if cut else w)
+    def run(cut):
+        _keep, wins = pass_rows(cand, copies, contigs, flank, contig_names, cut, recs=recs)
         return judge_windows(te_type, cand, wins, plant, None, keep_msa)       # (the rows are chosen: <= 100 windows)
 
-    if trunc:
-        res, _ = run(trunc, True)
+    if any(r[5] for r in recs):
+        res, _ = run(True)
         if res[0] == "EXC" or not res[0]:
             return res if res[0] != "EXC" else [False, "EXC", "", 0]
-    res, _ = run(full, False)
+    res, _ = run(False)
     if res[0] == "EXC":
         return [False, "EXC", "", 0]
     return res
