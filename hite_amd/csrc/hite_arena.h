@@ -1,5 +1,5 @@
 // hite_arena.h -- grow-only device arenas (no hipMalloc on the steady-state path), shared by the fine-stage
-// pipeline and the copy finder.
+// pipeline, the pairwise aligner, the copy finder, the protein search, the FMEA chaining and the sorter.
 #pragma once
 #include "hite_common.h"
 #include <vector>

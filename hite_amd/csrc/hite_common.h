@@ -139,6 +139,11 @@ __device__ __forceinline__ uint8_t comp_sym(uint8_t c) {
     }
 }
 
+// lane l takes the value of lane l - 1: one data-parallel move over the whole wavefront (wave_shr:1), no LDS.  Lane 0 gets 0; the
+// caller puts its own value there.
+#define HITE_DPP_WAVE_SHR1 0x138
+__device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, HITE_DPP_WAVE_SHR1, 0xF, 0xF, false); }
+
 // exclusive scan over the 256 threads of a block (s_tmp: >= 8 ints of LDS); returns the
 // exclusive prefix of v and the block total in *total.  Contains __syncthreads().
 __device__ __forceinline__ int block_excl_scan(int v, int *s_tmp, int *total) {

@@ -19,6 +19,7 @@
 // Bound: HBM streaming for the sorts (12 B in + 12 B out per element per pass) and L2-latency for the
 // directory lookups; integer work only.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_scan.h"
 #include "hite_sort.h"
 #include "hite_arena.h"
@@ -1294,18 +1295,6 @@ static int read_back(hite_ctx *ctx, CopyState *S, hipStream_t st, int count) {
 }
 
 // builds the minimizer index of the packed genome; *state_io receives the index handle
-// device temporaries of a host-side function: freed on every return path
-struct DevTmp {
-    void *p[8];
-    int n = 0;
-    ~DevTmp() { for (int i = 0; i < n; i++) if (p[i]) (void)hipFree(p[i]); }
-    hipError_t alloc(void **out, size_t bytes) {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-        if (e == hipSuccess && n < 8) p[n++] = *out;
-        return e;
-    }
-};
-
 static int copy_state_get(hite_ctx *ctx, void **state_io, CopyState **out) {
     CopyState *S = (CopyState *)*state_io;
     if (!S) {
@@ -1806,12 +1795,12 @@ static int find_copies_host(hite_ctx *ctx, void **state_io, int32_t n_cand, cons
     if (!ctx || !state_io || !cand || !cand_off || !copy_first || !n_out) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     if (!*state_io && !restricted) CCHK(hite_copy_index_build(ctx, state_io, nullptr));
-    uint8_t *dc = nullptr;
-    int64_t *dco = nullptr;
     int64_t bytes = cand_off[n_cand];
-    DevTmp tmp;
-    HITE_CHECK(ctx, tmp.alloc((void **)&dc, (size_t)bytes + 64));
-    HITE_CHECK(ctx, tmp.alloc((void **)&dco, (size_t)(n_cand + 1) * 8));
+    DevBuf b_off, b_cand;           // (freed b_cand, b_off)
+    HITE_CHECK(ctx, b_cand.alloc((size_t)bytes + 64));
+    HITE_CHECK(ctx, b_off.alloc((size_t)(n_cand + 1) * 8));
+    uint8_t *dc = b_cand.as<uint8_t>();
+    int64_t *dco = b_off.as<int64_t>();
     HITE_CHECK(ctx, hipMemcpy(dc, cand, (size_t)bytes, hipMemcpyHostToDevice));
     HITE_CHECK(ctx, hipMemcpy(dco, cand_off, (size_t)(n_cand + 1) * 8, hipMemcpyHostToDevice));
     int32_t *dcf, *dct, *dan;

@@ -7,6 +7,7 @@
 // Algorithmic bytes: pack reads G bytes, writes G/4 + G/8; gather reads W/4 + W/8 per window
 // and writes W (+1000 for the first500+last500 form).  Both are HBM-bound streaming kernels.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_align.h"
 #include "hite_genome.h"
 
@@ -184,7 +185,7 @@ __global__ void __launch_bounds__(256) pack_genome_kernel(const uint8_t *__restr
 
 static int genome_alloc(hite_ctx *ctx, const int64_t *contig_off, int32_t n_contigs) {
     if (n_contigs <= 0 || !contig_off || contig_off[0] != 0) return HITE_EINVAL;
-    for (int i = 0; i < n_contigs; i++) if (contig_off[i + 1] < contig_off[i]) return HITE_EINVAL;
+    if (!csr_sorted(contig_off, n_contigs)) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     free_genome(ctx);
     int64_t n = contig_off[n_contigs];
@@ -223,12 +224,11 @@ extern "C" int hite_genome_pack(hite_ctx *ctx, const uint8_t *seq, const int64_t
     if (!ctx || !seq || !contig_off || n_contigs <= 0) return HITE_EINVAL;
     int64_t n = contig_off[n_contigs];
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    uint8_t *d = nullptr;
-    HITE_CHECK(ctx, hipMalloc((void **)&d, (size_t)n + 64));
-    hipError_t e = hipMemcpy(d, seq, (size_t)n, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? hite_genome_pack_dev(ctx, d, contig_off, n_contigs, nullptr) : HITE_EHIP;
+    DevBuf d;
+    HITE_CHECK(ctx, d.alloc((size_t)n + 64));
+    hipError_t e = hipMemcpy(d.p, seq, (size_t)n, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? hite_genome_pack_dev(ctx, d.as<uint8_t>(), contig_off, n_contigs, nullptr) : HITE_EHIP;
     if (rc == HITE_OK && hipDeviceSynchronize() != hipSuccess) rc = HITE_EHIP;
-    (void)hipFree(d);
     return rc;
 }
 
@@ -281,21 +281,18 @@ extern "C" int hite_genome_mask(hite_ctx *ctx, int64_t n, const int32_t *contig,
         ctx->mask_log[2 * ctx->mask_log_n + 1] = b + ctx->h_contig_off[c];
         ctx->mask_log_n++;
     }
-    int32_t *dc = nullptr; int64_t *ds = nullptr, *de = nullptr;
-    hipError_t e = hipMalloc((void **)&dc, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&ds, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&de, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMemcpy(dc, contig, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, start1, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(de, end1, (size_t)n * 8, hipMemcpyHostToDevice);
+    DevBuf de, ds, dc;          // (freed dc, ds, de)
+    hipError_t e = dc.alloc((size_t)n * 4);
+    if (e == hipSuccess) e = ds.alloc((size_t)n * 8);
+    if (e == hipSuccess) e = de.alloc((size_t)n * 8);
+    if (e == hipSuccess) e = hipMemcpy(dc.p, contig, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds.p, start1, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(de.p, end1, (size_t)n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(genome_mask_kernel, dim3((unsigned)n), dim3(256), 0, nullptr, n, dc, ds, de, ctx->d_contig_off, ctx->n_contigs,
-                           ctx->d_nmask);
+        hipLaunchKernelGGL(genome_mask_kernel, dim3((unsigned)n), dim3(256), 0, nullptr, n, dc.as<int32_t>(), ds.as<int64_t>(), de.as<int64_t>(),
+                           ctx->d_contig_off, ctx->n_contigs, ctx->d_nmask);
         e = hipDeviceSynchronize();
     }
-    if (dc) (void)hipFree(dc);
-    if (ds) (void)hipFree(ds);
-    if (de) (void)hipFree(de);
     HITE_CHECK(ctx, e);
     return HITE_OK;
 }
@@ -354,17 +351,6 @@ extern "C" int hite_flank_sizes_dev(hite_ctx *ctx, int64_t n, const int32_t *d_c
 }
 
 // host-buffer wrappers -------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    hipError_t up(const void *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess) return e;
-        return n ? hipMemcpy(p, h, n, hipMemcpyHostToDevice) : hipSuccess;
-    }
-};
-
 extern "C" int hite_flank_sizes(hite_ctx *ctx, int64_t n, const int32_t *contig, const int64_t *start1,
                                 const int64_t *end1, int32_t flank, int64_t *out_len, int64_t *trunc_len) {
     if (!ctx || !ctx->d_bases || n < 0) return HITE_EINVAL;
@@ -386,21 +372,19 @@ extern "C" int hite_flank_sizes(hite_ctx *ctx, int64_t n, const int32_t *contig,
 
 extern "C" int hite_flank_gather(hite_ctx *ctx, int64_t n, const int32_t *contig, const int64_t *start1,
                                  const int64_t *end1, const uint8_t *minus, int32_t flank, const int64_t *out_off,
-                                 uint8_t *out, const int64_t *trunc_off, uint8_t *trunc_out) {
+                                 uint8_t *out, const int64_t *trunc_off, uint8_t *trunc_out) try {
     if (!ctx || !ctx->d_bases || n < 0 || !out_off || !out) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     // sizes of the output pools = last offset + last length (recomputed on the host side from the rules)
-    int64_t *len = (int64_t *)malloc(sizeof(int64_t) * n * 2);
-    if (!len) return HITE_ENOMEM;
-    int rc = hite_flank_sizes(ctx, n, contig, start1, end1, flank, len, len + n);
-    if (rc) { free(len); return rc; }
+    std::vector<int64_t> len((size_t)n * 2);
+    int rc = hite_flank_sizes(ctx, n, contig, start1, end1, flank, len.data(), len.data() + n);
+    if (rc) return rc;
     int64_t tot = 0, ttot = 0;
     for (int64_t i = 0; i < n; i++) {
         if (len[i] && out_off[i] + len[i] > tot) tot = out_off[i] + len[i];
         if (trunc_off && len[n + i] && trunc_off[i] + len[n + i] > ttot) ttot = trunc_off[i] + len[n + i];
     }
-    free(len);
     DevBuf c, s, e, m, oo, o, to, t;
     HITE_CHECK(ctx, c.up(contig, n * 4));
     HITE_CHECK(ctx, s.up(start1, n * 8));
@@ -421,6 +405,8 @@ extern "C" int hite_flank_gather(hite_ctx *ctx, int64_t n, const int32_t *contig
     if (tot) HITE_CHECK(ctx, hipMemcpy(out, o.p, tot, hipMemcpyDeviceToHost));
     if (do_t) HITE_CHECK(ctx, hipMemcpy(trunc_out, t.p, ttot, hipMemcpyDeviceToHost));
     return HITE_OK;
+} catch (const std::bad_alloc &) {
+    return HITE_ENOMEM;
 }
 
 // ---------------------------------------------------------------------------------------------

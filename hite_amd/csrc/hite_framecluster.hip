@@ -18,6 +18,7 @@
 //   3. the ordered leader pass, one THREAD per group of the unit: a row joins the lowest representative whose bit it has.
 // Nothing leaves the workgroup but one cluster index per row (vector stores); there is no global atomic.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -81,12 +82,9 @@ __device__ __forceinline__ int64_t fc_wave_max(int64_t v) {
     return v;
 }
 
-// lane l takes the value of lane l - 1: one data-parallel move over the whole wavefront per 32-bit half (wave_shr:1), no LDS.
-// Lane 0 gets 0; the caller puts its own value there.
-#define FC_DPP_WAVE_SHR1 0x138
-__device__ __forceinline__ int fc_up1(int v) { return __builtin_amdgcn_update_dpp(0, v, FC_DPP_WAVE_SHR1, 0xF, 0xF, false); }
+// lane l takes the value of lane l - 1: one wave_shr1 per 32-bit half.  Lane 0 gets 0; the caller puts its own value there.
 __device__ __forceinline__ int64_t fc_up1(int64_t v) {
-    const uint32_t lo = (uint32_t)fc_up1((int)(uint32_t)v), hi = (uint32_t)fc_up1((int)(uint32_t)((uint64_t)v >> 32));
+    const uint32_t lo = (uint32_t)wave_shr1((int)(uint32_t)v), hi = (uint32_t)wave_shr1((int)(uint32_t)((uint64_t)v >> 32));
     return (int64_t)((uint64_t)hi << 32 | lo);
 }
 
@@ -110,7 +108,7 @@ __device__ __forceinline__ int64_t fc_pair(const uint8_t *a, int m, const uint8_
             const int i = d - lane;
             if (((d - 1) & 63) == 0) a64 = d - 1 + lane < m ? a[d - 1 + lane] : 4;
             const int a_new = __builtin_amdgcn_readlane(a64, (d - 1) & 63);        // a[d - 1], or N past the end
-            ca = fc_up1(ca);
+            ca = wave_shr1(ca);
             int64_t left = fc_up1(cur);
             if (lane == 0) { ca = a_new; left = ahead; }
             if (s0 > 0) ahead = d + 1 <= m ? (int64_t)bnd[d + 1] : 0;
@@ -189,8 +187,6 @@ __global__ __launch_bounds__(FC_WAVES * 64) void fc_unit_kernel(const FcUnit *__
     }
 }
 
-static inline size_t fc_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct FcGroup { int64_t g, row0; int32_t n; };        // group g: its kept rows are the entries [row0, row0 + n) of `order`
 
 extern "C" int hite_frame_cluster(hite_ctx *ctx, int64_t n_group, const int64_t *row_off, const uint8_t *seqs, const int64_t *seq_off,
@@ -200,14 +196,10 @@ extern "C" int hite_frame_cluster(hite_ctx *ctx, int64_t n_group, const int64_t 
     if (!(ident >= 0.0 && ident <= 1.0) || !(cov_short >= 0.0 && cov_short <= 1.0) || !(cov_long >= 0.0 && cov_long <= 1.0))
         return HITE_EINVAL;                                                 // (NaN fails both compares)
     if (n_group == 0) return HITE_OK;
-    if (!row_off || !n_cluster || row_off[0] < 0) return HITE_EINVAL;
-    for (int64_t g = 0; g < n_group; g++)
-        if (row_off[g + 1] < row_off[g]) return HITE_EINVAL;
+    if (!row_off || !n_cluster || !csr_ok(row_off, n_group)) return HITE_EINVAL;
     const int64_t r_lo = row_off[0], r_hi = row_off[n_group];
     if (r_hi > r_lo) {
-        if (!seq_off || !cluster_of_row || seq_off[r_lo] < 0) return HITE_EINVAL;
-        for (int64_t r = r_lo; r < r_hi; r++)
-            if (seq_off[r + 1] < seq_off[r]) return HITE_EINVAL;
+        if (!seq_off || !cluster_of_row || !csr_ok(seq_off + r_lo, r_hi - r_lo)) return HITE_EINVAL;
         if (seq_off[r_hi] > seq_off[r_lo] && !seqs) return HITE_EINVAL;
     }
     const int64_t limit = ctx->framecluster_batch_bytes > 0 ? ctx->framecluster_batch_bytes : FC_BATCH_BYTES;
@@ -265,10 +257,12 @@ extern "C" int hite_frame_cluster(hite_ctx *ctx, int64_t n_group, const int64_t 
                 if (b.rows > (int64_t)1 << 30) return HITE_EINVAL;
             }
         }
+        // the device memory of a batch: the bytes of its rows, its units, its rows, the cluster of every row
+        auto layout = [](const Batch &b) {
+            return ScratchPlan({{1, (size_t)b.bytes, 16}, {sizeof(FcUnit), b.u1 - b.u0, 0}, {sizeof(FcRow), (size_t)b.rows, 0}, {4, (size_t)b.rows, 0}});
+        };
         size_t need = 0;
-        for (const Batch &b : batches)
-            need = std::max(need, fc_up((size_t)b.bytes + 16) + fc_up((b.u1 - b.u0) * sizeof(FcUnit)) + fc_up((size_t)b.rows * sizeof(FcRow)) +
-                                      fc_up((size_t)b.rows * 4));
+        for (const Batch &b : batches) need = std::max(need, layout(b).total);
         HITE_CHECK(ctx, hipSetDevice(ctx->device));
         void *scr = nullptr;
         const int rc = hite_scratch_reserve(ctx, need + 256, &scr);
@@ -278,10 +272,11 @@ extern "C" int hite_frame_cluster(hite_ctx *ctx, int64_t n_group, const int64_t 
         std::vector<int32_t> h_cl;
         size_t row_at = 0;        // unit rows before the batch
         for (const Batch &b : batches) {
-            uint8_t *d_seq = (uint8_t *)scr;
-            FcUnit *d_units = (FcUnit *)(d_seq + fc_up((size_t)b.bytes + 16));
-            FcRow *d_rows = (FcRow *)((uint8_t *)d_units + fc_up((b.u1 - b.u0) * sizeof(FcUnit)));
-            int32_t *d_cl = (int32_t *)((uint8_t *)d_rows + fc_up((size_t)b.rows * sizeof(FcRow)));
+            const ScratchPlan lay = layout(b);
+            uint8_t *d_seq = lay.at<uint8_t>(scr, 0);
+            FcUnit *d_units = lay.at<FcUnit>(scr, 1);
+            FcRow *d_rows = lay.at<FcRow>(scr, 2);
+            int32_t *d_cl = lay.at<int32_t>(scr, 3);
             stage.resize((size_t)b.bytes);
             size_t at = 0;
             for (int64_t k = 0; k < b.rows; k++) {

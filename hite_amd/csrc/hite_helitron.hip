@@ -21,6 +21,7 @@
 //           (sequence, strand, start, end) with no sort and no atomic.
 // Bit planes rather than 2-bit packed bases: a ballot builds a plane in one step, and a 32-position body is one 32-bit word per plane.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_scan.h"
 #include <vector>
 #include <new>
@@ -293,17 +294,7 @@ __global__ __launch_bounds__(256) void heli_dense_kernel(const int64_t *__restri
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-struct HeliBufs {
-    std::vector<void *> p;
-    ~HeliBufs() { for (void *q : p) (void)hipFree(q); }
-};
-#define HELI_ALLOC(ptr, type, bytes)                                                      \
-    do {                                                                                  \
-        void *p__ = nullptr;                                                              \
-        HITE_CHECK(ctx, hipMalloc(&p__, (size_t)(bytes) > 0 ? (size_t)(bytes) : 256));    \
-        B.p.push_back(p__);                                                               \
-        ptr = (type)p__;                                                                  \
-    } while (0)
+#define HELI_ALLOC(ptr, bytes) HITE_CHECK(ctx, B.alloc(ptr, (size_t)(bytes)))
 
 static inline unsigned heli_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -329,15 +320,15 @@ static int heli_check(const HeliArgs &a, std::vector<HeliPat> &hp, std::vector<H
 struct HeliScored { int64_t *d_off, *d_key; int32_t *d_seq, *d_score; int64_t n_anchor; };
 
 // anchors + scores of the nb bytes at d_s (sequence q = bytes rel[q] .. rel[q + 1]); nb > 0
-static int heli_score(hite_ctx *ctx, HeliBufs &B, const uint8_t *d_s, const std::vector<int64_t> &rel, int64_t n, int64_t nb,
+static int heli_score(hite_ctx *ctx, DevPool &B, const uint8_t *d_s, const std::vector<int64_t> &rel, int64_t n, int64_t nb,
                       const std::vector<HeliPat> &hp, const std::vector<HeliPat> &tp, hipStream_t st, HeliScored *S) {
     int32_t *d_cnt; int64_t *d_pos, *d_bs; HeliPat *d_hp, *d_tp;
-    HELI_ALLOC(S->d_off, int64_t *, (n + 1) * 8);
-    HELI_ALLOC(d_cnt, int32_t *, nb * 4);
-    HELI_ALLOC(d_pos, int64_t *, (nb + 1) * 8);
-    HELI_ALLOC(d_bs, int64_t *, scan_tmp_elems(nb) * 8);
-    HELI_ALLOC(d_hp, HeliPat *, hp.size() * sizeof(HeliPat));
-    HELI_ALLOC(d_tp, HeliPat *, tp.size() * sizeof(HeliPat));
+    HELI_ALLOC(S->d_off, (n + 1) * 8);
+    HELI_ALLOC(d_cnt, nb * 4);
+    HELI_ALLOC(d_pos, (nb + 1) * 8);
+    HELI_ALLOC(d_bs, scan_tmp_elems(nb) * 8);
+    HELI_ALLOC(d_hp, hp.size() * sizeof(HeliPat));
+    HELI_ALLOC(d_tp, tp.size() * sizeof(HeliPat));
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_off, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     if (!hp.empty()) HITE_CHECK(ctx, hipMemcpyAsync(d_hp, hp.data(), hp.size() * sizeof(HeliPat), hipMemcpyHostToDevice, st));
     if (!tp.empty()) HITE_CHECK(ctx, hipMemcpyAsync(d_tp, tp.data(), tp.size() * sizeof(HeliPat), hipMemcpyHostToDevice, st));
@@ -350,9 +341,9 @@ static int heli_score(hite_ctx *ctx, HeliBufs &B, const uint8_t *d_s, const std:
     HITE_CHECK(ctx, hipStreamSynchronize(st));
     const int64_t A = S->n_anchor;
     if (A >= ((int64_t)1 << 31)) { hite_prof_end(ctx, tk, st); return HITE_EINVAL; }      // (the lists count in packed 32-bit halves)
-    HELI_ALLOC(S->d_key, int64_t *, A * 8);
-    HELI_ALLOC(S->d_seq, int32_t *, A * 4);
-    HELI_ALLOC(S->d_score, int32_t *, A * 4);
+    HELI_ALLOC(S->d_key, A * 8);
+    HELI_ALLOC(S->d_seq, A * 4);
+    HELI_ALLOC(S->d_score, A * 4);
     if (A == 0) { hite_prof_end(ctx, tk, st); return HITE_OK; }
     hipLaunchKernelGGL(heli_anchor_fill_kernel, dim3(heli_grid(nb)), dim3(256), 0, st, d_s, S->d_off, n, nb, d_pos, S->d_key, S->d_seq);
     hite_prof_end(ctx, tk, st);
@@ -366,10 +357,10 @@ static int heli_score(hite_ctx *ctx, HeliBufs &B, const uint8_t *d_s, const std:
     return HITE_OK;
 }
 
-static int heli_list_alloc(hite_ctx *ctx, HeliBufs &B, int64_t n, HeliList *L) {
-    HELI_ALLOC(L->pos, int64_t *, n * 8);
-    HELI_ALLOC(L->score, int32_t *, n * 4);
-    HELI_ALLOC(L->seq, int32_t *, n * 4);
+static int heli_list_alloc(hite_ctx *ctx, DevPool &B, int64_t n, HeliList *L) {
+    HELI_ALLOC(L->pos, n * 8);
+    HELI_ALLOC(L->score, n * 4);
+    HELI_ALLOC(L->seq, n * 4);
     return HITE_OK;
 }
 
@@ -393,7 +384,7 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
         if (nb == 0) return HITE_OK;
         if (!d_seqs) return HITE_EINVAL;
         HITE_CHECK(ctx, hipSetDevice(ctx->device));
-        HeliBufs B;
+        DevPool B;
         HeliScored S;
         if ((rc = heli_score(ctx, B, d_seqs, rel, n, nb, hpat, tpat, st, &S))) return rc;
         const int64_t A = S.n_anchor;
@@ -402,9 +393,9 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
 
         // the four lists
         int64_t *d_val, *d_pre, *d_bs;
-        HELI_ALLOC(d_val, int64_t *, A * 8);
-        HELI_ALLOC(d_pre, int64_t *, (A + 1) * 8);
-        HELI_ALLOC(d_bs, int64_t *, scan_tmp_elems(A) * 8);
+        HELI_ALLOC(d_val, A * 8);
+        HELI_ALLOC(d_pre, (A + 1) * 8);
+        HELI_ALLOC(d_bs, scan_tmp_elems(A) * 8);
         HeliList L[4];          // plus heads, minus heads, plus tails, minus tails
         int64_t cnt[4];
         int tk = hite_prof_begin(ctx, "heli_list_kernels", st);
@@ -429,12 +420,12 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
 
         // pairs
         int64_t *d_partner, *d_pre_p, *d_pre_m, *d_bs2; int32_t *d_fp, *d_fm;
-        HELI_ALLOC(d_partner, int64_t *, nh * 8);
-        HELI_ALLOC(d_fp, int32_t *, n_hp * 4);
-        HELI_ALLOC(d_fm, int32_t *, n_hm * 4);
-        HELI_ALLOC(d_pre_p, int64_t *, (n_hp + 1) * 8);
-        HELI_ALLOC(d_pre_m, int64_t *, (n_hm + 1) * 8);
-        HELI_ALLOC(d_bs2, int64_t *, scan_tmp_elems(nh) * 8);
+        HELI_ALLOC(d_partner, nh * 8);
+        HELI_ALLOC(d_fp, n_hp * 4);
+        HELI_ALLOC(d_fm, n_hm * 4);
+        HELI_ALLOC(d_pre_p, (n_hp + 1) * 8);
+        HELI_ALLOC(d_pre_m, (n_hm + 1) * 8);
+        HELI_ALLOC(d_bs2, scan_tmp_elems(nh) * 8);
         tk = hite_prof_begin(ctx, "heli_pair_kernels", st);
         hipLaunchKernelGGL(heli_pair_kernel, dim3(heli_grid(nh)), dim3(256), 0, st, L[0], n_hp, L[1], n_hm, L[2], n_tp, L[3], n_tm, S.d_off,
                            len_min, len_max, d_partner, d_fp, d_fm);
@@ -450,8 +441,8 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
         if (stats) stats[3] = total;
         if (w > 0) {
             HeliOut o;
-            HELI_ALLOC(o.seq, int32_t *, w * 4); HELI_ALLOC(o.start, int32_t *, w * 4); HELI_ALLOC(o.end, int32_t *, w * 4);
-            HELI_ALLOC(o.hscore, int32_t *, w * 4); HELI_ALLOC(o.tscore, int32_t *, w * 4); HELI_ALLOC(o.strand, uint8_t *, w);
+            HELI_ALLOC(o.seq, w * 4); HELI_ALLOC(o.start, w * 4); HELI_ALLOC(o.end, w * 4);
+            HELI_ALLOC(o.hscore, w * 4); HELI_ALLOC(o.tscore, w * 4); HELI_ALLOC(o.strand, w);
             hipLaunchKernelGGL(heli_place_kernel, dim3(heli_grid(nh)), dim3(256), 0, st, L[0], n_hp, L[1], n_hm, L[2], L[3], S.d_off, d_partner,
                                d_pre_p, d_pre_m, w, o);
             HITE_CHECK(ctx, hipGetLastError());
@@ -472,17 +463,16 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
 }
 
 // host sequences -> device, then the device form
-static int heli_upload(hite_ctx *ctx, HeliBufs &B, int64_t n, const uint8_t *seqs, const int64_t *seq_off, const uint8_t **d_s) {
+static int heli_upload(hite_ctx *ctx, DevPool &B, int64_t n, const uint8_t *seqs, const int64_t *seq_off, const uint8_t **d_s) {
     *d_s = nullptr;
     if (n <= 0 || !seq_off) return HITE_OK;
-    for (int64_t q = 0; q < n; q++)
-        if (seq_off[q + 1] < seq_off[q]) return HITE_EINVAL;
+    if (!csr_sorted(seq_off, n)) return HITE_EINVAL;
     const int64_t nb = seq_off[n] - seq_off[0];
     if (nb == 0) return HITE_OK;
     if (!seqs) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     uint8_t *d;
-    HELI_ALLOC(d, uint8_t *, nb + 16);
+    HELI_ALLOC(d, nb + 16);
     HITE_CHECK(ctx, hipMemcpy(d, seqs + seq_off[0], (size_t)nb, hipMemcpyHostToDevice));
     *d_s = d;
     return HITE_OK;
@@ -494,7 +484,7 @@ extern "C" int hite_helitron_scan(hite_ctx *ctx, int64_t n, const uint8_t *seqs,
                                   int32_t *start_out, int32_t *end_out, uint8_t *strand_out, int32_t *hscore_out, int32_t *tscore_out,
                                   int64_t *n_out, int64_t *stats) {
     if (!ctx || n < 0) return HITE_EINVAL;
-    HeliBufs B;
+    DevPool B;
     const uint8_t *d_s;
     const int rc = heli_upload(ctx, B, n, seqs, seq_off, &d_s);
     if (rc) return rc;
@@ -514,14 +504,14 @@ extern "C" int hite_helitron_scores(hite_ctx *ctx, int64_t n, const uint8_t *seq
         const int64_t nb = rel[(size_t)n];
         if (nb == 0) return HITE_OK;
         if (!scores_out) return HITE_EINVAL;
-        HeliBufs B;
+        DevPool B;
         const uint8_t *d_s;
         if ((rc = heli_upload(ctx, B, n, seqs, seq_off, &d_s))) return rc;
         HeliScored S;
         hipStream_t st = nullptr;
         if ((rc = heli_score(ctx, B, d_s, rel, n, nb, hpat, tpat, st, &S))) return rc;
         int32_t *d_dense;
-        HELI_ALLOC(d_dense, int32_t *, nb * 16);
+        HELI_ALLOC(d_dense, nb * 16);
         HITE_CHECK(ctx, hipMemsetAsync(d_dense, 0, (size_t)nb * 16, st));
         if (S.n_anchor > 0)
             hipLaunchKernelGGL(heli_dense_kernel, dim3(heli_grid(S.n_anchor)), dim3(256), 0, st, S.d_key, S.d_seq, S.d_score, S.n_anchor,

@@ -13,6 +13,7 @@
 // The host entry point checks every pair (ids, intervals, limits), turns it into a task (byte offsets + lengths) and launches the
 // pairs in batches of IDENT_BATCH, so device memory is the sequences plus one batch whatever n_pair is.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include <vector>
 #include <new>
 
@@ -129,14 +130,13 @@ static int ident_run(hite_ctx *ctx, const uint8_t *seqs, int64_t n_bytes, const 
     hipStream_t st = nullptr;
     const int64_t n_pair = (int64_t)tasks.size();
     const int64_t batch = std::min<int64_t>(ident_batch_size(), n_pair);
-    const size_t seq_bytes = ((size_t)n_bytes + 16 + 255) & ~(size_t)255;
-    const size_t task_bytes = ((size_t)batch * sizeof(IdentTask) + 255) & ~(size_t)255;
+    const ScratchPlan plan({{1, (size_t)n_bytes, 16}, {sizeof(IdentTask), (size_t)batch, 0}, {8, (size_t)batch, 0}});
     void *p = nullptr;
-    int rc = hite_scratch_reserve(ctx, seq_bytes + task_bytes + (size_t)batch * 8 + 256, &p);
+    int rc = hite_scratch_reserve(ctx, plan.total + 256, &p);
     if (rc) return rc;
-    uint8_t *d_seq = (uint8_t *)p;
-    IdentTask *d_tasks = (IdentTask *)(d_seq + seq_bytes);
-    int32_t *d_out = (int32_t *)(d_seq + seq_bytes + task_bytes);
+    uint8_t *d_seq = plan.at<uint8_t>(p, 0);
+    IdentTask *d_tasks = plan.at<IdentTask>(p, 1);
+    int32_t *d_out = plan.at<int32_t>(p, 2);
     if (n_bytes > 0) HITE_CHECK(ctx, hipMemcpyAsync(d_seq, seqs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
     std::vector<int32_t> res((size_t)batch * 2);
     for (int64_t at = 0; at < n_pair; at += batch) {
@@ -163,8 +163,7 @@ extern "C" int hite_pair_identity(hite_ctx *ctx, int64_t n_seq, const uint8_t *s
     if (!ctx || n_seq < 0 || n_pair < 0 || band < 0 || (n_seq > 0 && !seq_off)) return HITE_EINVAL;
     if (n_pair == 0) return HITE_OK;
     if (!a_id || !a_start || !a_end || !b_id || !b_start || !b_end || !strand || !cost_out || !match_out) return HITE_EINVAL;
-    for (int64_t s = 0; s < n_seq; s++)
-        if (seq_off[s + 1] < seq_off[s]) return HITE_EINVAL;
+    if (!csr_sorted(seq_off, n_seq)) return HITE_EINVAL;
     const int64_t base = n_seq > 0 ? seq_off[0] : 0, n_bytes = n_seq > 0 ? seq_off[n_seq] - seq_off[0] : 0;
     if (n_bytes > 0 && !seqs) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
@@ -173,16 +172,12 @@ extern "C" int hite_pair_identity(hite_ctx *ctx, int64_t n_seq, const uint8_t *s
         for (int64_t p = 0; p < n_pair; p++) {
             IdentTask &t = tasks[p];
             t.a0 = t.b0 = 0; t.m = -1; t.n = 0; t.strand = strand[p] ? 1 : 0; t.pad = 0;
-            const int64_t ia = a_id[p], ib = b_id[p];
-            if (ia < 0 || ia >= n_seq || ib < 0 || ib >= n_seq) continue;
-            const int64_t la = seq_off[ia + 1] - seq_off[ia], lb = seq_off[ib + 1] - seq_off[ib];
-            if (a_start[p] < 0 || a_end[p] < a_start[p] || a_end[p] > la || b_start[p] < 0 || b_end[p] < b_start[p] || b_end[p] > lb) continue;
-            const int64_t m = a_end[p] - a_start[p], n = b_end[p] - b_start[p];
-            if (m > IDENT_MAX_LEN || n > IDENT_MAX_LEN) continue;
+            int64_t m, n;
+            if (!interval_pair_ok(n_seq, seq_off, a_id[p], a_start[p], a_end[p], b_id[p], b_start[p], b_end[p], 0, IDENT_MAX_LEN, &m, &n)) continue;
             const int64_t diff = n > m ? n - m : m - n;
             if (diff + 2 * (int64_t)band + 1 > HITE_IDENT_MAX_WIDTH) continue;
-            t.a0 = seq_off[ia] - base + a_start[p];
-            t.b0 = seq_off[ib] - base + b_start[p];
+            t.a0 = seq_off[a_id[p]] - base + a_start[p];
+            t.b0 = seq_off[b_id[p]] - base + b_start[p];
             t.m = (int32_t)m; t.n = (int32_t)n;
         }
         return ident_run(ctx, seqs ? seqs + base : nullptr, n_bytes, tasks, band, cost_out, match_out);

@@ -15,6 +15,7 @@
 // maximum in row-major order (per-lane best, then a wave reduction on (score, -i, -j)); the traceback and the identity count are
 // a serial walk every lane executes alike.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 
 #define ITR_MAX_H 500   // ItrAlign's own cap on either end (main() constructs it with 500)
 #define ITR_LDS_H 64    // up to here the traceback store fits the wavefront's LDS share
@@ -196,33 +197,25 @@ extern "C" int hite_itr_search(hite_ctx *ctx, int64_t n, const uint8_t *seqs, co
     if (!ctx || n < 0 || (n > 0 && (!seqs || !seq_off || !out))) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!csr_sorted(seq_off, n)) return HITE_EINVAL;
     int64_t max_l = 0;
-    for (int64_t k = 0; k < n; k++) {
-        int64_t l = seq_off[k + 1] - seq_off[k];
-        if (l < 0) return HITE_EINVAL;
-        if (l > max_l) max_l = l;
-    }
+    for (int64_t k = 0; k < n; k++) max_l = std::max(max_l, seq_off[k + 1] - seq_off[k]);
     int64_t mh = end_len > 0 ? (max_l < end_len ? max_l : end_len) : max_l / 2;
     if (mh > ITR_MAX_H) mh = ITR_MAX_H;
     const size_t nb = (size_t)seq_off[n];
-    uint8_t *d_seq = nullptr;
-    int64_t *d_off = nullptr;
-    int32_t *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_seq, nb + 16);
-    if (e == hipSuccess) e = hipMalloc(&d_off, (size_t)(n + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)n * 32);
-    if (e == hipSuccess && nb) e = hipMemcpy(d_seq, seqs, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off, seq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
+    DevBuf d_out, d_off, d_seq;         // (freed d_seq, d_off, d_out)
+    hipError_t e = d_seq.alloc(nb + 16);
+    if (e == hipSuccess) e = d_off.alloc((size_t)(n + 1) * 8);
+    if (e == hipSuccess) e = d_out.alloc((size_t)n * 32);
+    if (e == hipSuccess && nb) e = hipMemcpy(d_seq.p, seqs, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off.p, seq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
     int rc = HITE_OK;
     if (e == hipSuccess) {
-        rc = hite_itr_search_dev(ctx, n, d_seq, d_off, end_len, (int32_t)mh, min_identity, min_len, match, mismatch, gap_open,
-                                 gap_extend, d_out, nullptr);
+        rc = hite_itr_search_dev(ctx, n, d_seq.as<uint8_t>(), d_off.as<int64_t>(), end_len, (int32_t)mh, min_identity, min_len, match, mismatch,
+                                 gap_open, gap_extend, d_out.as<int32_t>(), nullptr);
         if (rc == HITE_OK) e = hipDeviceSynchronize();
-        if (rc == HITE_OK && e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost);
+        if (rc == HITE_OK && e == hipSuccess) e = hipMemcpy(out, d_out.p, (size_t)n * 32, hipMemcpyDeviceToHost);
     }
-    if (d_seq) (void)hipFree(d_seq);
-    if (d_off) (void)hipFree(d_off);
-    if (d_out) (void)hipFree(d_out);
     if (rc) return rc;
     HITE_CHECK(ctx, e);
     return HITE_OK;

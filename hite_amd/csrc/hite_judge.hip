@@ -19,6 +19,7 @@
 // Algorithmic bytes per candidate: rows*cols read (1 B/cell) + 12 B/col of column statistics
 // + cols bytes of consensus written.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_fill.h"
 
 #ifndef JB
@@ -338,17 +339,6 @@ __global__ void tsd_search_kernel(int n, const uint8_t *__restrict__ bytes, cons
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    hipError_t up(const void *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess) return e;
-        return n ? hipMemcpy(p, h, n, hipMemcpyHostToDevice) : hipSuccess;
-    }
-};
-
 static int batch_shape(int32_t n, const int64_t *msa_off, const int32_t *rows, const int32_t *cols, int64_t *total_bytes,
                        int64_t *total_cols, int *maxC, int *maxR, int64_t *col_off /* n+1 or NULL */) {
     int64_t tb = 0, tc = 0;
@@ -382,22 +372,20 @@ extern "C" int hite_sparse_cols_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_m
 }
 
 extern "C" int hite_sparse_cols(hite_ctx *ctx, int32_t n, const uint8_t *msa, const int64_t *msa_off, const int32_t *rows,
-                                const int32_t *cols, uint8_t *out, int32_t *new_cols) {
+                                const int32_t *cols, uint8_t *out, int32_t *new_cols) try {
     if (!ctx || n < 0 || !msa || !msa_off || !rows || !cols || !out || !new_cols) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     int64_t tb, tc; int mc, mr;
-    int64_t *co = (int64_t *)malloc(sizeof(int64_t) * (n + 1));
-    if (!co) return HITE_ENOMEM;
-    int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, co);
-    if (rc) { free(co); return rc; }
-    for (int i = 0; i < n; i++) if (rows[i] <= 0 || cols[i] <= 0) { free(co); return HITE_EINVAL; }
-    DBuf dm, dof, dr, dc, dout, dnc, dco;
+    std::vector<int64_t> co((size_t)n + 1);
+    int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, co.data());
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) if (rows[i] <= 0 || cols[i] <= 0) return HITE_EINVAL;
+    DevBuf dm, dof, dr, dc, dout, dnc, dco;
     hipError_t e;
     e = dm.up(msa, tb); if (e == hipSuccess) e = dof.up(msa_off, n * 8); if (e == hipSuccess) e = dr.up(rows, n * 4);
     if (e == hipSuccess) e = dc.up(cols, n * 4); if (e == hipSuccess) e = dout.alloc(tb); if (e == hipSuccess) e = dnc.alloc(n * 4);
-    if (e == hipSuccess) e = dco.up(co, (n + 1) * 8);
-    free(co);
+    if (e == hipSuccess) e = dco.up(co.data(), (n + 1) * 8);
     HITE_CHECK(ctx, e);
     rc = hite_sparse_cols_dev(ctx, n, (uint8_t *)dm.p, (int64_t *)dof.p, (int32_t *)dr.p, (int32_t *)dc.p, (int64_t *)dco.p,
                                tc, (uint8_t *)dout.p, (int32_t *)dnc.p, nullptr);
@@ -406,6 +394,8 @@ extern "C" int hite_sparse_cols(hite_ctx *ctx, int32_t n, const uint8_t *msa, co
     HITE_CHECK(ctx, hipMemcpy(out, dout.p, tb, hipMemcpyDeviceToHost));
     HITE_CHECK(ctx, hipMemcpy(new_cols, dnc.p, n * 4, hipMemcpyDeviceToHost));
     return HITE_OK;
+} catch (const std::bad_alloc &) {
+    return HITE_ENOMEM;
 }
 
 extern "C" int hite_column_vote(hite_ctx *ctx, int32_t n, const uint8_t *msa, const int64_t *msa_off, const int32_t *rows,
@@ -416,7 +406,7 @@ extern "C" int hite_column_vote(hite_ctx *ctx, int32_t n, const uint8_t *msa, co
     int64_t tb, tc; int mc, mr;
     int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, nullptr);
     if (rc) return rc;
-    DBuf dm, dof, dr, dc, dco, dcnt;
+    DevBuf dm, dof, dr, dc, dco, dcnt;
     hipError_t e;
     e = dm.up(msa, tb); if (e == hipSuccess) e = dof.up(msa_off, n * 8); if (e == hipSuccess) e = dr.up(rows, n * 4);
     if (e == hipSuccess) e = dc.up(cols, n * 4); if (e == hipSuccess) e = dco.up(col_off, n * 8);
@@ -435,28 +425,26 @@ extern "C" int hite_column_vote(hite_ctx *ctx, int32_t n, const uint8_t *msa, co
 extern "C" int hite_boundary_search(hite_ctx *ctx, int32_t n, const uint8_t *msa, const int64_t *msa_off,
                                     const int32_t *rows, const int32_t *cols, const int32_t *pos, const int32_t *side,
                                     const double *thr, const double *int_thr, const double *out_thr, int32_t variant,
-                                    int32_t win_in, int32_t win_out, int32_t *boundary_out, int32_t *valid_out) {
+                                    int32_t win_in, int32_t win_out, int32_t *boundary_out, int32_t *valid_out) try {
     if (!ctx || n < 0 || !msa || !pos || !side || !thr || !boundary_out) return HITE_EINVAL;
     if (variant != 3 && variant != 4) return HITE_EINVAL;
     if (variant == 4 && (!int_thr || !out_thr)) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     int64_t tb, tc; int mc, mr;
-    int64_t *co = (int64_t *)malloc(sizeof(int64_t) * (n + 1));
-    if (!co) return HITE_ENOMEM;
-    int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, co);
-    if (rc || mr > MAXSEL) { free(co); return HITE_EINVAL; }
-    for (int i = 0; i < n; i++) if (rows[i] <= 0 || cols[i] <= 0 || pos[i] < 0 || pos[i] >= cols[i]) { free(co); return HITE_EINVAL; }
-    DBuf dm, dof, dr, dc, dco, dpos, dside, dthr, dit, dot, dcs, db, dv;
+    std::vector<int64_t> co((size_t)n + 1);
+    int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, co.data());
+    if (rc || mr > MAXSEL) return HITE_EINVAL;
+    for (int i = 0; i < n; i++) if (rows[i] <= 0 || cols[i] <= 0 || pos[i] < 0 || pos[i] >= cols[i]) return HITE_EINVAL;
+    DevBuf dm, dof, dr, dc, dco, dpos, dside, dthr, dit, dot, dcs, db, dv;
     hipError_t e;
     e = dm.up(msa, tb); if (e == hipSuccess) e = dof.up(msa_off, n * 8); if (e == hipSuccess) e = dr.up(rows, n * 4);
-    if (e == hipSuccess) e = dc.up(cols, n * 4); if (e == hipSuccess) e = dco.up(co, (n + 1) * 8);
+    if (e == hipSuccess) e = dc.up(cols, n * 4); if (e == hipSuccess) e = dco.up(co.data(), (n + 1) * 8);
     if (e == hipSuccess) e = dpos.up(pos, n * 4); if (e == hipSuccess) e = dside.up(side, n * 4);
     if (e == hipSuccess) e = dthr.up(thr, n * 8);
     if (e == hipSuccess && variant == 4) e = dit.up(int_thr, n * 8);
     if (e == hipSuccess && variant == 4) e = dot.up(out_thr, n * 8);
     if (e == hipSuccess) e = dcs.alloc((size_t)tc * CS + 64); if (e == hipSuccess) e = db.alloc(n * 4); if (e == hipSuccess) e = dv.alloc(n * 4);
-    free(co);
     HITE_CHECK(ctx, e);
     hipLaunchKernelGGL(fold_kernel, dim3(1024), dim3(256), 0, nullptr, (uint8_t *)dm.p, tb);
     SearchParams P;
@@ -471,6 +459,8 @@ extern "C" int hite_boundary_search(hite_ctx *ctx, int32_t n, const uint8_t *msa
     HITE_CHECK(ctx, hipMemcpy(boundary_out, db.p, n * 4, hipMemcpyDeviceToHost));
     if (valid_out) HITE_CHECK(ctx, hipMemcpy(valid_out, dv.p, n * 4, hipMemcpyDeviceToHost));
     return HITE_OK;
+} catch (const std::bad_alloc &) {
+    return HITE_ENOMEM;
 }
 
 // which kernel judges which alignment (JUDGE_CLS_*):
@@ -727,25 +717,23 @@ extern "C" int hite_judge_dev(hite_ctx *ctx, int32_t te_type, int32_t plant, int
 
 extern "C" int hite_judge(hite_ctx *ctx, int32_t te_type, int32_t plant, int32_t n, const uint8_t *msa,
                           const int64_t *msa_off, const int32_t *rows, const int32_t *cols, const uint8_t *cand,
-                          const int64_t *cand_off, hite_call *calls, uint8_t *cons) {
+                          const int64_t *cand_off, hite_call *calls, uint8_t *cons) try {
     if (!ctx || n < 0 || !msa || !msa_off || !rows || !cols || !cand || !cand_off || !calls || !cons) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     int64_t tb, tc; int mc, mr;
-    int64_t *co = (int64_t *)malloc(sizeof(int64_t) * (n + 1));
-    if (!co) return HITE_ENOMEM;
-    int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, co);
-    if (rc) { free(co); return rc; }
-    if (mc <= 0 || mr <= 0) { free(co); return HITE_EINVAL; }
+    std::vector<int64_t> co((size_t)n + 1);
+    int rc = batch_shape(n, msa_off, rows, cols, &tb, &tc, &mc, &mr, co.data());
+    if (rc) return rc;
+    if (mc <= 0 || mr <= 0) return HITE_EINVAL;
     int64_t cand_bytes = cand_off[n];
     int64_t cons_bytes = tc + 8 * (int64_t)n;
-    DBuf dm, dof, dr, dc, dco, dcand, dcoff, dcalls, dcons;
+    DevBuf dm, dof, dr, dc, dco, dcand, dcoff, dcalls, dcons;
     hipError_t e;
     e = dm.up(msa, tb); if (e == hipSuccess) e = dof.up(msa_off, n * 8); if (e == hipSuccess) e = dr.up(rows, n * 4);
-    if (e == hipSuccess) e = dc.up(cols, n * 4); if (e == hipSuccess) e = dco.up(co, (n + 1) * 8);
+    if (e == hipSuccess) e = dc.up(cols, n * 4); if (e == hipSuccess) e = dco.up(co.data(), (n + 1) * 8);
     if (e == hipSuccess) e = dcand.up(cand, cand_bytes); if (e == hipSuccess) e = dcoff.up(cand_off, (n + 1) * 8);
     if (e == hipSuccess) e = dcalls.alloc(sizeof(hite_call) * n); if (e == hipSuccess) e = dcons.alloc(cons_bytes + 16);
-    free(co);
     HITE_CHECK(ctx, e);
     hipLaunchKernelGGL(fold_kernel, dim3(1024), dim3(256), 0, nullptr, (uint8_t *)dm.p, tb);
     hipLaunchKernelGGL(fold_kernel, dim3(64), dim3(256), 0, nullptr, (uint8_t *)dcand.p, cand_bytes);
@@ -757,6 +745,8 @@ extern "C" int hite_judge(hite_ctx *ctx, int32_t te_type, int32_t plant, int32_t
     HITE_CHECK(ctx, hipMemcpy(calls, dcalls.p, sizeof(hite_call) * n, hipMemcpyDeviceToHost));
     HITE_CHECK(ctx, hipMemcpy(cons, dcons.p, cons_bytes, hipMemcpyDeviceToHost));
     return HITE_OK;
+} catch (const std::bad_alloc &) {
+    return HITE_ENOMEM;
 }
 
 extern "C" int hite_tsd_search(hite_ctx *ctx, int32_t n, const uint8_t *rows_bytes, const int64_t *row_off,
@@ -765,7 +755,7 @@ extern "C" int hite_tsd_search(hite_ctx *ctx, int32_t n, const uint8_t *rows_byt
     if (!ctx || n < 0 || !rows_bytes || !row_off || !bstart || !bend || !tsd_len_out || !left_out || !right_out) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    DBuf db, dof, dbs, dbe, dl, dlo, dro;
+    DevBuf db, dof, dbs, dbe, dl, dlo, dro;
     hipError_t e;
     e = db.up(rows_bytes, row_off[n]); if (e == hipSuccess) e = dof.up(row_off, (n + 1) * 8);
     if (e == hipSuccess) e = dbs.up(bstart, n * 4); if (e == hipSuccess) e = dbe.up(bend, n * 4);
@@ -865,7 +855,7 @@ extern "C" int hite_ltr_frame(hite_ctx *ctx, int32_t n, const uint8_t *frames, c
         int64_t e = off[i] + (int64_t)rows[i] * cols[i];
         if (e > total) total = e;
     }
-    DBuf df, doff, dr, dc, dok, db;
+    DevBuf df, doff, dr, dc, dok, db;
     hipError_t e = df.alloc((size_t)total + 16);
     if (e == hipSuccess && total) e = hipMemcpy(df.p, frames, (size_t)total, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = doff.up(off, (size_t)n * 8);
@@ -1011,7 +1001,7 @@ extern "C" int hite_ltr_both_ends(hite_ctx *ctx, int32_t n, const uint8_t *msa, 
     }
     const size_t maxC16 = ((size_t)maxC + 15) & ~(size_t)15;
     const size_t slot = 12 * maxC16 + 64;
-    DBuf dm, dmo, dr, dc, dcd, dco, dfr, dfro, dfu, dfuo, dfc, dnp, dst, dscr;
+    DevBuf dm, dmo, dr, dc, dcd, dco, dfr, dfro, dfu, dfuo, dfc, dnp, dst, dscr;
     hipError_t e = dm.alloc((size_t)msa_total + 16);
     if (e == hipSuccess && msa_total) e = hipMemcpy(dm.p, msa, (size_t)msa_total, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dmo.up(msa_off, (size_t)n * 8);

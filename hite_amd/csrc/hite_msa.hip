@@ -10,6 +10,7 @@
 //   * layout / fill kernels turn those ops into the rows x cols matrix -- in the pipeline fused with
 //     remove_sparse_col_in_align_file, so that only the surviving columns are ever written.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_align.h"
 #include "hite_scan.h"
 #include "hite_fill.h"
@@ -633,65 +634,51 @@ extern "C" int hite_star_msa_fill_dev(hite_ctx *ctx, int32_t n, const uint8_t *d
     return HITE_OK;
 }
 
-struct MBuf {
-    void *p = nullptr;
-    ~MBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    hipError_t up(const void *h, size_t n) {
-        hipError_t e = alloc(n);
-        if (e != hipSuccess) return e;
-        return n ? hipMemcpy(p, h, n, hipMemcpyHostToDevice) : hipSuccess;
-    }
-};
-
 // host-buffer convenience: pass 1 (msa_out == NULL) returns cols_out / rows_out only; otherwise also the
 // alignments at msa_off_out[i] (16-byte aligned slots), msa_cap bytes available.  info_out (may be NULL): 5 int32 per
 // input row (U, certified, status, k*, band words | 0x100), zeros for the centres.
 static int star_msa_host(hite_ctx *ctx, int32_t n, const uint8_t *win, const int64_t *win_off,
                          const int32_t *row_first, int32_t *cols_out, int32_t *rows_out, int64_t msa_cap, uint8_t *msa_out,
-                         int64_t *msa_off_out, int32_t *info_out, bool sparse, uint8_t **msa_alloc = nullptr, int64_t *msa_bytes = nullptr) {
+                         int64_t *msa_off_out, int32_t *info_out, bool sparse, uint8_t **msa_alloc = nullptr, int64_t *msa_bytes = nullptr) try {
     if (!ctx || n < 0 || !win || !win_off || !row_first || !cols_out) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     int64_t total_rows = row_first[n];
-    int64_t *ops_base = (int64_t *)malloc(sizeof(int64_t) * (n + 1));
-    if (!ops_base) return HITE_ENOMEM;
+    std::vector<int64_t> ops_base((size_t)n + 1);
     int64_t acc = 0;
     int maxlen = 1;
     for (int c = 0; c < n; c++) {
         int R = row_first[c + 1] - row_first[c];
-        if (R <= 0) { free(ops_base); return HITE_EINVAL; }
+        if (R <= 0) return HITE_EINVAL;
         int64_t m = win_off[row_first[c] + 1] - win_off[row_first[c]];
         ops_base[c] = acc;
         acc += (int64_t)(R + 1) * (m + 1);
         for (int r = 0; r < R; r++) {
             int64_t L = win_off[row_first[c] + r + 1] - win_off[row_first[c] + r];
-            if (L <= 0 || L > 32767) { free(ops_base); return HITE_EINVAL; }
+            if (L <= 0 || L > 32767) return HITE_EINVAL;
             if (L > maxlen) maxlen = (int)L;
         }
     }
     ops_base[n] = acc;
-    int32_t *wl = (int32_t *)malloc(sizeof(int32_t) * (total_rows + 1));
-    int64_t *wo = (int64_t *)malloc(sizeof(int64_t) * (total_rows + 1));
-    if (!wl || !wo) { free(ops_base); free(wl); free(wo); return HITE_ENOMEM; }
-    // the device side reads the row bases 16 at a time: every window gets a 16-byte aligned, padded slot
-    int64_t pos = 0;
-    for (int64_t g = 0; g < total_rows; g++) { wl[g] = (int32_t)(win_off[g + 1] - win_off[g]); wo[g] = pos; pos += ((int64_t)wl[g] + 15) & ~(int64_t)15; }
-    wo[total_rows] = pos;
-    uint8_t *wpad = (uint8_t *)calloc((size_t)pos + 16, 1);
-    if (!wpad) { free(ops_base); free(wl); free(wo); return HITE_ENOMEM; }
-    for (int64_t g = 0; g < total_rows; g++) memcpy(wpad + wo[g], win + win_off[g], (size_t)wl[g]);
-    MBuf dw, dwo, dwl, drf, dob, dcols, dst, dmo, dmsa, dnew, dlast, drows, dinfo;
+    DevBuf dw, dwo, dwl, drf, dob, dcols, dst, dmo, dmsa, dnew, dlast, drows, dinfo;
     hipError_t e;
-    e = dw.up(wpad, pos + 16); if (e == hipSuccess) e = dwo.up(wo, (total_rows + 1) * 8);
-    if (e == hipSuccess) e = dwl.up(wl, total_rows * 4);
-    free(wl); free(wo); free(wpad);
-    if (e == hipSuccess) e = drf.up(row_first, (n + 1) * 4); if (e == hipSuccess) e = dob.up(ops_base, (n + 1) * 8);
+    {
+        std::vector<int32_t> wl((size_t)total_rows + 1);
+        std::vector<int64_t> wo((size_t)total_rows + 1);
+        // the device side reads the row bases 16 at a time: every window gets a 16-byte aligned, padded slot
+        int64_t pos = 0;
+        for (int64_t g = 0; g < total_rows; g++) { wl[g] = (int32_t)(win_off[g + 1] - win_off[g]); wo[g] = pos; pos += ((int64_t)wl[g] + 15) & ~(int64_t)15; }
+        wo[total_rows] = pos;
+        std::vector<uint8_t> wpad((size_t)pos + 16, 0);
+        for (int64_t g = 0; g < total_rows; g++) memcpy(wpad.data() + wo[g], win + win_off[g], (size_t)wl[g]);
+        e = dw.up(wpad.data(), pos + 16); if (e == hipSuccess) e = dwo.up(wo.data(), (total_rows + 1) * 8);
+        if (e == hipSuccess) e = dwl.up(wl.data(), total_rows * 4);
+    }
+    if (e == hipSuccess) e = drf.up(row_first, (n + 1) * 4); if (e == hipSuccess) e = dob.up(ops_base.data(), (n + 1) * 8);
     if (e == hipSuccess) e = dcols.alloc(n * 4); if (e == hipSuccess) e = dst.alloc(n * 4);
     if (e == hipSuccess) e = dnew.alloc(n * 4); if (e == hipSuccess) e = dlast.alloc(n * 4);
     if (e == hipSuccess) e = drows.alloc(n * 4);
     if (e == hipSuccess && info_out) e = dinfo.alloc((size_t)total_rows * 20);
-    free(ops_base);
     HITE_CHECK(ctx, e);
     int rc = star_msa_launch(ctx, n, (uint8_t *)dw.p, (int64_t *)dwo.p, (int32_t *)dwl.p, (int32_t *)drf.p, total_rows, (int64_t *)dob.p, acc,
                              maxlen, (int32_t *)dcols.p, (int32_t *)dst.p, sparse ? (int32_t *)dnew.p : nullptr,
@@ -699,19 +686,17 @@ static int star_msa_host(hite_ctx *ctx, int32_t n, const uint8_t *win, const int
     if (rc) return rc;
     HITE_CHECK(ctx, hipDeviceSynchronize());
     HITE_CHECK(ctx, hipMemcpy(cols_out, sparse ? dnew.p : dcols.p, n * 4, hipMemcpyDeviceToHost));
-    int32_t *rows_h = (int32_t *)malloc(sizeof(int32_t) * n);
-    if (!rows_h) return HITE_ENOMEM;
-    if (hipMemcpy(rows_h, drows.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) { free(rows_h); return HITE_EHIP; }
-    if (rows_out) memcpy(rows_out, rows_h, sizeof(int32_t) * n);
-    if (info_out && hipMemcpy(info_out, dinfo.p, (size_t)total_rows * 20, hipMemcpyDeviceToHost) != hipSuccess) { free(rows_h); return HITE_EHIP; }
-    if (!msa_out && !msa_alloc) { free(rows_h); return HITE_OK; }
-    if (!msa_off_out) { free(rows_h); return HITE_EINVAL; }
+    std::vector<int32_t> rows_h((size_t)n);
+    if (hipMemcpy(rows_h.data(), drows.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return HITE_EHIP;
+    if (rows_out) memcpy(rows_out, rows_h.data(), sizeof(int32_t) * n);
+    if (info_out && hipMemcpy(info_out, dinfo.p, (size_t)total_rows * 20, hipMemcpyDeviceToHost) != hipSuccess) return HITE_EHIP;
+    if (!msa_out && !msa_alloc) return HITE_OK;
+    if (!msa_off_out) return HITE_EINVAL;
     int64_t off = 0;
     for (int c = 0; c < n; c++) {
         msa_off_out[c] = off;
         off += ((int64_t)rows_h[c] * cols_out[c] + 15) / 16 * 16;
     }
-    free(rows_h);
     if (msa_alloc) {       // one-call form: the alignments come back in a buffer of exactly the size they need (hite_host_free)
         msa_out = (uint8_t *)malloc((size_t)off + 16);
         if (!msa_out) return HITE_ENOMEM;
@@ -730,6 +715,8 @@ static int star_msa_host(hite_ctx *ctx, int32_t n, const uint8_t *win, const int
     HITE_CHECK(ctx, hipDeviceSynchronize());
     HITE_CHECK(ctx, hipMemcpy(msa_out, dmsa.p, off, hipMemcpyDeviceToHost));
     return HITE_OK;
+} catch (const std::bad_alloc &) {
+    return HITE_ENOMEM;
 }
 
 extern "C" int hite_star_msa(hite_ctx *ctx, int32_t n, const uint8_t *win, const int64_t *win_off,

@@ -19,6 +19,7 @@
 // start coordinates in an unsigned 32-bit one that only ties look at.  The raw HSPs (at most 12 per pair) leave by ordinary vector
 // stores; the host orders them and applies the containment rule.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -74,14 +75,12 @@ __device__ __forceinline__ bool ph_best_better(int64_t a, uint32_t b, uint32_t e
 
 struct PhTask { int64_t q0, s0; int32_t m, n; };      // byte offsets of the two intervals in the batch's bytes
 
-// lane l takes the value of lane l - 1 (wave_shr:1), lane 0 gets 0 and the caller puts its own value there
-#define PH_DPP_WAVE_SHR1 0x138
-__device__ __forceinline__ int ph_up1(int v) { return __builtin_amdgcn_update_dpp(0, v, PH_DPP_WAVE_SHR1, 0xF, 0xF, false); }
+// lane l takes the value of lane l - 1 (wave_shr1), lane 0 gets 0 and the caller puts its own value there
 __device__ __forceinline__ PhVal ph_up1(PhVal v) {
     PhVal r;
-    const uint32_t lo = (uint32_t)ph_up1((int)(uint32_t)v.a), hi = (uint32_t)ph_up1((int)(uint32_t)((uint64_t)v.a >> 32));
+    const uint32_t lo = (uint32_t)wave_shr1((int)(uint32_t)v.a), hi = (uint32_t)wave_shr1((int)(uint32_t)((uint64_t)v.a >> 32));
     r.a = (int64_t)((uint64_t)hi << 32 | lo);
-    r.b = (uint32_t)ph_up1((int)v.b);
+    r.b = (uint32_t)wave_shr1((int)v.b);
     return r;
 }
 
@@ -135,7 +134,7 @@ __device__ __forceinline__ PhBest ph_align(const uint8_t *q, int m, const uint8_
                 a64 = r <= m ? ph_code(q[r - 1]) : 4;
             }
             const int a_new = __builtin_amdgcn_readlane(a64, (d - 1) & 63);      // the code of row ib + d
-            ca = ph_up1(ca);
+            ca = wave_shr1(ca);
             PhVal left = ph_up1(cur);
             if (lane == 0) { ca = a_new; left = ahead; }
             ahead = edge(ib + d + 1);
@@ -285,8 +284,6 @@ __global__ __launch_bounds__(PH_WAVES * 64) void ph_pair_kernel(const PhTask *__
     }
 }
 
-static inline size_t ph_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct PhHsp { int32_t f[7]; };      // q_start, q_end, s_start, s_end, score, matches, columns
 
 extern "C" int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs, const int64_t *seq_off, int64_t n_pair, const int32_t *a_id,
@@ -299,8 +296,7 @@ extern "C" int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs,
         return HITE_OK;
     }
     if (!a_id || !a_start || !a_end || !b_id || !b_start || !b_end || !status || !first || !n_out || (cap > 0 && !recs)) return HITE_EINVAL;
-    for (int64_t s = 0; s < n_seq; s++)
-        if (seq_off[s + 1] < seq_off[s]) return HITE_EINVAL;
+    if (!csr_sorted(seq_off, n_seq)) return HITE_EINVAL;
     if (n_seq > 0 && seq_off[n_seq] > seq_off[0] && !seqs) return HITE_EINVAL;
     const int64_t batch_pairs = ctx->pairhsp_batch_pairs > 0 ? ctx->pairhsp_batch_pairs : PH_BATCH_PAIRS;
     try {
@@ -312,25 +308,26 @@ extern "C" int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs,
         std::vector<Batch> batches;
         for (int64_t p = 0; p < n_pair; p++) {
             status[p] = -1;
-            const int64_t ia = a_id[p], ib = b_id[p];
-            if (ia < 0 || ia >= n_seq || ib < 0 || ib >= n_seq) continue;
-            const int64_t la = seq_off[ia + 1] - seq_off[ia], lb = seq_off[ib + 1] - seq_off[ib];
-            if (a_start[p] < 0 || a_end[p] < a_start[p] || a_end[p] > la || b_start[p] < 0 || b_end[p] < b_start[p] || b_end[p] > lb) continue;
-            const int64_t m = a_end[p] - a_start[p], n = b_end[p] - b_start[p];
-            if (m < 1 || n < 1 || m > HITE_PAIRHSP_MAX_LEN || n > HITE_PAIRHSP_MAX_LEN) continue;
+            int64_t m, n;
+            if (!interval_pair_ok(n_seq, seq_off, a_id[p], a_start[p], a_end[p], b_id[p], b_start[p], b_end[p], 1, HITE_PAIRHSP_MAX_LEN, &m, &n)) continue;
             status[p] = 0;
             if (batches.empty() || (int64_t)(batches.back().t1 - batches.back().t0) >= batch_pairs || batches.back().bytes + m + n > PH_BATCH_BYTES)
                 batches.push_back(Batch{tasks.size(), tasks.size(), 0, 0});
             Batch &b = batches.back();
             tasks.push_back(PhTask{b.bytes, b.bytes + m, (int32_t)m, (int32_t)n});
-            src.push_back(Src{p, seq_off[ia] + a_start[p], seq_off[ib] + b_start[p]});
+            src.push_back(Src{p, seq_off[a_id[p]] + a_start[p], seq_off[b_id[p]] + b_start[p]});
             b.t1 = tasks.size();
             b.bytes += m + n;
             b.max_m = std::max(b.max_m, (int32_t)m);
         }
         std::vector<std::vector<PhHsp>> found((size_t)n_pair);
         if (!batches.empty()) {
-            struct Plan { size_t table_words; unsigned blocks; size_t need; };
+            struct Plan { size_t table_words; unsigned blocks; };
+            // the device memory of a batch: the bytes of its pairs, its tasks, its records, the tables of its blocks
+            auto layout = [](const Batch &b, const Plan &pl) {
+                const size_t nt = b.t1 - b.t0;
+                return ScratchPlan({{1, (size_t)b.bytes, 16}, {sizeof(PhTask), nt, 0}, {4, nt * PH_OUT_WORDS, 0}, {4, pl.blocks * pl.table_words, 0}});
+            };
             std::vector<Plan> plans;
             size_t need = 0;
             for (const Batch &b : batches) {
@@ -340,8 +337,7 @@ extern "C" int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs,
                 pl.table_words = 3 * slots + (((size_t)b.max_m + 63) & ~(size_t)63);
                 const size_t nt = b.t1 - b.t0;
                 pl.blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nt, PH_MAX_BLOCKS), PH_TABLE_BYTES / (pl.table_words * 4)));
-                pl.need = ph_up((size_t)b.bytes + 16) + ph_up(nt * sizeof(PhTask)) + ph_up(nt * PH_OUT_WORDS * 4) + ph_up(pl.blocks * pl.table_words * 4);
-                need = std::max(need, pl.need);
+                need = std::max(need, layout(b, pl).total);
                 plans.push_back(pl);
             }
             HITE_CHECK(ctx, hipSetDevice(ctx->device));
@@ -355,10 +351,11 @@ extern "C" int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs,
                 const Batch &b = batches[bi];
                 const Plan &pl = plans[bi];
                 const size_t nt = b.t1 - b.t0;
-                uint8_t *d_seq = (uint8_t *)scr;
-                PhTask *d_tasks = (PhTask *)(d_seq + ph_up((size_t)b.bytes + 16));
-                int32_t *d_out = (int32_t *)((uint8_t *)d_tasks + ph_up(nt * sizeof(PhTask)));
-                uint32_t *d_tables = (uint32_t *)((uint8_t *)d_out + ph_up(nt * PH_OUT_WORDS * 4));
+                const ScratchPlan lay = layout(b, pl);
+                uint8_t *d_seq = lay.at<uint8_t>(scr, 0);
+                PhTask *d_tasks = lay.at<PhTask>(scr, 1);
+                int32_t *d_out = lay.at<int32_t>(scr, 2);
+                uint32_t *d_tables = lay.at<uint32_t>(scr, 3);
                 stage.resize((size_t)b.bytes);
                 for (size_t t = b.t0; t < b.t1; t++) {
                     memcpy(stage.data() + tasks[t].q0, seqs + src[t].a0, (size_t)tasks[t].m);

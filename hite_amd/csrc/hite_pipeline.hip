@@ -12,6 +12,7 @@
 // Util.py:10439-10449).  Everything stays in HBM; the host reads back a handful of totals per
 // pass to size the next allocation.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_genome.h"
 #include "hite_scan.h"
 #include "hite_arena.h"
@@ -801,16 +802,6 @@ extern "C" int hite_flank_region_align_dev(hite_ctx *ctx, void **state_io, int32
 }
 
 // host-buffer wrapper (numpy callers / the drop-in scripts): uploads, runs, downloads
-struct PBuf {
-    void *p = nullptr;
-    ~PBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    hipError_t up(const void *h, size_t n) {
-        hipError_t e = alloc(n + 16);
-        if (e != hipSuccess) return e;
-        return n ? hipMemcpy(p, h, n, hipMemcpyHostToDevice) : hipSuccess;
-    }
-};
 __global__ void fold_bytes_kernel(uint8_t *__restrict__ p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = fold_sym(p[i]);
 }
@@ -823,7 +814,7 @@ extern "C" int hite_flank_region_align_clip(hite_ctx *ctx, int32_t te_type, int3
     if (!ctx || n_cand < 0 || !cand || !cand_off || !copy_first || !calls || !cons) return HITE_EINVAL;
     if (n_cand == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    PBuf dc, dco, dcf, dct, ds, de, dm, dcl, dcalls, dcons;
+    DevBuf dc, dco, dcf, dct, ds, de, dm, dcl, dcalls, dcons;
     hipError_t e;
     e = dc.up(cand, cand_off[n_cand]); if (e == hipSuccess) e = dco.up(cand_off, (n_cand + 1) * 8);
     if (e == hipSuccess) e = dcf.up(copy_first, (n_cand + 1) * 4); if (e == hipSuccess) e = dct.up(contig, n_copies * 4);
@@ -912,7 +903,7 @@ extern "C" int hite_fine_rows(hite_ctx *ctx, int32_t n_cand, const uint8_t *cand
     if (win_cap > 0 && !win) return HITE_EINVAL;
     if ((int64_t)copy_first[n_cand] != n_copies) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    PBuf dc, dco, dcf, dct, ds, de, dm, dcl;
+    DevBuf dc, dco, dcf, dct, ds, de, dm, dcl;
     hipError_t e;
     e = dc.up(cand, cand_off[n_cand]); if (e == hipSuccess) e = dco.up(cand_off, (n_cand + 1) * 8);
     if (e == hipSuccess) e = dcf.up(copy_first, (n_cand + 1) * 4); if (e == hipSuccess) e = dct.up(contig, n_copies * 4);

@@ -20,6 +20,7 @@
 // The library index (hite_protein_lib_build): prot_kmer_kernel (bucket of every library 4-mer + bucket counts), a scan of the counts
 // (hite_scan.h) -> the 20^4-bucket directory, and a stable radix sort of (bucket, position) as the fill: entries in position order.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include "hite_arena.h"
 #include "hite_scan.h"
 #include "hite_sort.h"
@@ -470,26 +471,22 @@ extern "C" int hite_translate6(hite_ctx *ctx, int64_t n, const uint8_t *nt, cons
     if (R == 0) return HITE_OK;
     if (!nt || !aa_out) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    uint8_t *d_nt = nullptr, *d_out = nullptr;
-    int64_t *d_off = nullptr, *d_foff = nullptr;
+    DevBuf d_foff, d_off, d_out, d_nt;          // (freed d_nt, d_out, d_off, d_foff)
     std::vector<int64_t> rel(n + 1);
     for (int64_t q = 0; q <= n; q++) rel[q] = nt_off[q] - nt_off[0];
-    hipError_t e = hipMalloc((void **)&d_nt, (size_t)nb + 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)R);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_off, (size_t)(n + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_foff, (size_t)(6 * n + 1) * 8);
-    if (e == hipSuccess) e = hipMemcpy(d_nt, nt + nt_off[0], (size_t)nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_foff, frame_off, (size_t)(6 * n + 1) * 8, hipMemcpyHostToDevice);
+    hipError_t e = d_nt.alloc((size_t)nb + 16);
+    if (e == hipSuccess) e = d_out.alloc((size_t)R);
+    if (e == hipSuccess) e = d_off.alloc((size_t)(n + 1) * 8);
+    if (e == hipSuccess) e = d_foff.alloc((size_t)(6 * n + 1) * 8);
+    if (e == hipSuccess) e = hipMemcpy(d_nt.p, nt + nt_off[0], (size_t)nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_foff.p, frame_off, (size_t)(6 * n + 1) * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(prot_translate_kernel, dim3(prot_grid(R, 256)), dim3(256), 0, nullptr, d_nt, d_off, d_foff, 6 * n, 1, d_out);
+        hipLaunchKernelGGL(prot_translate_kernel, dim3(prot_grid(R, 256)), dim3(256), 0, nullptr, d_nt.as<uint8_t>(), d_off.as<int64_t>(),
+                           d_foff.as<int64_t>(), 6 * n, 1, d_out.as<uint8_t>());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(aa_out, d_out, (size_t)R, hipMemcpyDeviceToHost);
-    if (d_nt) (void)hipFree(d_nt);
-    if (d_out) (void)hipFree(d_out);
-    if (d_off) (void)hipFree(d_off);
-    if (d_foff) (void)hipFree(d_foff);
+    if (e == hipSuccess) e = hipMemcpy(aa_out, d_out.p, (size_t)R, hipMemcpyDeviceToHost);
     HITE_CHECK(ctx, e);
     return HITE_OK;
 }

@@ -18,6 +18,7 @@
 // 32-bit words, population count) with the bytes before the first and after the last whole word taken one by one.  A wavefront
 // leaves a pair once diff > cutoff * C: n <= C, so the pair cannot match any more.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 #include <vector>
 #include <new>
 
@@ -194,25 +195,14 @@ __global__ __launch_bounds__(64) void sub_resolve_kernel(int r0, int nb, int32_t
     if (lane == 0) *n_lead = L;
 }
 
-static inline size_t sub_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct SubBatch { int a0, a1; int64_t bytes, rows, max_rows; };     // alignments [a0, a1) go up together
 
-// device memory of a batch, carved from the context's scratch
-struct SubLayout {
-    size_t mats, tasks, sub, nsub, leaders, best, bits, total;
-    SubLayout(const SubBatch &b) {
-        size_t at = 0;
-        mats = at; at += sub_up((size_t)b.bytes + 32);
-        tasks = at; at += sub_up((size_t)(b.a1 - b.a0) * sizeof(SubTask));
-        sub = at; at += sub_up((size_t)b.rows * 4 + 4);
-        nsub = at; at += sub_up((size_t)(b.a1 - b.a0) * 4);
-        leaders = at; at += sub_up((size_t)b.max_rows * 4 + 4);
-        best = at; at += sub_up(64 * 4);
-        bits = at; at += sub_up(64 * 8);
-        total = at;
-    }
-};
+// device memory of a batch, carved from the context's scratch: the alignments, the tasks, the sub-cluster of every row, the count of every
+// alignment, the leaders of a chunked alignment, and the best pair / the bit rows of a chunk
+static ScratchPlan sub_layout(const SubBatch &b) {
+    const size_t na = (size_t)(b.a1 - b.a0);
+    return ScratchPlan({{1, (size_t)b.bytes, 32}, {sizeof(SubTask), na, 0}, {4, (size_t)b.rows, 4}, {4, na, 0}, {4, (size_t)b.max_rows, 4}, {4, 64, 0}, {8, 64, 0}});
+}
 
 extern "C" int hite_msa_subcluster(hite_ctx *ctx, int32_t nmat, const int32_t *rows, const int64_t *cols, const int64_t *mat_off,
                                    const uint8_t *mats, double cutoff, const int64_t *row_off, int32_t *sub_of_row, int32_t *n_sub) {
@@ -248,7 +238,7 @@ extern "C" int hite_msa_subcluster(hite_ctx *ctx, int32_t nmat, const int32_t *r
         }
         if (batches.empty()) return HITE_OK;
         size_t need = 0;
-        for (const SubBatch &b : batches) need = std::max(need, SubLayout(b).total);
+        for (const SubBatch &b : batches) need = std::max(need, sub_layout(b).total);
         HITE_CHECK(ctx, hipSetDevice(ctx->device));
         void *scr = nullptr;
         const int rc = hite_scratch_reserve(ctx, need + 256, &scr);
@@ -257,13 +247,12 @@ extern "C" int hite_msa_subcluster(hite_ctx *ctx, int32_t nmat, const int32_t *r
         std::vector<SubTask> tasks, small;
         std::vector<int32_t> h_sub, h_nsub;
         for (const SubBatch &b : batches) {
-            const SubLayout lay(b);
-            uint8_t *base = (uint8_t *)scr;
-            uint8_t *d_mats = base + lay.mats;
-            SubTask *d_tasks = (SubTask *)(base + lay.tasks);
-            int32_t *d_sub = (int32_t *)(base + lay.sub), *d_nsub = (int32_t *)(base + lay.nsub), *d_leaders = (int32_t *)(base + lay.leaders);
-            int32_t *d_best = (int32_t *)(base + lay.best);
-            unsigned long long *d_bits = (unsigned long long *)(base + lay.bits);
+            const ScratchPlan lay = sub_layout(b);
+            uint8_t *d_mats = lay.at<uint8_t>(scr, 0);
+            SubTask *d_tasks = lay.at<SubTask>(scr, 1);
+            int32_t *d_sub = lay.at<int32_t>(scr, 2), *d_nsub = lay.at<int32_t>(scr, 3), *d_leaders = lay.at<int32_t>(scr, 4);
+            int32_t *d_best = lay.at<int32_t>(scr, 5);
+            unsigned long long *d_bits = lay.at<unsigned long long>(scr, 6);
             tasks.clear(); small.clear();
             int64_t row_base = 0;
             for (int a = b.a0; a < b.a1; a++) {

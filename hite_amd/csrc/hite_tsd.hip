@@ -11,6 +11,7 @@
 // replaces the reference's PYTHONHASHSEED-dependent tie order -- and the top 100 are kept.
 // Integer / byte work only; per candidate ~(len+100) bytes in, <= 1.6 KB out: latency bound.
 #include "hite_common.h"
+#include "hite_hostbuf.h"
 
 #define TW 128        // max window length (2*dist+1 <= 101 in every reference call; the entry point takes dist <= 63: 127)
 // Records of one candidate before the cut.  A record belongs to one (k, right position), so at dist 63 (windows of 127): the seven
@@ -161,17 +162,6 @@ __global__ void __launch_bounds__(64) tsd_kmer_kernel(int n, const uint8_t *__re
     if (lane == 0) cnt_out[c] = nr < 100 ? nr : 100;
 }
 
-struct TBuf {
-    void *p = nullptr;
-    ~TBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    hipError_t up(const void *h, size_t n) {
-        hipError_t e = alloc(n + 16);
-        if (e != hipSuccess) return e;
-        return n ? hipMemcpy(p, h, n, hipMemcpyHostToDevice) : hipSuccess;
-    }
-};
-
 extern "C" int hite_tsd_kmer_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_seqs, const int64_t *d_seq_off, int32_t flank,
                                  int32_t plant, int32_t *d_rec_out, int32_t *d_cnt_out, void *stream) {
     if (!ctx || n < 0 || flank < 0 || 2 * flank + 1 > TW) return HITE_EINVAL;
@@ -187,7 +177,7 @@ extern "C" int hite_tsd_kmer(hite_ctx *ctx, int32_t n, const uint8_t *seqs, cons
     if (!ctx || n < 0 || !seqs || !seq_off || !rec_out || !cnt_out) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    TBuf ds, dof, dr, dc;
+    DevBuf ds, dof, dr, dc;
     hipError_t e = ds.up(seqs, seq_off[n]);
     if (e == hipSuccess) e = dof.up(seq_off, (n + 1) * 8);
     if (e == hipSuccess) e = dr.alloc((size_t)n * 100 * 16);
@@ -349,7 +339,7 @@ extern "C" int hite_nonltr_prep(hite_ctx *ctx, int32_t n, const uint8_t *seqs, c
     if (!ctx || n < 0 || (n > 0 && (!seqs || !seq_off || !out)) || flank < 0 || win5 < 0 || win5 > 25) return HITE_EINVAL;
     if (n == 0) return HITE_OK;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    TBuf ds, dof, dout;
+    DevBuf ds, dof, dout;
     hipError_t e = ds.up(seqs, seq_off[n]);
     if (e == hipSuccess) e = dof.up(seq_off, (size_t)(n + 1) * 8);
     if (e == hipSuccess) e = dout.alloc((size_t)n * 48);
