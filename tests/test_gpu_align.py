@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from align_check import check_pairs, check_pairs_once, pair_matrix  # noqa: F401  (the checker, shared with test_gpu_align_limits.py)
 from test_align_oracle import make_pair, mutate, rnd
 
 pytestmark = pytest.mark.gpu
@@ -20,83 +21,18 @@ def ctx():
     c.close()
 
 
-def pair_matrix(a, b, ops):
-    """2 x cols alignment from the ops of one pair (insertion blocks left-justified, as the star layout does)"""
-    rows = ([], [])
-    nxt = 0
-    for p in range(len(a)):
-        q, gap = int(ops[p]) & 0x7FFF, int(ops[p]) >> 15
-        for x in range(nxt, q):
-            rows[0].append(ord("-"))
-            rows[1].append(b[x])
-        rows[0].append(a[p])
-        if gap:
-            rows[1].append(ord("-"))
-            nxt = q
-        else:
-            rows[1].append(b[q])
-            nxt = q + 1
-    for x in range(nxt, len(b)):
-        rows[0].append(ord("-"))
-        rows[1].append(b[x])
-    return np.array(rows, dtype=np.uint8)
-
-
-def check_pairs(ctx, pairs, cap):
-    """pairs: list of (a, b) uint8 arrays; runs them as two-row groups with exact_cap = cap -- three times: through the
-    thread-per-pair kernels alone, with EVERY pair in the lane-parallel kernels (hite_align_lanes; 4 / 8 lanes per pair in the
-    forward passes, a wavefront per pair in the traceback), and with the two kinds side by side"""
-    res = []
-    for lanes in (-2, 0, 400):
-        ctx.align_lanes(lanes)
-        try:
-            res.append(check_pairs_once(ctx, pairs, cap))
-        finally:
-            ctx.align_lanes(-1)
-    assert res[0] == res[1] == res[2]
-    return res[0]
-
-
-def check_pairs_once(ctx, pairs, cap):
-    ctx.align_config(cap)
-    prev = O.set_align_exact(cap)
-    try:
-        groups = [[bytes(a), bytes(b)] for a, b in pairs]
-        got, info = ctx.star_msa(groups, info=True)
-        n_cert = n_opt = n_drop = 0
-        for (a, b), m, inf in zip(pairs, got, info):
-            ops, ti = O.align_pair(a, b, cap)
-            U, cert, status, kst, nw = (int(x) for x in inf[1])
-            assert (U, cert, status, kst, nw) == (ti["U"], ti["cert"] if ti["status"] != 2 else 0, ti["status"], ti["kstar"], ti["nw"]), (inf[1], ti)
-            if ops is None:
-                n_drop += 1
-                assert m is not None and m.shape[0] == 1 and bytes(m[0]) == bytes(a)
-                continue
-            exp = pair_matrix(a, b, ops)
-            assert m is not None and m.shape == exp.shape and np.array_equal(m, exp)
-            gap = (m[0] == ord("-")) | (m[1] == ord("-"))
-            cost = 3 * int(gap.sum()) + int(((m[0] != m[1]) & ~gap).sum()) + int(((m[0] == m[1]) & ~np.isin(m[0], list(b"ACGT"))).sum())
-            assert cost == U
-            d = O.nw_distance(a, b)
-            assert U >= d
-            n_opt += U == d
-            if cert:
-                n_cert += 1
-                nops, nd = O.nw_pair(a, b)
-                assert U == nd and np.array_equal(m, pair_matrix(a, b, nops))
-        return n_cert, n_opt, n_drop
-    finally:
-        O.set_align_exact(prev)
-        ctx.align_config(8)
-
-
 def test_align_families_all_modes(ctx):
+    """random families of 60 - 900 columns, every kernel mix at every cap.  All 160 pairs are certified by the 4-word band, so the four
+    caps run the SAME work -- the 4-word forward kernels and the traceback: no wider level, no fall-back.  The caps differ only in
+    the schedule around that work (at 16 and 32 the lists of the overlap path are built and found empty).  The wider levels, the
+    certificate's and the schedule's thresholds and the fall-back are reached by test_gpu_align_limits.py."""
     rng = np.random.default_rng(7001)
     pairs = [make_pair(rng, int(rng.integers(60, 900))) for _ in range(160)]
     for cap in (0, 8, 16, 32):
-        n_cert, n_opt, n_drop = check_pairs(ctx, pairs, cap)
+        n_cert, n_opt, n_drop, classes = check_pairs(ctx, pairs, cap)
+        assert set(classes) == {(4, 0, 1)}         # (what the docstring says; measured with the twin)
         assert n_drop == 0
-        assert n_opt >= 0.98 * len(pairs)          # these families hardly ever need more than the narrow band
+        assert n_opt >= 0.98 * len(pairs)          # these families never need more than the narrow band
         if cap >= 16:
             assert n_cert >= 0.9 * len(pairs)
 
@@ -105,7 +41,7 @@ def test_align_long_indels_exact(ctx):
     """65-400 bp insertions / deletions: certified == textbook optimum; the fast mode may be worse, never certified wrongly"""
     rng = np.random.default_rng(7002)
     pairs = [make_pair(rng, int(rng.integers(500, 900)), big_indel=int(rng.integers(65, 401))) for _ in range(60)]
-    n_cert, n_opt, n_drop = check_pairs(ctx, pairs, 32)
+    n_cert, n_opt, n_drop, _ = check_pairs(ctx, pairs, 32)
     assert n_drop == 0 and n_cert >= 0.8 * len(pairs) and n_opt >= n_cert
     check_pairs(ctx, pairs, 0)
     check_pairs(ctx, pairs, 16)
@@ -126,7 +62,7 @@ def test_align_ragged_and_edge(ctx):
     pairs.append((s, t))
     pairs.append((t, s))
     for cap in (0, 16):
-        n_cert, n_opt, n_drop = check_pairs(ctx, pairs, cap)
+        n_cert, n_opt, n_drop, _ = check_pairs(ctx, pairs, cap)
         assert n_drop >= 3       # (7, 1), (130, 64)-like rows shorter than half the centre are dropped
 
 
