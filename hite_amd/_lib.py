@@ -532,6 +532,33 @@ class Context:
         rows, at = recs[:n_out.value].tolist(), first.tolist()
         return [None if status[p] < 0 else [tuple(r) for r in rows[at[p]:at[p + 1]]] for p in range(n)]
 
+    # ---- LTR candidate scan (where FiLTR runs LtrDetector, HiTE's other branch gt ltrharvest + LTR_FINDER) -------------------
+    LTR_SCAN_STATS = ("words", "hits", "runs", "runs_span", "alignments", "redos", "no_hsp", "drop_ltr", "drop_len", "drop_overlap",
+                      "drop_identity", "records")
+
+    def ltr_scan(self, seqs, min_len=400, max_len=22000, min_ltr=100, max_ltr=6000, identity=85, stats=None, cap=1 << 14):
+        """seqs: str / bytes -> int32 [n, 8]: (seq, ls, le, rs, re, score, matches, columns) of the LTR candidate scan that
+        include/hite_gpu.h defines ("LTR candidate scan"; hite_ltr_scan): [ls, le) and [rs, re) are the two terminals, 0-based and
+        half-open on the plus strand, ordered by (seq, ls, re, le, rs).  The defaults are LtrDetector's.  A result beyond `cap`
+        records is asked again with the room it reported.  stats (a dict): the counters of this call (LTR_SCAN_STATS)."""
+        buf, off = self._csr(seqs)
+        room = int(cap)
+        while True:
+            recs = np.zeros((max(room, 1), 8), dtype=np.int32)
+            n_out = C.c_int64(0)
+            st = np.zeros(len(self.LTR_SCAN_STATS), dtype=np.int64)
+            rc = self.lib.hite_ltr_scan(self.h, C.c_int64(len(off) - 1), _p(buf), _p(off), C.c_int32(int(min_len)), C.c_int32(int(max_len)),
+                                        C.c_int32(int(min_ltr)), C.c_int32(int(max_ltr)), C.c_int32(int(identity)), C.c_int64(room), _p(recs),
+                                        C.byref(n_out), _p(st))
+            if rc == -4 and n_out.value > room:       # HITE_ECAP: now the room is known
+                room = n_out.value
+                continue
+            self._check(rc, "hite_ltr_scan")
+            break
+        if stats is not None:
+            stats.update(zip(self.LTR_SCAN_STATS, (int(v) for v in st)))
+        return np.ascontiguousarray(recs[:n_out.value])
+
     # ---- Helitron candidate scan (multi_process_helitronscanner, Util.py:263: HelitronScanner.jar) ---------------------------
     def _helitron_args(self, seqs, head_patterns, tail_patterns):
         buf, off = self._csr(seqs)

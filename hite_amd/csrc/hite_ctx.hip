@@ -43,6 +43,10 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
         const long long v = strtoll(e, nullptr, 10);
         if (v >= 1 && v <= ((long long)1 << 24)) c->pairhsp_batch_pairs = (int64_t)v;
     }
+    if (const char *e = getenv("HITE_LTRSCAN_BATCH_BYTES")) {           // test knob of hite_ltr_scan (hite_ltrscan.hip)
+        const long long v = strtoll(e, nullptr, 10);
+        if (v >= 1 && v <= ((long long)1 << 30)) c->ltrscan_batch_bytes = (int64_t)v;
+    }
     if (hipSetDevice(device_id) != hipSuccess) { free(c); return HITE_EHIP; }
     *out = c;
     return HITE_OK;

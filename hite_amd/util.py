@@ -2419,3 +2419,63 @@ def ltr_scn_filter(scn_file, reference, out_dir, ctx=None, hsps=None, seconds=No
     lap("flank_align")
     left_LTR_contigs, _map = left_ltr_terminals(filter_terminal_align_scn, ref_contigs, log)
     return filter_terminal_align_scn, dirty_dicts, left_LTR_contigs
+
+
+# ---- the LTR candidate table itself (where FiLTR runs LtrDetector: main.py:135-156; HiTE's other branch gt ltrharvest + LTR_FINDER) --
+# In-tree stage, PARITY UNPINNED against the three tools: what is computed is the "LTR candidate scan" of include/hite_gpu.h
+# (Context.ltr_scan), held to its CPU twin.  scan= replaces the scan (the signature of Context.ltr_scan; the CPU tests pass the twin).
+def ltr_scn_lines(records, names):
+    """the candidate lines of scan records (seq, ls, le, rs, re, score, matches, columns; 0-based, half-open): the twelve
+    space-separated fields the reference's convert_LtrDetector_scn writes (bin/FiLTR-main/src/Util.py:9131) -- start, end and length
+    of the element, of the left and of the right terminal (1-based, inclusive), the identity of the terminals (100 * matches /
+    columns, two decimals), `NA` as seq_id, the chromosome name"""
+    lines = []
+    for seq, ls, le, rs, re_, _score, matches, columns in records:
+        fields = (ls + 1, re_, re_ - ls, ls + 1, le, le - ls, rs + 1, re_, re_ - rs, "%.2f" % (100.0 * matches / columns), "NA", names[seq])
+        lines.append(" ".join(str(x) for x in fields))
+    return lines
+
+
+def ltr_candidate_scan(reference, scn_file, ctx=None, scan=None, **limits):
+    """genome in, `.scn` candidate table out: reference is a FASTA path or {name: sequence}; the scan (Context.ltr_scan, or scan=) runs
+    on all sequences in one call with LtrDetector's default limits unless given (min_len, max_len, min_ltr, max_ltr, identity; also
+    stats=, cap=); scn_file receives a `#` header line and one line per record (ltr_scn_lines), in the order of the records: by
+    chromosome in the order of the reference, then by start.  -> the lines"""
+    if isinstance(reference, dict):
+        names, contigs = list(reference), reference
+    else:
+        names, contigs = read_fasta(reference)
+    scan = scan or (ctx or get_ctx()).ltr_scan
+    records = scan([contigs[n] for n in names], **limits)
+    lines = ltr_scn_lines([[int(v) for v in r] for r in records], names)
+    with open(scn_file, "w") as f_save:
+        f_save.write("# hite_ltr_scan: start end len lLTR_start lLTR_end lLTR_len rLTR_start rLTR_end rLTR_len similarity seq_id chr\n")
+        for line in lines:
+            f_save.write(line + "\n")
+    return lines
+
+
+def ltr_detect(reference, out_dir, flanking_len=100, max_copy_num=100, ctx=None, scan=None, hsps=None, cluster=None, frame_vote=None,
+               seconds=None):
+    """FiLTR from the genome to the is_LTR table, in-tree: ltr_candidate_scan -> out_dir/total.scn, ltr_scn_filter (steps 1 and 2) ->
+    out_dir/filter_terminal_align.scn and the left terminals, ltr_flank_filter (step 3) -> the is_LTR table;
+    out_dir/confident_ltr.scn receives the lines of filter_terminal_align.scn whose left terminal step 3 kept.  reference is a FASTA
+    path.  The reference is NOT cut into pieces of 10 Mb as FiLTR cuts it for LtrDetector: the scan has no such limit, so an element
+    that lies across such a cut is found.  scan / hsps / cluster / frame_vote replace the device stages (the signatures of
+    Context.ltr_scan, .pair_hsps, .frame_cluster, .ltr_frame); seconds: a dict that receives the wall seconds of every step.
+    -> (path of confident_ltr.scn, {chr-start-end of a left terminal: (is_ltr, "low" | "high" | None, dropped_by)})"""
+    os.makedirs(out_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    total_scn = os.path.join(out_dir, "total.scn")
+    ltr_candidate_scan(reference, total_scn, ctx=ctx, scan=scan)
+    if seconds is not None:
+        seconds["scan"] = time.perf_counter() - t0
+    final_scn, _dirty, terminals = ltr_scn_filter(total_scn, reference, out_dir, ctx=ctx, hsps=hsps, seconds=seconds)
+    table, _high = ltr_flank_filter(terminals, reference, flanking_len, max_copy_num, ctx=ctx, cluster=cluster, frame_vote=frame_vote,
+                                    seconds=seconds)
+    _ref_names, ref_contigs = read_fasta(reference)
+    _terminals, candidate_of = left_ltr_terminals(final_scn, ref_contigs)
+    _candidates, lines = read_scn(final_scn, None)
+    confident_scn = os.path.join(out_dir, "confident_ltr.scn")
+    store_scn([lines[candidate_of[name]] for name in candidate_of if table.get(name, (False,))[0]], confident_scn)
+    return confident_scn, table

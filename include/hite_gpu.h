@@ -515,6 +515,73 @@ int hite_pair_hsps(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs, const int6
                    int32_t diag_min, int64_t cap, int32_t *status /* n_pair: count or -1 */, int64_t *first /* n_pair + 1 */,
                    int32_t *recs /* cap x 7 */, int64_t *n_out);
 
+/* ---- LTR candidate scan --- the `.scn` candidate table FiLTR gets from the vendored LtrDetector (main.py:135-156 through
+ * Reproduction/run_LtrDetector_parallel.py and convert_LtrDetector_scn) and HiTE's other branch from `gt ltrharvest` and LTR_FINDER
+ * (Util.py:569-667).  In-tree stage, genome in, candidate pairs of direct repeats out.  PARITY UNPINNED against LtrDetector /
+ * LTR_harvest / LTR_FINDER (no machine of the project has any of them, and none of their text is here): what is computed is the
+ * definition below, its CPU twin tests/ltrscan_twin.py + tests/ltrscan_twin.c, HIP == twin record for record and counter for
+ * counter; the stage is measured on planted truth (profiles/r13_ltr_scan.txt).  Stated deviations: a position links to its nearest
+ * admissible copy only; words of 13 bases; alignments live in a band of 192 diagonals; no TSD, TG..CA motif or PPT test.
+ *
+ * The input is a CSR batch of byte sequences.  Bytes are read as A C G T in either case; any other byte is in no word and matches
+ * nothing.  Positions are 0-based inside their sequence; len is the length of the sequence at hand.
+ *  1. Words.  Position i has a word when s[i, i+13) is all ACGT (HITE_LTRSCAN_WORD).
+ *  2. Links.  dmin = min_ltr, dmax = max_len - min_ltr.  For a position i with a word, the next HITE_LTRSCAN_MAX_OCC later
+ *     occurrences of the same word in the same sequence are looked at by ascending position; the first j with j - i >= dmin is
+ *     taken, and (seq, i, d = j - i) is a hit iff d <= dmax.  A position gives at most one hit.
+ *  3. Runs, on two lattices lambda = 0 and 32.  The bin of a hit is (d + lambda) >> 6.  With the hits ordered by (seq, bin, i), a
+ *     run is a maximal chain of consecutive hits with equal (seq, bin) and i - i_prev <= HITE_LTRSCAN_GAP; it counts from
+ *     HITE_LTRSCAN_MIN_HITS hits on and is (seq, i_lo, i_hi, d_lo, d_hi) (first and last i, smallest and largest d).  A run with
+ *     i_hi - i_lo + 13 > max_ltr is dropped.  The runs of both lattices go on (step 6 removes what they find twice).
+ *  4. Extension, per run.  dc = (d_lo + d_hi) >> 1.  The pads PL and PR each walk through the four values min(256, max_ltr),
+ *     min(1024, max_ltr), min(4096, max_ltr), max_ltr, starting at the first.
+ *        Q = [max(0, i_lo - PL), min(len, i_hi + 13 + PR)),  S = [max(0, Q.begin + dc - 96), min(len, Q.end + dc + 96)).
+ *     The alignment is step 4 of hite_pair_hsps as it stands (the same cell tuple, 2 / -4 / -5, the same "best", the same best-cell
+ *     tie rule) with Q as rows and S as columns, on the whole rectangle Q x S inside the band dc - 96 <= y - x <= dc + 95 (x, y:
+ *     positions in the sequence); its result is an HSP at score >= HITE_PAIRHSP_MIN_SCORE, [ls, le) in Q and [rs, re) in S.  No
+ *     HSP: the run gives nothing.  If ls - Q.begin < HITE_LTRSCAN_EDGE while Q.begin > 0 and PL is not at its fourth value, PL
+ *     steps to its next value; if Q.end - le < HITE_LTRSCAN_EDGE while Q.end < len and PR is not at its fourth value, PR steps.
+ *     If either stepped and fewer than HITE_LTRSCAN_MAX_REDO alignments have been redone, the alignment is redone.
+ *  5. Filters, integers only, in this order; a record is counted at the first it fails:
+ *        min_ltr <= le - ls <= max_ltr and min_ltr <= re - rs <= max_ltr;   min_len <= re - ls <= max_len;   le <= rs;
+ *        100 * matches >= identity * columns.
+ *  6. Order and duplicates.  Records are ordered by (seq, ls, re, le, rs, -score, -matches, columns); the first of every
+ *     (seq, ls, le, rs, re) is kept.
+ *  Record: eight int32 -- seq, ls, le, rs, re (0-based, half-open, plus strand: direct repeats need no minus-strand pass), score,
+ *  matches, columns.  The caller passes the limits; LtrDetector's defaults are 400 / 22 000 / 100 / 6 000 / 85.
+ *
+ * Limits: 1 <= min_ltr <= max_ltr <= HITE_LTRSCAN_MAX_LTR (a window then stays under the 32 768 the packed start coordinates of a
+ * cell hold), min_len <= max_len, identity in 1 .. 100, every sequence shorter than 2^31: anything else, a negative count, a missing
+ * buffer or descending offsets is HITE_EINVAL.  n = 0, empty sequences and sequences shorter than a word are valid and give nothing.
+ * recs holds cap records; *n_out is the number of records of the call, HITE_ECAP when cap is smaller (the first cap are written).
+ * stats (may be NULL) receives HITE_LTRSCAN_STATS counters: positions with a word, hits, runs that count (both lattices), of these
+ * dropped for their span, alignments run, of these redone, runs without an HSP, records dropped by each of the four filters of
+ * step 5, records.
+ * Whole sequences go to the device in batches of bounded bytes; a sequence is never split (one longer than the bound is a batch of
+ * its own).  Device memory of a batch: 33 bytes per base (the bases, 8 + 4 for the word keys and positions, as much again for the
+ * sort, 8 for the hits), 34 bytes per hit while the runs are formed (a position gives at most one hit) and 40 per run that is
+ * aligned; the default bound of 64 MiB of bases is 2.1 GiB (4.4 GiB if every position had a hit), which fits beside a resident
+ * genome.  $HITE_LTRSCAN_BATCH_BYTES, read by hite_ctx_create,
+ * sets another bound: a test knob that never changes a result. */
+#define HITE_LTRSCAN_WORD       13
+#define HITE_LTRSCAN_MAX_OCC    16
+#define HITE_LTRSCAN_BIN_SHIFT  6
+#define HITE_LTRSCAN_LATTICE    32
+#define HITE_LTRSCAN_GAP        100
+#define HITE_LTRSCAN_MIN_HITS   4
+#define HITE_LTRSCAN_BAND_BELOW 96
+#define HITE_LTRSCAN_BAND_ABOVE 96
+#define HITE_LTRSCAN_PAD_0      256
+#define HITE_LTRSCAN_PAD_1      1024
+#define HITE_LTRSCAN_PAD_2      4096
+#define HITE_LTRSCAN_EDGE       32
+#define HITE_LTRSCAN_MAX_REDO   3
+#define HITE_LTRSCAN_MAX_LTR    8192
+#define HITE_LTRSCAN_STATS      12
+int hite_ltr_scan(hite_ctx *ctx, int64_t n, const uint8_t *seqs, const int64_t *seq_off,
+                  int32_t min_len, int32_t max_len, int32_t min_ltr, int32_t max_ltr, int32_t identity /* percent */,
+                  int64_t cap, int32_t *recs /* cap x 8 */, int64_t *n_out, int64_t *stats);
+
 /* ---- Helitron candidate scan --- multi_process_helitronscanner  Util.py:263 (third-party HelitronScanner.jar: scanHead, scanTail,
  * pairends, draw -pure_helitron per 50 kb part of longest_repeats_{i}.flanked.fa; judge_Helitron_transposons.py:27-34) -------------
  * In-tree stage, not pinned to the tool (no machine of the project runs it, and the tool's pairing rule and the tie-breaks of its
