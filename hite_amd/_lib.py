@@ -88,6 +88,18 @@ class Context:
         process-wide setting again (hite_copy_config; HITE_COPY_INTERVAL = aligned | whole, else the default)"""
         self._check(self.lib.hite_copy_config_ctx(self.h, -1 if aligned_interval is None else int(bool(aligned_interval))), "hite_copy_config_ctx")
 
+    def fill_config(self, tiles):
+        """which form of the sparse fill THIS context runs (include/hite_gpu.h hite_fill_config_ctx): True = tiles of positions built in
+        LDS (the default), False = the per-cell form, None = follow the process default again (HITE_FILL_TILES=0: the per-cell form).
+        Both write the same bytes."""
+        self._check(self.lib.hite_fill_config_ctx(self.h, -1 if tiles is None else int(bool(tiles))), "hite_fill_config_ctx")
+
+    def fill_tile_limits(self):
+        """(positions of a tile, window-range bytes that fit the LDS slot, rows of a workgroup per trip, row slices) of the tile form"""
+        out = (C.c_int32 * 4)()
+        self._check(self.lib.hite_fill_tile_limits(out), "hite_fill_tile_limits")
+        return tuple(out)
+
     def release_copy_index(self):
         """drops the minimizer index of the packed genome (device memory is freed); the next copy / seeding call rebuilds it"""
         if getattr(self, "_copy_state", None) is not None and getattr(self, "h", None):

@@ -68,6 +68,8 @@ struct hite_ctx {
     const int32_t *d_msa_rows_eff;  // per candidate: rows that were aligned (NULL: all)
     uint32_t *d_msa_lay;             // layout words of the last sparse star alignment (hite_msa.hip)
     int msa_long;                    // the last star alignment held windows of more than 1 536 bases (the fill's unroll)
+    int msa_max_len;                 // its longest window (the tile form's grid)
+    int32_t fill_tiles;              // hite_fill_config_ctx: 1 the tile form of the sparse fill / 0 the per-cell form / -1 the process default
     const int64_t *d_msa_win_off;    // per row of the last star alignment: its window, and where its back pads begin (HITE_IS_ROW_PAD;
     const int32_t *d_msa_win_len;    // layout, fill and the judge's LDS kernels read the rows through these)
     const uint32_t *d_msa_pads;      // per row: pad bytes in front | behind << 16

@@ -25,6 +25,7 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
     if (!c) return HITE_ENOMEM;
     c->device = device_id;
     c->copy_interval = -1;
+    c->fill_tiles = -1;
     // test knobs of hite_msa_subcluster (hite_subcluster.hip), read here so that two contexts of a process may differ
     c->subcluster_chunk = HITE_SUBCLUSTER_CHUNK;
     if (const char *e = getenv("HITE_SUBCLUSTER_CHUNK_ROWS")) {

@@ -14,6 +14,7 @@
 #include "hite_align.h"
 #include "hite_scan.h"
 #include "hite_fill.h"
+#include "hite_fill_tile.h"
 
 #define MSA_MAXR 128   // rows whose lengths are cached in LDS by the layout / fill kernels
 
@@ -403,6 +404,131 @@ __global__ void __launch_bounds__(256) star_fill_sparse_kernel(FillSparseParams 
     }
 }
 
+// The tile form of the same fill (hite_fill_tile.h): grid (candidate, tile of FT_T positions, row slice); a wavefront takes ONE tile
+// and walks the rows of its slice, the layout words of its positions in registers over all of them (with FT_ROWS > 1 the
+// wavefronts of a workgroup take different rows of the tile).  A wavefront runs three rows deep: the ops of the row after next and
+// the window range of the next row are requested before the current row goes from its registers through the LDS slot and the
+// image to the output row -- one dependent level per (row, tile), and nothing in a step waits for what the step itself requested.
+// No workgroup barrier anywhere: a wavefront owns its slot and its image.  What a wavefront pays once per tile (layout words, the
+// windows of its rows, two rows to fill the pipeline) is five round trips: the more rows it walks the better -- C3, both passes,
+// ms per step: 4 wavefronts x 4 / 2 / 1 slices 10.4 / 7.5 / 5.6, 2 x 2 5.3, 2 x 1 4.4, 1 x 1 4.2 (profiles/r14_fill_tiles.txt).
+#ifndef FT_GRID_Z
+#define FT_GRID_Z 1                      // row slices of a candidate: a workgroup takes the rows FT_ROWS z + wave, + FT_ROWS FT_GRID_Z, ...
+#endif
+#define FT_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+__global__ void __launch_bounds__(64 * FT_ROWS) star_fill_tile_kernel(FillSparseParams Q) {
+    const FillParams &P = Q.F;
+    const int c = blockIdx.x;
+    if (c >= P.n) return;
+    const int C = P.cols[c];
+    if (C <= 0 || (Q.cls && Q.cls[c] >= JUDGE_CLS_LDS)) return;
+    const int64_t g0 = P.row_first[c];
+    const int m = P.win_len[g0];
+    const int P0 = (int)blockIdx.y * FT_T;                     // first position of the tile
+    if (P0 > m) return;
+    const int R = msa_rows(P.rows_eff, P.row_first, c);
+    const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int step = FT_ROWS * (int)gridDim.z;
+    int r = (int)blockIdx.z * FT_ROWS + wave;
+    if (r >= R) return;
+    const uint16_t *ops = P.ops + P.ops_base[c];
+    const uint32_t *lay = Q.lay + (P.ops_base[c] >> 1);
+    const int le = Q.last_extra[c];
+    uint8_t *out = P.msa + P.msa_off[c];
+    const int64_t rs = m + 1;
+    const int pl = min(P0 + FT_T - 1, m);                      // last position of the tile
+    const int p0 = P0 + lane * FT_NP;
+    uint32_t w[FT_NP];
+#pragma unroll
+    for (int u = 0; u < FT_NP; u++) {
+        const int p = p0 + u;
+        const uint32_t wl = lay[p <= m ? p : m];
+        w[u] = p <= m ? wl : 0u;
+    }
+    int c0, W;
+    const bool tile_ok = ft_tile_plan(lay[P0], lay[pl < m ? pl + 1 : m], pl == m, C, &c0, &W);
+    __shared__ FtV16 s_slot[FT_ROWS][FT_LDS / 16], s_img[FT_ROWS][FT_LDS / 16];
+    uint8_t *slot = (uint8_t *)s_slot[wave], *img = (uint8_t *)s_img[wave];
+
+    // the windows of the wavefront's rows: lane i looks up the i-th of them once (row_map -> win_off / win_len are two dependent
+    // round trips); a row then takes its two values from that lane.  64 rows of the wavefront at a time: the loop around everything
+    int Rc = 0;                          // rows below Rc have their windows in the lanes
+  for (; r < R; ) {
+    Rc = min(R, r + 64 * step);
+    // (the ops of the first two rows are requested before the windows are looked up: they need the row numbers alone)
+    FtOps S0 = ft_ops_load(ops + r * rs, p0, m, r == 0, r == 0), S1, S2 = {};
+    S1 = ft_ops_load(ops + min(r + step, Rc - 1) * rs, p0, m, false, min(r + step, Rc - 1) == 0);
+    int64_t my_off = 0;
+    int my_len = 0;
+    if (r + lane * step < R) { const int s = msa_src(P.row_map, g0, r + lane * step); my_off = P.win_off[g0 + s]; my_len = P.win_len[g0 + s]; }
+    struct RowWin { const uint8_t *b; int n; };
+    auto row_win = [&](int i) -> RowWin {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(my_off & 0xffffffff), i), hi = (unsigned)__builtin_amdgcn_readlane((int)(my_off >> 32), i);
+        return RowWin{P.win + (int64_t)(((uint64_t)hi << 32) | lo), __builtin_amdgcn_readlane(my_len, i)};
+    };
+    // the plan of a row that is still ahead, and the request for its window range
+    struct RowPlan { const uint8_t *b; int n, qa, len; bool ok; };
+    auto plan_row = [&](const FtOps &L, int i, int rr, FtV16 *v) -> RowPlan {
+        RowPlan pr;
+        const RowWin rw = row_win(i);
+        pr.b = rw.b; pr.n = rw.n;
+        const unsigned tprev = (unsigned)__builtin_amdgcn_readfirstlane((int)L.oprev);
+        const unsigned tlast = (unsigned)__builtin_amdgcn_readlane((int)ft_lane_op(L, (pl - P0) % FT_NP), (pl - P0) / FT_NP);
+        const bool ok = ft_row_plan(tprev, tlast, P0, pl, m, pr.n, rr == 0, &pr.qa, &pr.len) && tile_ok;
+        pr.ok = __builtin_amdgcn_readfirstlane((int)ok) != 0; pr.qa = __builtin_amdgcn_readfirstlane(pr.qa); pr.len = __builtin_amdgcn_readfirstlane(pr.len);
+        ft_win_load(v, pr.b, pr.ok ? pr.qa : 0, pr.ok ? pr.len : 0, lane);     // (always: see ft_win_load)
+        return pr;
+    };
+    // One step: A = the ops of the current row, vA its window range (requested a step ago, plan pa), B = the ops of the next row
+    // (requested two steps ago), N takes the ops of the row after next.  The steps below pass the same registers round in turn:
+    // a copy of B into A at the end of a step would wait for loads that were requested a moment ago.
+    // (a row whose range does not fit is put down in `bad` and done cell by cell behind the loop: its loads and stores, whose number
+    // is not known, would make every step wait for all of its own requests)
+    int i = 0;
+    const int rbase = r;
+    unsigned long long bad = 0;
+    RowPlan pa, pb = {};
+    auto step_row = [&](FtOps &A, FtOps &B, FtOps &N, FtV16 *vA, FtV16 *vB) -> bool {
+        const int rn = r + step, rnn = rn + step;
+        // (behind the wavefront's last row both requests go to that row once more: they are always issued, see ft_win_load)
+        N = ft_ops_load(ops + min(rnn, Rc - 1) * rs, p0, m, false, min(rnn, Rc - 1) == 0);
+        pb = plan_row(B, min(i + 1, 63), min(rn, Rc - 1), vB);
+        uint8_t *row = out + (int64_t)r * C;
+        if (pa.ok) {
+            const int sh = ft_win_shift(pa.b, pa.qa);
+            ft_win_put(slot, vA, ft_win_chunks(sh, pa.len), lane);
+            FT_WAVE_SYNC();
+            ft_cells(img, slot, A, w, p0, m, pa.n, le, r == 0, sh - pa.qa, ft_img_shift(row + c0) - c0);
+            FT_WAVE_SYNC();
+            ft_store(row + c0, img, W, lane);
+            FT_WAVE_SYNC();
+        } else {
+            bad |= 1ull << i;
+        }
+        pa = pb; r = rn; i++;
+        return r < Rc;
+    };
+    FtV16 V0[FT_CH], V1[FT_CH];
+#pragma unroll
+    for (int k = 0; k < FT_CH; k++) V0[k] = V1[k] = FtV16{0, 0, 0, 0};
+    pa = plan_row(S0, 0, r, V0);
+    for (;;) {
+        if (!step_row(S0, S1, S2, V0, V1)) break;
+        if (!step_row(S1, S2, S0, V1, V0)) break;
+        if (!step_row(S2, S0, S1, V0, V1)) break;
+        if (!step_row(S0, S1, S2, V1, V0)) break;
+        if (!step_row(S1, S2, S0, V0, V1)) break;
+        if (!step_row(S2, S0, S1, V1, V0)) break;
+    }
+    while (bad) {
+        const int k = __builtin_ctzll(bad), rr = rbase + k * step;
+        bad &= bad - 1;
+        const RowWin rw = row_win(k);
+        ft_cells_direct(out + (int64_t)rr * C, rw.b, rw.n, ops + rr * rs, lay, m, le, rr == 0, P0, pl + 1, lane);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -531,7 +657,7 @@ static int star_msa_launch(hite_ctx *ctx, int32_t n, const uint8_t *d_win, const
     if (total_rows > 0)
         hipLaunchKernelGGL(row_pad_scan_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, d_win, d_win_off, d_win_len,
                            len2, pads);
-    ctx->d_msa_win_off = d_win_off; ctx->d_msa_win_len = len2; ctx->d_msa_pads = pads; ctx->msa_long = max_win_len > 1536;
+    ctx->d_msa_win_off = d_win_off; ctx->d_msa_win_len = len2; ctx->d_msa_pads = pads; ctx->msa_long = max_win_len > 1536; ctx->msa_max_len = max_win_len;
     MsaParams P;
     P.n = n; P.total_rows = total_rows; P.win = d_win; P.win_off = d_win_off; P.win_len = len2; P.row_first = d_row_first;
     P.ops_base = d_ops_base; P.ops = (uint16_t *)opsb; P.cols_out = d_cols_out; P.status = d_status;
@@ -581,6 +707,30 @@ extern "C" int hite_star_msa_sparse_dev(hite_ctx *ctx, int32_t n, const uint8_t 
                            d_cols_out, d_status, d_new_cols, d_last_extra, d_rows_out, nullptr, stream);
 }
 
+// which form of the sparse fill a context runs: 1 = the tile form (the default), 0 = the per-cell form, -1 = the process default,
+// taken from the environment once (HITE_FILL_TILES=0: the per-cell form)
+static int g_fill_tiles = -1;
+static int fill_tiles_mode(const hite_ctx *ctx) {
+    if (ctx->fill_tiles >= 0) return ctx->fill_tiles;
+    int v = __atomic_load_n(&g_fill_tiles, __ATOMIC_RELAXED);
+    if (v < 0) {
+        const char *e = getenv("HITE_FILL_TILES");
+        v = (e && !strcmp(e, "0")) ? 0 : 1;
+        __atomic_store_n(&g_fill_tiles, v, __ATOMIC_RELAXED);
+    }
+    return v;
+}
+extern "C" int hite_fill_config_ctx(hite_ctx *ctx, int32_t mode) {
+    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
+    ctx->fill_tiles = mode;
+    return HITE_OK;
+}
+extern "C" int hite_fill_tile_limits(int32_t out[4]) {
+    if (!out) return HITE_EINVAL;
+    out[0] = FT_T; out[1] = FT_SLOT; out[2] = FT_ROWS; out[3] = FT_GRID_Z;
+    return HITE_OK;
+}
+
 // compacted alignments (rows x d_new_cols[i] at d_msa_off[i]) from the ops of the last hite_star_msa_sparse_dev call
 extern "C" int hite_star_msa_fill_sparse_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_win, const int64_t *d_win_off,
                                              const int32_t *d_win_len, const int32_t *d_row_first, const int64_t *d_ops_base,
@@ -613,7 +763,13 @@ extern "C" int hite_star_msa_fill_sparse_dev(hite_ctx *ctx, int32_t n, const uin
 #ifndef FILL_U_SHORT
 #define FILL_U_SHORT 4
 #endif
-    if (ctx->msa_long) hipLaunchKernelGGL(HIP_KERNEL_NAME(star_fill_sparse_kernel<FILL_U_LONG>), dim3(n, 4), dim3(256), 0, (hipStream_t)stream, Q);
+    // Round 14: the tile form (star_fill_tile_kernel, hite_fill_tile.h) -- tiles of 512 positions built in LDS by one wavefront that
+    // walks all rows, layout words once per tile, 16-byte loads and stores, ops two rows and the window range one row ahead:
+    // 0.97 + 3.25 ms where the per-cell form above takes 1.68 + 4.96 (profiles/r14_fill_tiles.txt); it is the default.
+    // hite_fill_config_ctx / HITE_FILL_TILES=0 select the per-cell form.
+    if (fill_tiles_mode(ctx) && ctx->msa_max_len > 0)
+        hipLaunchKernelGGL(star_fill_tile_kernel, dim3(n, ctx->msa_max_len / FT_T + 1, FT_GRID_Z), dim3(64 * FT_ROWS), 0, (hipStream_t)stream, Q);
+    else if (ctx->msa_long) hipLaunchKernelGGL(HIP_KERNEL_NAME(star_fill_sparse_kernel<FILL_U_LONG>), dim3(n, 4), dim3(256), 0, (hipStream_t)stream, Q);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(star_fill_sparse_kernel<FILL_U_SHORT>), dim3(n, 4), dim3(256), 0, (hipStream_t)stream, Q);
     HITE_CHECK(ctx, hipGetLastError());
     return HITE_OK;

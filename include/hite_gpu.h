@@ -797,6 +797,13 @@ int hite_star_msa_fill_sparse_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_win
                                   const int32_t *d_win_len, const int32_t *d_row_first, const int64_t *d_ops_base,
                                   const int32_t *d_new_cols, const int32_t *d_last_extra, const int64_t *d_msa_off,
                                   uint8_t *d_msa, void *stream);
+/* The sparse fill has two forms that write the same bytes: tiles of positions built in LDS (the default) and the per-cell form.
+ * mode 1 / 0 selects the tile / per-cell form for this context, -1 follows the process default again (HITE_FILL_TILES=0 in the
+ * environment: the per-cell form).  hite_fill_tile_limits: out[0] = positions of a tile, out[1] = bytes of a row's window range
+ * (and of a tile's output columns) that fit the LDS slot, out[2] = rows a workgroup takes per trip, out[3] = row slices of a
+ * candidate (a workgroup takes the rows out[2] * z + wave, stepping by out[2] * out[3]). */
+int hite_fill_config_ctx(hite_ctx *ctx, int32_t mode);
+int hite_fill_tile_limits(int32_t out[4]);
 
 /* ---- the fine stage in one call --- body of flank_region_align_v5 from the copy table on ----------
  * (Util.py:8095-8194 + run_find_members_v8 :10439 + is_TE_from_align_file :10407).
