@@ -489,6 +489,13 @@ class Context:
                                              int(match), int(mismatch), int(gap_open), int(gap_extend), _p(out)), "hite_itr_search")
         return out
 
+    def itr_limits(self):
+        """(cap on h, largest h with the traceback store in LDS, sequences per workgroup, grid cap on the LDS path, grid cap on the
+        HBM path, columns of a strip) of itr_search_kernel"""
+        out = (C.c_int32 * 6)()
+        self._check(self.lib.hite_itr_limits(out), "hite_itr_limits")
+        return tuple(out)
+
     # ---- pairwise identity (the -c / -A of cd-hit-est -aS 0.95 -aL 0.95 -c <c> -G 0 -g 1 -A 80) ---------------------------
     def pair_identity(self, seqs, pairs, band=32):
         """seqs: str / bytes; pairs: rows (a_id, a_start, a_end, b_id, b_start, b_end, strand), intervals 0-based and half-open, the

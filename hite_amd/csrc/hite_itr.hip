@@ -21,6 +21,9 @@
 #define ITR_LDS_H 64    // up to here the traceback store fits the wavefront's LDS share
 #define ITR_WAVES 4     // wavefronts (sequences in flight) per workgroup
 #define ITR_LDS_TB ((ITR_LDS_H + 63) * 64)
+#define ITR_STRIP 64            // columns of a strip: one per lane
+#define ITR_LDS_BLOCKS (256 * 8)   // grid cap when everything lives in LDS: 8 workgroups on each of 256 CUs
+#define ITR_HBM_BLOCKS 128      // grid cap with the store in HBM: 512 slots of <= 0.3 MB
 
 struct ItrArgs {
     int64_t n;
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(ITR_WAVES * 64) void itr_search_kernel(ItrArgs a) {
                 } else if (dir == 3) {      // gap in seq1: back to the column where this E-gap opened
                     int kk = bj;
                     while (kk >= 1 && !(ITR_TB(bi, kk) & 4)) kk--;
-                    if (kk < 1) { flags |= 1; kk = 1; }   // (a gap run into the matrix edge: see the definition, never seen)
+                    if (kk < 1) { flags |= 1; kk = 1; }   // (a gap run into the matrix edge: see the definition; seen only where gaps are cheap, gap_extend 1 -- tests/itr_limit_cases.py: bands)
                     bj = kk - 1;
                 } else {                    // gap in seq2
                     int kk = bi;
@@ -159,6 +162,12 @@ __global__ __launch_bounds__(ITR_WAVES * 64) void itr_search_kernel(ItrArgs a) {
     }
 }
 
+extern "C" int hite_itr_limits(int32_t out[6]) {
+    if (!out) return HITE_EINVAL;
+    out[0] = ITR_MAX_H; out[1] = ITR_LDS_H; out[2] = ITR_WAVES; out[3] = ITR_LDS_BLOCKS; out[4] = ITR_HBM_BLOCKS; out[5] = ITR_STRIP;
+    return HITE_OK;
+}
+
 extern "C" int hite_itr_search_dev(hite_ctx *ctx, int64_t n, const uint8_t *d_seqs, const int64_t *d_seq_off, int32_t end_len,
                                    int32_t max_h, double min_identity, int32_t min_len, int32_t match, int32_t mismatch,
                                    int32_t gap_open, int32_t gap_extend, int32_t *d_out, void *stream) {
@@ -175,12 +184,12 @@ extern "C" int hite_itr_search_dev(hite_ctx *ctx, int64_t n, const uint8_t *d_se
     size_t lds;
     if (max_h <= ITR_LDS_H) {
         lds = (size_t)ITR_WAVES * (2 * ((ITR_LDS_H + 15) & ~15) + ITR_LDS_TB);
-        if (blocks > 256 * 8) blocks = 256 * 8;
+        if (blocks > ITR_LDS_BLOCKS) blocks = ITR_LDS_BLOCKS;
     } else {
         lds = (size_t)ITR_WAVES * 2 * ((ITR_MAX_H + 15) & ~15);
         const size_t ns = (size_t)(max_h + 63) >> 6;
         a.slot_bytes = (4 * (size_t)(ITR_MAX_H + 1) * 4 + ns * (size_t)(max_h + 63) * 64 + 255) & ~(size_t)255;
-        if (blocks > 128) blocks = 128;     // 512 slots of <= 0.3 MB
+        if (blocks > ITR_HBM_BLOCKS) blocks = ITR_HBM_BLOCKS;
         void *p = nullptr;
         int rc = hite_scratch_reserve(ctx, (size_t)blocks * ITR_WAVES * a.slot_bytes, &p);
         if (rc) return rc;

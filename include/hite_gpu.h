@@ -344,6 +344,10 @@ int hite_itr_search(hite_ctx *ctx, int64_t n, const uint8_t *seqs, const int64_t
 int hite_itr_search_dev(hite_ctx *ctx, int64_t n, const uint8_t *d_seqs, const int64_t *d_seq_off, int32_t end_len, int32_t max_h,
                         double min_identity, int32_t min_len, int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend,
                         int32_t *d_out, void *stream);
+/* the kernel's constants, for the tests at its limits (no GPU is touched): out = { cap on h (500, the tool's own), largest h whose
+ * traceback store lives in LDS, sequences in flight per workgroup, grid cap on the LDS path, grid cap on the HBM path, columns of
+ * a strip } */
+int hite_itr_limits(int32_t out[6]);
 
 /* ---- translated protein search --- get_domain_info  Util.py:4571-4612 (third-party `blastx -evalue 1e-20 -outfmt 6`) -------------
  * The search behind the recall of low-copy candidates by intact protein domains (Util.py:8215-8276; the fragments are chained by

@@ -1432,6 +1432,40 @@ def gen_itr_search(U, tmp):
 
 
 
+def gen_itr_limits(U, tmp):
+    """`itrsearch` ITSELF on the records of tests/itr_limit_cases.py: fixture_cases (a thinned set of the closed-form, seam,
+    alphabet and length cases at the tool's scoring): once as the reference calls it (`-i 0.7 -l 7`, through run_itrsearch) and once
+    with the tool's own defaults written out (`-i 0.8 -l 10`).  Per record: written to <input>.itr or not, "Length itr=", and the
+    ends ITR(1,end1)..(L,p) of the header, end2 = L - p + 1."""
+    import subprocess
+
+    import itr_limit_cases as IC
+
+    trs = _itrsearch_dir(tmp)
+    cases = IC.fixture_cases()
+    seqs = [s for _label, s in cases]
+    runs = []
+    for ident, min_len in IC.FIXTURE_RUNS:
+        d = os.path.join(tmp, "itr_limits_%d" % min_len)
+        os.makedirs(d, exist_ok=True)
+        fa = os.path.join(d, "limits.fa")
+        write_fasta(fa, ["s%d" % k for k in range(len(seqs))], seqs)
+        if (ident, min_len) == (0.7, 7):
+            out, _log = U.run_itrsearch(trs, fa, d)
+        else:
+            with open(fa + ".log", "w") as log:
+                subprocess.run([os.path.join(trs, "itrsearch"), "-i", repr(ident), "-l", str(min_len), fa], cwd=d, stdout=log, check=True)
+            out = fa + ".itr"
+        found = {}
+        for line in open(out):
+            if line.startswith(">"):
+                k = int(line[2:].split(" ")[0])
+                found[k] = [1] + list(IC.parse_itr_header(line, len(seqs[k])))
+        runs.append([found.get(k, [0, -1, 0, 0]) for k in range(len(seqs))])
+        print("itr_limits -i %r -l %d: %d found of %d" % (ident, min_len, len(found), len(seqs)))
+    dump("itr_limits", dict(seqs=seqs, labels=[label for label, _s in cases], runs=runs))
+
+
 def gen_low_copy_rescue(U, tmp):
     """The low-copy recall at the end of flank_region_align_v5 (Util.py:8196-8287) run by the REFERENCE with its tools: `trf` =
     the TRF 4.09 it bundles, `itrsearch` = the ELF it bundles (through remove_no_tirs), get_domain_info / multiple_alignment_blastx_v1
@@ -1571,7 +1605,7 @@ def main():
     assert os.environ.get("PYTHONHASHSEED") == "0", "run with PYTHONHASHSEED=0"
     U = ref_harness.load_reference_util()
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["fmea", "judge", "search", "tsd", "kmer", "gather", "tails", "host", "ltr", "nonltr", "qcopies", "libdedup", "bothends", "split", "bucketing", "consv1", "trf", "rfm", "chainvar", "edge", "itr", "lcr", "fmea_limits", "tsd_limits"]
+    which = sys.argv[1:] or ["fmea", "judge", "search", "tsd", "kmer", "gather", "tails", "host", "ltr", "nonltr", "qcopies", "libdedup", "bothends", "split", "bucketing", "consv1", "trf", "rfm", "chainvar", "edge", "itr", "lcr", "fmea_limits", "tsd_limits", "itr_limits"]
     with tempfile.TemporaryDirectory() as tmp:
         if "fmea" in which:
             gen_fmea(U, tmp)
@@ -1619,6 +1653,8 @@ def main():
             gen_judge_edge(U, tmp)
         if "itr" in which:
             gen_itr_search(U, tmp)
+        if "itr_limits" in which:
+            gen_itr_limits(U, tmp)
         if "lcr" in which:
             gen_low_copy_rescue(U, tmp)
 
