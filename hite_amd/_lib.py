@@ -578,6 +578,37 @@ class Context:
             stats.update(zip(self.LTR_SCAN_STATS, (int(v) for v in st)))
         return np.ascontiguousarray(recs[:n_out.value])
 
+    # ---- genome annotation (where HiTE ends with RepeatMasker: annotate_genome.py:17, pan_annotate_genome.py:27) --------------
+    ANNOTATE_STATS = ("table", "silenced", "too_long", "hits", "runs", "alignments", "redos", "no_hsp", "hsps", "duplicates", "dominated",
+                      "records")
+
+    def annotate(self, seqs, lib, piece_len=0, cap=None, stats=None):
+        """seqs, lib: str / bytes (the genome's sequences, the library's entries) -> (int32 [n, 10], int8 [n_lib]): the records (seq,
+        g_start, g_end, lib, strand, q_start, q_end, score, matches, columns) of the annotation that include/hite_gpu.h defines ("genome
+        annotation"; hite_annotate) -- intervals 0-based and half-open, g on the plus strand of the sequence, q on the entry's forward
+        strand, strand 1: the copy is the entry's reverse complement --, ordered by (seq, g_start, g_end, lib, strand, q_start), and
+        per entry 0 or -1 (longer than HITE_ANNOT_MAX_LIB_LEN: not searched).  piece_len 0: HITE_ANNOT_PIECE.  A result beyond `cap`
+        records is asked again with the room it reported.  stats (a dict): the counters of this call (ANNOTATE_STATS)."""
+        buf, off = self._csr(seqs)
+        lbuf, loff = self._csr(lib)
+        n_lib = len(loff) - 1
+        room = 1 << 14 if cap is None else int(cap)
+        status = np.zeros(max(n_lib, 1), dtype=np.int8)
+        while True:
+            recs = np.zeros((max(room, 1), 10), dtype=np.int32)
+            n_out = C.c_int64(0)
+            st = np.zeros(len(self.ANNOTATE_STATS), dtype=np.int64)
+            rc = self.lib.hite_annotate(self.h, C.c_int64(len(off) - 1), _p(buf), _p(off), C.c_int32(n_lib), _p(lbuf), _p(loff),
+                                        C.c_int32(int(piece_len)), C.c_int64(room), _p(recs), C.byref(n_out), _p(status), _p(st))
+            if rc == -4 and n_out.value > room:       # HITE_ECAP: now the room is known
+                room = n_out.value
+                continue
+            self._check(rc, "hite_annotate")
+            break
+        if stats is not None:
+            stats.update(zip(self.ANNOTATE_STATS, (int(v) for v in st)))
+        return np.ascontiguousarray(recs[:n_out.value]), status[:n_lib].copy()
+
     # ---- Helitron candidate scan (multi_process_helitronscanner, Util.py:263: HelitronScanner.jar) ---------------------------
     def _helitron_args(self, seqs, head_patterns, tail_patterns):
         buf, off = self._csr(seqs)

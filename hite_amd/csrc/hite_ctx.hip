@@ -48,6 +48,10 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
         const long long v = strtoll(e, nullptr, 10);
         if (v >= 1 && v <= ((long long)1 << 30)) c->ltrscan_batch_bytes = (int64_t)v;
     }
+    if (const char *e = getenv("HITE_ANNOT_BATCH_BYTES")) {             // knob of hite_annotate (hite_annotate.hip)
+        const long long v = strtoll(e, nullptr, 10);
+        if (v >= 1 && v <= ((long long)1 << 26)) c->annot_batch_bytes = (int64_t)v;
+    }
     if (hipSetDevice(device_id) != hipSuccess) { free(c); return HITE_EHIP; }
     *out = c;
     return HITE_OK;

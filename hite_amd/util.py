@@ -2479,3 +2479,260 @@ def ltr_detect(reference, out_dir, flanking_len=100, max_copy_num=100, ctx=None,
     confident_scn = os.path.join(out_dir, "confident_ltr.scn")
     store_scn([lines[candidate_of[name]] for name in candidate_of if table.get(name, (False,))[0]], confident_scn)
     return confident_scn, table
+
+
+# ---- the annotation of the genome with the library (where HiTE ends with RepeatMasker: annotate_genome.py:17, pan_annotate_genome.py:27)
+# In-tree stage, PARITY UNPINNED against RepeatMasker: what is computed is the "genome annotation" of include/hite_gpu.h
+# (Context.annotate), held to its CPU twin.  annot= replaces the device stage (the signature of Context.annotate; the CPU tests pass the
+# twin).  The files are written in RepeatMasker's layouts because the reference reads them back (get_full_length_copies_from_gff_v1).
+def annotation_columns(rec, g_len=None, q_len=None):
+    """(mismatches, gaps in the library row, gaps in the genome row) of an annotation record (seq, g_start, g_end, lib, strand, q_start,
+    q_end, score, matches, columns), from the arithmetic of the alignment alone: a column is a match (+2), a mismatch (-4) or a gap (-5),
+    so G = 6 matches - 4 columns - score columns are gaps, X = columns - matches - G are mismatches, the genome interval holds
+    matches + X + (gaps in the library row) bases and the library interval matches + X + (gaps in the genome row)."""
+    g_len = rec[2] - rec[1] if g_len is None else g_len
+    q_len = rec[6] - rec[5] if q_len is None else q_len
+    score, matches, columns = int(rec[7]), int(rec[8]), int(rec[9])
+    gaps = 6 * matches - 4 * columns - score
+    mism = columns - matches - gaps
+    return mism, int(g_len) - matches - mism, int(q_len) - matches - mism
+
+
+def _lib_name_class(header):
+    name, _, cls = header.partition("#")
+    return name, cls or "Unknown"
+
+
+def _publish(path, lines):
+    """a temporary name first, then the rename: a file that exists is complete"""
+    tmp = path + ".tmp"
+    with open(tmp, "w") as f_save:
+        f_save.writelines(lines)
+    os.replace(tmp, path)
+
+
+def _pct(part, whole):
+    return "%.1f" % (100.0 * part / whole if whole else 0.0)
+
+
+def repeatmasker_out_lines(records, ref_names, ref_lens, lib_names, lib_lens):
+    """the lines of write_repeatmasker_out, the three header lines first"""
+    lines = ["   SW   perc perc perc  query     position in query    matching  repeat       position in repeat\n",
+             "score   div. del. ins.  sequence  begin end   (left)   repeat    class/family begin  end    (left)  ID\n", "\n"]
+    for k, rec in enumerate(records):
+        rec = [int(v) for v in rec]
+        seq, gs, ge, lib, strand, qs, qe = rec[:7]
+        mism, gap_lib, gap_genome = annotation_columns(rec)
+        name, cls = _lib_name_class(lib_names[lib])
+        left = "(%d)" % (lib_lens[lib] - qe)
+        repeat = (left, qe, qs + 1) if strand else (qs + 1, qe, left)
+        lines.append("%6d %5s %4s %4s  %s %8d %8d %s %s %s %s %6s %6s %6s %5d\n" % (
+            rec[7], _pct(mism, rec[8] + mism), _pct(gap_genome, ge - gs), _pct(gap_lib, ge - gs), ref_names[seq], gs + 1, ge,
+            "(%d)" % (ref_lens[seq] - ge), "C" if strand else "+", name, cls, repeat[0], repeat[1], repeat[2], k + 1))
+    return lines
+
+
+def write_repeatmasker_out(records, ref_names, ref_lens, lib_names, lib_lens, path):
+    """the 15 columns of a RepeatMasker `.out` under its three header lines, one line per record in the order given: SW score (the
+    record's score: 2 / -4 / -5, not a matrix score), percentage divergence 100 X / (M + X), percentage deletions (library bases without
+    a genome base) and insertions (genome bases without a library base), both of the genome interval, all to one decimal; the
+    sequence, begin, end (1-based, inclusive) and (left); + or C; the name (the library header before #) and class/family (after #, or
+    Unknown); begin, end, (left) in the entry -- (left), end, begin for C; a running ID."""
+    _publish(path, repeatmasker_out_lines(records, ref_names, ref_lens, lib_names, lib_lens))
+
+
+def repeatmasker_gff_lines(records, ref_names, lib_names):
+    lines = ["##gff-version 2\n"]
+    for rec in records:
+        rec = [int(v) for v in rec]
+        mism = annotation_columns(rec)[0]
+        lines.append("%s\tRepeatMasker\tdispersed_repeat\t%d\t%d\t%s\t%s\t.\tTarget \"Motif:%s\" %d %d\n" % (
+            ref_names[rec[0]], rec[1] + 1, rec[2], _pct(mism, rec[8] + mism), "-" if rec[4] else "+", _lib_name_class(lib_names[rec[3]])[0],
+            rec[5] + 1, rec[6]))
+    return lines
+
+
+def write_repeatmasker_gff(records, ref_names, lib_names, path):
+    """one line per record in the form `RepeatMasker -gff` writes and the reference's reader splits (Util.py:13689-13708): sequence,
+    RepeatMasker, dispersed_repeat, start, end (1-based, inclusive), the divergence, + or -, ., Target "Motif:NAME" and the interval in
+    the entry (1-based, inclusive, ascending on either strand)"""
+    _publish(path, repeatmasker_gff_lines(records, ref_names, lib_names))
+
+
+def repeatmasker_tbl_rows(records, ref_lens, lib_names):
+    """[(class, elements, bases covered)] by class name and the total row ("total", ...): the bases are the union of the genome
+    intervals of the class (of all records for the total)"""
+    by_class = {}
+    for rec in records:
+        by_class.setdefault(_lib_name_class(lib_names[int(rec[3])])[1], []).append((int(rec[0]), int(rec[1]), int(rec[2])))
+
+    def union(ivs):
+        total, cur = 0, None
+        for seq, a, b in sorted(ivs):
+            if cur is not None and cur[0] == seq and a <= cur[2]:
+                cur[2] = max(cur[2], b)
+            else:
+                total += cur[2] - cur[1] if cur else 0
+                cur = [seq, a, b]
+        return total + (cur[2] - cur[1] if cur else 0)
+
+    rows = [(cls, len(ivs), union(ivs)) for cls, ivs in sorted(by_class.items())]
+    return rows + [("total", sum(r[1] for r in rows), union([iv for ivs in by_class.values() for iv in ivs]))]
+
+
+def write_repeatmasker_tbl(records, ref_names, ref_lens, lib_names, path):
+    """a summary in the spirit of RepeatMasker's `.tbl`, NOT byte-compatible with it: the number of sequences and bases, then per
+    class/family the number of elements, the bases covered (the union on the genome) and their percentage of the genome, and a total"""
+    total = sum(ref_lens)
+    lines = ["sequences: %d\n" % len(ref_names), "total length: %d bp\n" % total, "%-28s %10s %14s %8s\n" % ("class", "elements", "bases", "percent")]
+    for cls, n, bases in repeatmasker_tbl_rows(records, ref_lens, lib_names):
+        lines.append("%-28s %10d %14d %7s%%\n" % (cls, n, bases, "%.2f" % (100.0 * bases / total if total else 0.0)))
+    _publish(path, lines)
+
+
+def _log_info(log, msg):
+    if log is not None:
+        (log.logger if hasattr(log, "logger") else log).info(msg)
+
+
+def annotate_to_files(lib_path, reference, out_path, gff_path, tbl_path, ctx=None, annot=None, log=None):
+    """the in-tree annotation of `reference` (a FASTA path) with the library `lib_path`: the three files -> the records"""
+    ref_names, ref_contigs = read_fasta(reference)
+    lib_names, lib_contigs = read_fasta(lib_path)
+    annot = annot or (ctx or get_ctx()).annotate
+    stats = {}
+    records, status = annot([ref_contigs[n] for n in ref_names], [lib_contigs[n] for n in lib_names], stats=stats)
+    for e, s in enumerate(status):
+        if s:
+            _log_info(log, "annotate: %s is longer than the annotation's limit for an entry and was not searched" % lib_names[e])
+    _log_info(log, "annotate: %d records (%s)" % (len(records), ", ".join("%s %d" % kv for kv in stats.items())))
+    ref_lens, lib_lens = [len(ref_contigs[n]) for n in ref_names], [len(lib_contigs[n]) for n in lib_names]
+    write_repeatmasker_out(records, ref_names, ref_lens, lib_names, lib_lens, out_path)
+    write_repeatmasker_gff(records, ref_names, lib_names, gff_path)
+    write_repeatmasker_tbl(records, ref_names, ref_lens, lib_names, tbl_path)
+    return records
+
+
+def annotate_genome(tmp_output_dir, classified_TE_consensus, reference, annotate, threads, log, ctx=None, annot=None):
+    """annotate_genome.py:14 with its positional arguments: HiTE.out, HiTE.gff and HiTE.tbl in tmp_output_dir when annotate is 1.
+    RepeatMasker runs when it is installed, unless HITE_ANNOTATOR=gpu or annot= is given; otherwise the in-tree stage
+    (annotate_to_files).  The in-tree stage writes no HiTE.cat.gz (the alignments themselves are not kept)."""
+    if annotate is None or int(annotate) != 1:
+        return
+    if annot is None and os.environ.get("HITE_ANNOTATOR", "") != "gpu" and shutil.which("RepeatMasker") is not None:
+        cmd = "cd %s && RepeatMasker -e ncbi -pa %s -gff -lib %s -cutoff 225 %s" % (tmp_output_dir, threads, classified_TE_consensus, reference)
+        _log_info(log, "Running command: " + cmd)
+        subprocess.run(cmd, shell=True, check=False)
+        for suffix, name in ((".out", "HiTE.out"), (".tbl", "HiTE.tbl"), (".out.gff", "HiTE.gff"), (".cat.gz", "HiTE.cat.gz")):
+            if os.path.exists(reference + suffix):
+                shutil.move(reference + suffix, os.path.join(tmp_output_dir, name))
+        return
+    _log_info(log, "annotate: the in-tree annotation (hite_annotate) stands in for RepeatMasker; no HiTE.cat.gz is written")
+    annotate_to_files(classified_TE_consensus, reference, os.path.join(tmp_output_dir, "HiTE.out"), os.path.join(tmp_output_dir, "HiTE.gff"),
+                      os.path.join(tmp_output_dir, "HiTE.tbl"), ctx=ctx, annot=annot, log=log)
+
+
+def _fmea_new_chain(frags, skip_gap, subject_name, minus):
+    """the chaining of FMEA_new (Util.py:12340) on the fragments (q_start, q_end, s_start, s_end) of one entry, one sequence and one
+    direction, in its order: a fragment extends EVERY earlier chain it fits (latest first, until one lies skip_gap or more before it),
+    and starts a chain of its own only when it extended none"""
+    chains = []
+    for qs, qe, ss, se in frags:
+        extended = False
+        for k in range(len(chains) - 1, -1, -1):
+            pqs, pqe, pss, pse, _name = chains[k]
+            dist = pse - ss if minus else ss - pse
+            if dist >= skip_gap:
+                break
+            if (se < pse if minus else se > pse) and qs - pqe < skip_gap and qe > pqe:
+                if minus:
+                    chains[k] = (pqs, qe, max(pss, ss), se, subject_name)
+                else:
+                    chains[k] = (min(pqs, qs), qe, min(pss, ss), se, subject_name)
+                extended = True
+        if not extended:
+            chains.append((qs, qe, ss, se, subject_name))
+    return chains
+
+
+def FMEA_new(query_contigs, query_records, full_length_threshold):
+    """Util.py:12340 restated: {entry: [(entry, q_start, q_end, sequence, s_start, s_end)]}, starts 0-based.  Entries in the order of
+    query_records, sequences in the order met, the plus fragments (s_start <= s_end, by (s_start, s_end)) before the minus ones (by
+    descending (s_start, s_end)); an entry that is not in query_contigs is left out."""
+    longest_repeats = {}
+    for query_name, subject_dict in query_records.items():
+        if query_name not in query_contigs:
+            continue
+        skip_gap = len(query_contigs[query_name]) * (1 - full_length_threshold)
+        chains = []
+        for subject_name, frags in subject_dict.items():
+            plus = sorted((f for f in frags if not f[2] > f[3]), key=lambda x: (x[2], x[3]))
+            minus = sorted((f for f in frags if f[2] > f[3]), key=lambda x: (-x[2], -x[3]))
+            chains += _fmea_new_chain(plus, skip_gap, subject_name, False) + _fmea_new_chain(minus, skip_gap, subject_name, True)
+        longest_repeats[query_name] = [(query_name, c[0] - 1, c[1], c[4], c[2] - 1, c[3]) for c in chains]
+    return longest_repeats
+
+
+def read_repeatmasker_gff(gff_path):
+    """-> ({entry: {sequence: [(q_start, q_end, s_start, s_end)]}}, the entry of the last line) as Util.py:13689-13708 reads the file"""
+    query_records, last = {}, None
+    with open(gff_path) as f_r:
+        for line in f_r:
+            if line.startswith("#"):
+                continue
+            parts = line.split("\t")
+            info = parts[8].split(" ")
+            last = info[1].replace('"', "").split(":")[1]
+            query_records.setdefault(last, {}).setdefault(parts[0], []).append((int(info[2]), int(info[3]), int(parts[3]), int(parts[4])))
+    return query_records, last
+
+
+def get_full_length_copies_from_gff_v1(TE_lib, reference, gff_path, full_length_threshold, te_classes):
+    """Util.py:13679 restated: the chains of FMEA_new over the GFF's records that span at least full_length_threshold of their entry
+    -> (full_length_copies {entry: {"seq:start-end": bases}}, the same with flanks, full_length_annotations {entry: [(class, sequence,
+    start (0-based), end, direction)]}).  As there: the flank is 5 bases when the entry of the LAST line of the GFF has Helitron in
+    its name and 50 otherwise, for every entry; a flank that would begin before the sequence gives what Python's slice gives; a GFF's
+    start is never above its end, so every copy is '+' whatever its strand column says.  A GFF without records gives three empty
+    dictionaries (the reference fails there)."""
+    _ref_names, ref_contigs = read_fasta(reference)
+    query_names, contigs = read_fasta(TE_lib)
+    query_contigs = {name.split("#")[0]: contigs[name] for name in query_names}
+    query_records, last = read_repeatmasker_gff(gff_path)
+    if last is None:
+        return {}, {}, {}
+    longest_repeats = FMEA_new(query_contigs, query_records, full_length_threshold)
+    flanking_len = 5 if "Helitron" in str(last) else 50
+    full_length_copies, flank_full_length_copies, full_length_annotations = {}, {}, {}
+    for query_name, repeats in longest_repeats.items():
+        query_len = len(query_contigs[query_name])
+        annotations, query_copies, flank_query_copies = [], {}, {}
+        for _name, q_start, q_end, subject_name, s_start, s_end in repeats:
+            if abs(q_end - q_start) < full_length_threshold * query_len:
+                continue
+            direct = "-" if s_start > s_end else "+"
+            lo, hi = (s_end, s_start) if s_start > s_end else (s_start, s_end)
+            subject_pos = "%s:%d-%d" % (subject_name, lo, hi)
+            query_copies[subject_pos] = ref_contigs[subject_name][lo:hi]
+            flank_query_copies[subject_pos] = ref_contigs[subject_name][lo - flanking_len:hi + flanking_len]
+            annotations.append((te_classes[query_name], subject_name, lo, hi, direct))
+        full_length_copies[query_name] = query_copies
+        flank_full_length_copies[query_name] = flank_query_copies
+        full_length_annotations[query_name] = annotations
+    return full_length_copies, flank_full_length_copies, full_length_annotations
+
+
+def get_TE_class(panTE_lib):
+    """Util.py:13421: ({name before #: class after #}, {name before #: sequence})"""
+    te_names, te_contigs = read_fasta(panTE_lib)
+    return {n.split("#")[0]: n.split("#")[1] for n in te_names}, {n.split("#")[0]: te_contigs[n] for n in te_names}
+
+
+def full_length_gff_lines(full_length_annotations):
+    """the lines of <genome>.full_length.gff as pan_annotate_genome.py:50-66 makes them: numbered in the order of the annotations, then
+    ordered as `sort -k1,1 -k4n` orders them in the C locale (by sequence name, then by start, ties by the whole line)"""
+    lines, n = [], 0
+    for query_name, annotations in full_length_annotations.items():
+        for cls, chr_name, start, end, direct in annotations:
+            n += 1
+            lines.append("%s\tHiTE\t%s\t%d\t%d\t.\t%s\t.\tid=te_intact_%d;name=%s;classification=%s\n" % (chr_name, cls, start + 1, end, direct, n, query_name, cls))
+    return sorted(lines, key=lambda ln: (ln.split("\t")[0].encode(), int(ln.split("\t")[3]), ln.encode()))

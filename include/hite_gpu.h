@@ -586,6 +586,89 @@ int hite_ltr_scan(hite_ctx *ctx, int64_t n, const uint8_t *seqs, const int64_t *
                   int32_t min_len, int32_t max_len, int32_t min_ltr, int32_t max_ltr, int32_t identity /* percent */,
                   int64_t cap, int32_t *recs /* cap x 8 */, int64_t *n_out, int64_t *stats);
 
+/* ---- genome annotation --- the `RepeatMasker -e ncbi -gff -lib <lib> -cutoff 225 <genome>` run that ends HiTE
+ * (module/annotate_genome.py:17, module/pan_annotate_genome.py:27) and gives HiTE.out / HiTE.gff / HiTE.tbl and panHiTE's
+ * <genome>.full_length.gff.  In-tree stage, library + genome in, annotation records out.  PARITY UNPINNED against RepeatMasker (no
+ * machine of the project has it, and none of its text is here): what is computed is the definition below, its CPU twin
+ * tests/annotate_twin.py + tests/annotate_twin.c, HIP == twin record for record and counter for counter; the stage is measured on
+ * planted truth (tools/annotate_bench.py).  Stated deviations: exact 13-base seeds; alignments live in a band of 192 diagonals; no
+ * scoring matrix by divergence and no e-value (the 2 / -4 / -5 arithmetic of hite_pair_hsps at a fixed score threshold instead of
+ * -cutoff 225); a copy longer than a window comes as several records; no simple-repeat or low-complexity annotation; no `.cat.gz`.
+ *
+ * The genome and the library are CSR batches of byte sequences.  Bytes are read as A C G T in either case; any other byte is in no
+ * word and matches nothing.  Positions are 0-based; g is a position in its genome sequence (of len bases), q one in a text.
+ *  1. Library table.  Entry e (of L bases) gives two texts of L bases: t = 2e is the entry, t = 2e + 1 its reverse complement (a
+ *     byte outside ACGT stays outside).  An entry with L > HITE_ANNOT_MAX_LIB_LEN gives no text and has lib_status -1; the others
+ *     have 0.  The table holds (word, t, q) for every position q of a text where text[q, q+13) is all ACGT (HITE_ANNOT_WORD).  A
+ *     word with more than HITE_ANNOT_MAX_OCC entries in the whole table casts no hit ("silenced": counted per entry).
+ *  2. Pieces and hits.  P = piece_len (0: HITE_ANNOT_PIECE).  Piece k of a sequence is [kP, min(len, (k+1)P + HITE_ANNOT_OVERLAP)),
+ *     k = 0 .. ceil(len / P) - 1.  piece_len is part of the definition (it decides which hits chain); the number of pieces that go
+ *     to the device together is not.  Inside a piece, a position g with piece.begin <= g and g + 13 <= piece.end whose word is a
+ *     table word that is not silenced gives one hit (t, q, g) per table entry, with d = g - q.
+ *  3. Runs, on two lattices lambda = 0 and 32.  The bin of a hit is (d - piece.begin + lambda + HITE_ANNOT_MAX_LIB_LEN) >> 6.  The
+ *     hits of equal (piece, t, bin) are taken by ascending g (hits of equal g in any order: a run is made of minima, maxima and a count).  A hit joins the chain of the
+ *     hit before it when g - g_prev <= HITE_ANNOT_GAP and g - g_first < HITE_ANNOT_MAX_SPAN (g_first: the chain's first hit);
+ *     otherwise it starts a new chain.  A chain of at least HITE_ANNOT_MIN_HITS hits is a run (t, g_lo, g_hi, d_lo, d_hi): the
+ *     first and the last g, the smallest and the largest d.  The runs of both lattices and of all pieces go on.
+ *  4. Extension, per run.  dc = (d_lo + d_hi) >> 1, q_lo = g_lo - dc, q_hi = g_hi - dc.  The pads PL and PR each walk through
+ *     HITE_ANNOT_PAD_0 .. _3, starting at the first.
+ *        Q = [max(0, q_lo - PL), min(L, q_hi + 13 + PR)) of text t,
+ *        S = [max(0, Q.begin + dc - 96), min(len, Q.end + dc + 96)) of the sequence (the whole sequence, not the piece).
+ *     The alignment is step 4 of hite_pair_hsps as it stands (the same cell tuple, 2 / -4 / -5, the same "best", the same best-cell
+ *     tie rule) with Q as rows and S as columns, on the whole rectangle inside the band dc - 96 <= g - q <= dc + 95; its result is
+ *     an HSP at score >= HITE_PAIRHSP_MIN_SCORE, [qs, qe) in the text and [gs, ge) in the sequence.  No HSP: the run gives
+ *     nothing.  If qs - Q.begin < HITE_ANNOT_EDGE while Q.begin > 0 and PL is not at its last value, PL steps; if Q.end - qe <
+ *     HITE_ANNOT_EDGE while Q.end < L and PR is not at its last value, PR steps.  If either stepped and fewer than
+ *     HITE_ANNOT_MAX_REDO alignments have been redone, the alignment is redone.  (A run spans less than HITE_ANNOT_MAX_SPAN + 13
+ *     bases and the last pad is 8 192: a window stays under the 32 768 the packed start coordinates of a cell hold.)
+ *  5. Resolve.  The record of an HSP is ten int32: seq, g_start, g_end (0-based, half-open, plus strand of the sequence), lib = t >> 1,
+ *     strand = t & 1 (1: the entry's reverse complement), q_start, q_end (0-based, half-open, on the entry's FORWARD strand: for
+ *     strand 1 they are L - qe, L - qs), score, matches, columns.  The order key of a record is (seq, g_start, g_end, lib, strand,
+ *     q_start, q_end, -score, -matches, columns).  (a) Of the records equal in (seq, g_start, g_end, lib, strand, q_start, q_end)
+ *     the first by the order key is kept (two lattices or two pieces find a copy twice).  (b) Of what (a) kept, a record A is
+ *     dropped when a record B != A of the same sequence is better -- a higher score, or the same score and a smaller order key --
+ *     and 5 * overlap(A, B) >= 4 * (A.g_end - A.g_start), overlap being the number of bases the two g intervals share.  A is held
+ *     against every B of (a), dropped or not: the rule does not depend on an order.
+ *  6. Order.  The records are written by ascending order key.
+ *
+ * Limits: n_lib <= HITE_ANNOT_MAX_LIB, every genome sequence shorter than 2^31, piece_len 0 or HITE_ANNOT_MIN_PIECE ..
+ * HITE_ANNOT_PIECE: anything else, a negative count, a missing buffer or descending offsets is HITE_EINVAL.  n_seq = 0, n_lib = 0,
+ * empty sequences and sequences shorter than a word are valid and give nothing.  recs holds cap records; *n_out is the number of
+ * records of the call, HITE_ECAP when cap is smaller (the first cap are written).  lib_status (may be NULL) holds n_lib entries.
+ * stats (may be NULL) receives HITE_ANNOT_STATS counters: table entries, of these silenced, entries too long, hits, runs (both
+ * lattices, all pieces), alignments run, of these redone, runs without an HSP, HSPs before the resolve, duplicates dropped by
+ * 5 (a), records dropped by 5 (b), records.
+ * Pieces go to the device whole, each with the HITE_ANNOT_PAD_3 + 109 bases of its sequence on either side that a window can
+ * reach, as many as stay within 64 MiB of bases; $HITE_ANNOT_BATCH_BYTES, read by hite_ctx_create, sets a smaller bound: a knob
+ * that never changes a result.  Device memory: 12 bytes per table entry and as much again for its sort, the bases of a batch, 32
+ * bytes per hit (the hit, its sort key and its diagonal, and as much again for the sort; the room for the hits comes from a first
+ * pass that counts them and a second that writes them when the first guess was too small) and 72 per run. */
+#define HITE_ANNOT_WORD        13
+#define HITE_ANNOT_MAX_OCC     16
+#define HITE_ANNOT_BIN_SHIFT   6
+#define HITE_ANNOT_LATTICE     32
+#define HITE_ANNOT_GAP         300
+#define HITE_ANNOT_MIN_HITS    3
+#define HITE_ANNOT_MAX_SPAN    8192
+#define HITE_ANNOT_BAND_BELOW  96
+#define HITE_ANNOT_BAND_ABOVE  96
+#define HITE_ANNOT_PAD_0       256
+#define HITE_ANNOT_PAD_1       1024
+#define HITE_ANNOT_PAD_2       4096
+#define HITE_ANNOT_PAD_3       8192
+#define HITE_ANNOT_EDGE        32
+#define HITE_ANNOT_MAX_REDO    3
+#define HITE_ANNOT_PIECE       (1 << 24)
+#define HITE_ANNOT_MIN_PIECE   256
+#define HITE_ANNOT_OVERLAP     (1 << 16)
+#define HITE_ANNOT_MAX_LIB_LEN 24576
+#define HITE_ANNOT_MAX_LIB     32768
+#define HITE_ANNOT_REC         10
+#define HITE_ANNOT_STATS       12
+int hite_annotate(hite_ctx *ctx, int64_t n_seq, const uint8_t *seqs, const int64_t *seq_off,
+                  int32_t n_lib, const uint8_t *lib, const int64_t *lib_off, int32_t piece_len /* 0: HITE_ANNOT_PIECE */,
+                  int64_t cap, int32_t *recs /* cap x 10 */, int64_t *n_out, int8_t *lib_status /* n_lib: 0 or -1 */, int64_t *stats);
+
 /* ---- Helitron candidate scan --- multi_process_helitronscanner  Util.py:263 (third-party HelitronScanner.jar: scanHead, scanTail,
  * pairends, draw -pure_helitron per 50 kb part of longest_repeats_{i}.flanked.fa; judge_Helitron_transposons.py:27-34) -------------
  * In-tree stage, not pinned to the tool (no machine of the project runs it, and the tool's pairing rule and the tie-breaks of its
