@@ -13,22 +13,23 @@
 //   3. runs, once per lattice: the hits are sorted on (t, bin, position) packed into one 64-bit key; the thread of a hit that begins
 //      a chain (another t, bin or piece, or more than HITE_ANNOT_GAP after the hit before) walks the chain, closes it where the span
 //      limit says so and emits every run as a task with one atomic per run;
-//   4. extension: ONE WAVEFRONT PER RUN in the lane layout of ph_align (hite_pairhsp.hip), as ls_extend_kernel has it: rows are the
-//      text, columns the genome; the redo loop of the pads runs inside the wavefront.
-// The resolve and the order (steps 5 and 6) are host code.  hite_pairhsp.hip and hite_ltrscan.hip are left as they are: this file
-// carries its own copy of the cell and of the strip routine.
+//   4. extension: ONE WAVEFRONT PER RUN through hsp_align (hite_hsp.h: the cell and the strip routine of hite_pair_hsps, which the
+//      word key and the word kernel of step 1 come from as well), as ls_extend_kernel has it: rows are the text, columns the genome;
+//      the redo loop of the pads runs inside the wavefront.
+// The resolve and the order (steps 5 and 6) are host code.
 #include "hite_common.h"
 #include "hite_hostbuf.h"
+#include "hite_hsp.h"
 #include "hite_sort.h"
 #include <algorithm>
 #include <new>
 #include <vector>
 
 #define AN_WAVES 4
-#define AN_BAND (HITE_ANNOT_BAND_BELOW + HITE_ANNOT_BAND_ABOVE)      // diagonals of the band
+static_assert(HITE_ANNOT_BAND_BELOW + HITE_ANNOT_BAND_ABOVE == HSP_BAND, "the band of a run is the band of hsp_align");
 #define AN_BATCH_BYTES ((int64_t)64 << 20)      // bases per batch, the margins included ($HITE_ANNOT_BATCH_BYTES sets a smaller bound)
 #define AN_HALO (HITE_ANNOT_PAD_3 + HITE_ANNOT_BAND_ABOVE + HITE_ANNOT_WORD)      // bases beside a piece that a window can reach
-#define AN_NO_WORD ((unsigned long long)1 << 26)
+#define AN_NO_WORD ((unsigned long long)1 << 2 * HITE_ANNOT_WORD)      // what hsp_word_key gives a position without a word
 #define AN_WORD_BITS 27
 #define AN_OUT_WORDS 12                          // per run: found, seq, gs, ge, t, qs, qe, score, matches, columns, alignments, fault
 #define AN_MAX_BLOCKS 2048
@@ -36,54 +37,7 @@
 #define __host__
 #endif
 
-// >>> annotate_cell
-// The cell of hite_pair_hsps, step 4 (a copy of the pairhsp_cell block of hite_pairhsp.hip).  A cell value (score, matches, columns,
-// q_start, s_start) is TWO words.  a = score * 2^40 + matches * 2^20 + columns, signed: matches and columns stay below 2^20 (a window
-// holds at most 3 * 8192 + 192 bases), so the integer order of a is the lexicographic order of the first three fields, a step is one
-// addition and "score <= 0" is a < 2^40.  b = q_start * 2^16 + s_start (both < 32 768): on equal a the smaller b wins.  The empty
-// value is (0, 0).
-#define AN_SCORE_ONE ((int64_t)1 << 40)
-#define AN_STEP_MATCH (HITE_PAIRHSP_MATCH * AN_SCORE_ONE + ((int64_t)1 << 20) + 1)
-#define AN_STEP_MISMATCH (HITE_PAIRHSP_MISMATCH * AN_SCORE_ONE + 1)
-#define AN_STEP_GAP (HITE_PAIRHSP_GAP * AN_SCORE_ONE + 1)
-struct AnVal { int64_t a; uint32_t b; };
-// a byte (either case) as a base code A 0 / C 1 / G 2 / T 3 / anything else 4
-__device__ __forceinline__ int an_code(uint8_t c) {
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-__device__ __forceinline__ bool an_better(int64_t a1, uint32_t b1, int64_t a2, uint32_t b2) { return a1 > a2 || (a1 == a2 && b1 < b2); }
-__device__ __forceinline__ AnVal an_cell(AnVal diag, AnVal up, AnVal left, int ca, int cb, int i, int j) {
-    AnVal v;
-    v.a = diag.a + ((ca == cb && ca < 4) ? AN_STEP_MATCH : AN_STEP_MISMATCH);
-    v.b = diag.a == 0 ? ((uint32_t)i << 16 | (uint32_t)j) : diag.b;
-    const int64_t ua = up.a + AN_STEP_GAP, la = left.a + AN_STEP_GAP;
-    if (an_better(ua, up.b, v.a, v.b)) { v.a = ua; v.b = up.b; }
-    if (an_better(la, left.b, v.a, v.b)) { v.a = la; v.b = left.b; }
-    if (v.a < AN_SCORE_ONE) { v.a = 0; v.b = 0; }
-    return v;
-}
-// the best cell so far: its value and e = i * 2^16 + j; a later cell takes its place when its value is better, or equal at a smaller e
-struct AnBest { int64_t a; uint32_t b, e; };
-__device__ __forceinline__ bool an_best_better(int64_t a, uint32_t b, uint32_t e, const AnBest &o) {
-    return a > o.a || (a == o.a && (b < o.b || (b == o.b && e < o.e)));
-}
-// <<< annotate_cell
-
 // >>> annotate_key
-// the word of 13 base codes (the first one in the highest bits), or AN_NO_WORD when one of them is not in ACGT
-__host__ __device__ __forceinline__ unsigned long long an_word_key(const int *codes) {
-    unsigned long long w = 0;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < HITE_ANNOT_WORD; k++) { ok = ok && codes[k] < 4; w = w * 4 + (unsigned long long)(codes[k] & 3); }
-    return ok ? w : ((unsigned long long)1 << 26);
-}
 // the reverse complement's byte for a byte of the entry: anything outside ACGT (either case) becomes N
 __host__ __device__ __forceinline__ uint8_t an_comp(uint8_t c) {
     switch (c) {
@@ -111,8 +65,6 @@ __host__ __device__ __forceinline__ unsigned long long an_run_key(uint32_t t, ui
 }
 __host__ __device__ __forceinline__ int64_t an_key_pos(unsigned long long key, int pos_bits) { return (int64_t)(key & (((unsigned long long)1 << pos_bits) - 1)); }
 __host__ __device__ __forceinline__ unsigned long long an_key_group(unsigned long long key, int pos_bits) { return key >> pos_bits; }
-// bits that hold every value 0 .. v
-__host__ __device__ __forceinline__ int an_bits(unsigned long long v) { int b = 1; while (b < 64 && (v >> b) != 0) b++; return b; }
 // the pad of level k = 0 .. 3
 __host__ __device__ __forceinline__ int an_pad(int k) { return k == 0 ? HITE_ANNOT_PAD_0 : k == 1 ? HITE_ANNOT_PAD_1 : k == 2 ? HITE_ANNOT_PAD_2 : HITE_ANNOT_PAD_3; }
 // the two windows of a run at the pad levels pl, pr: Q = [qb, qe) of a text of L bases, S = [sb, se) of a sequence of len bases, and
@@ -200,15 +152,6 @@ struct AnPiece { int64_t seq_len; int32_t seq, begin, end, lead, trail; int64_t 
 struct AnTask { int32_t piece, t, g_lo, g_hi, d_lo, d_hi; };      // a run: g in the sequence, d = g - q
 enum { AN_C_WORDS = 0, AN_C_SILENT, AN_C_HITS, AN_C_RUNS, AN_C_N };
 
-// the last x in 0 .. n - 1 with off[x] <= p (off[0] <= p)
-__device__ __forceinline__ int an_last_le(const int64_t *__restrict__ off, int n, int64_t p) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 // the piece of the batch that holds byte gp (at[0] = 0 <= gp < at[n])
 __device__ __forceinline__ int an_piece_of(const AnPiece *__restrict__ pc, int n, int64_t gp) {
     int lo = 0, hi = n;
@@ -217,43 +160,6 @@ __device__ __forceinline__ int an_piece_of(const AnPiece *__restrict__ pc, int n
         if (pc[mid].at <= gp) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-// adds v of every lane to *counter with one atomic per wavefront; returns the sum of the lanes before this one plus the counter's
-// value before (every lane of the wavefront must come here)
-__device__ __forceinline__ unsigned long long an_wave_take(unsigned v, unsigned long long *counter) {
-    const int lane = lane_id();
-    unsigned incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const unsigned y = __shfl_up(incl, s, 64);
-        if (lane >= s) incl += y;
-    }
-    const unsigned total = __shfl(incl, 63, 64);
-    unsigned long long base = 0;
-    if (lane == 0 && total) base = atomicAdd(counter, (unsigned long long)total);
-    base = (unsigned long long)__shfl((long long)base, 0, 64);
-    return base + (incl - v);
-}
-
-// one thread per byte of the texts: the word that begins there
-__global__ __launch_bounds__(256) void an_table_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ off, int n_text, int64_t nb,
-                                                       unsigned long long *__restrict__ keys, unsigned *__restrict__ vals,
-                                                       unsigned long long *__restrict__ counters) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned long long key = AN_NO_WORD;
-    if (p < nb) {
-        const int t = an_last_le(off, n_text, p);
-        if (p + HITE_ANNOT_WORD <= off[t + 1]) {
-            int codes[HITE_ANNOT_WORD];
-#pragma unroll
-            for (int k = 0; k < HITE_ANNOT_WORD; k++) codes[k] = an_code(text[p + k]);
-            key = an_word_key(codes);
-        }
-        keys[p] = key;
-        vals[p] = (unsigned)p;
-    }
-    (void)an_wave_take(key != AN_NO_WORD ? 1u : 0u, &counters[AN_C_WORDS]);
 }
 
 // the first entry of the sorted table with a key >= w
@@ -277,7 +183,7 @@ __global__ __launch_bounds__(256) void an_silent_kernel(const unsigned long long
         for (int64_t k = e + 1; k < nw && n <= HITE_ANNOT_MAX_OCC && keys[k] == w; k++) n++;
         silent = n > HITE_ANNOT_MAX_OCC;
     }
-    (void)an_wave_take(silent ? 1u : 0u, &counters[AN_C_SILENT]);
+    (void)wave_take_flag(silent, &counters[AN_C_SILENT]);
 }
 
 // one thread per byte of the batch: the hits of the position (step 2); written while they fit hit_cap, counted always
@@ -294,8 +200,8 @@ __global__ __launch_bounds__(256) void an_hit_kernel(const uint8_t *__restrict__
         if (gp >= lo && gp + HITE_ANNOT_WORD <= hi) {
             int codes[HITE_ANNOT_WORD];
 #pragma unroll
-            for (int k = 0; k < HITE_ANNOT_WORD; k++) codes[k] = an_code(seqs[gp + k]);
-            const unsigned long long w = an_word_key(codes);
+            for (int k = 0; k < HITE_ANNOT_WORD; k++) codes[k] = hsp_code(seqs[gp + k]);
+            const unsigned long long w = hsp_word_key<HITE_ANNOT_WORD>(codes);
             if (w != AN_NO_WORD) {
                 first = an_lower(tkeys, nw, w);
                 while (n <= HITE_ANNOT_MAX_OCC && first + n < nw && tkeys[first + n] == w) n++;
@@ -303,11 +209,11 @@ __global__ __launch_bounds__(256) void an_hit_kernel(const uint8_t *__restrict__
             }
         }
     }
-    const unsigned long long at = an_wave_take(n, &counters[AN_C_HITS]);
+    const unsigned long long at = wave_take_count(n, &counters[AN_C_HITS]);
     for (unsigned k = 0; k < n; k++) {
         if ((int64_t)(at + k) >= hit_cap) break;
         const int64_t tp = tvals[first + k];
-        const int t = an_last_le(text_off, n_text, tp);
+        const int t = last_le(text_off, n_text, tp);
         hits[at + k] = an_hit_pack((uint32_t)t, (uint32_t)(tp - text_off[t]), (uint32_t)gp);
     }
 }
@@ -364,94 +270,13 @@ __global__ __launch_bounds__(256) void an_run_kernel(const unsigned long long *_
     emit();
 }
 
-// lane l takes the value of lane l - 1 (wave_shr1), lane 0 gets 0 and the caller puts its own value there
-__device__ __forceinline__ AnVal an_up1(AnVal v) {
-    AnVal r;
-    const uint32_t lo = (uint32_t)wave_shr1((int)(uint32_t)v.a), hi = (uint32_t)wave_shr1((int)(uint32_t)((uint64_t)v.a >> 32));
-    r.a = (int64_t)((uint64_t)hi << 32 | lo);
-    r.b = (uint32_t)wave_shr1((int)v.b);
-    return r;
-}
-
-__device__ __forceinline__ AnBest an_wave_best(AnBest v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        AnBest y;
-        y.a = __shfl_xor((long long)v.a, d, 64);
-        y.b = __shfl_xor(v.b, d, 64);
-        y.e = __shfl_xor(v.e, d, 64);
-        if (an_best_better(y.a, y.b, y.e, v)) v = y;
-    }
-    return v;
-}
-
-// The best cell of rows r0 .. r1 and columns c0 .. c1 (1-based, inside [1, m] x [1, n]) within the band dlo <= j - i <= dhi
-// (dhi - dlo < AN_BAND), by one wavefront; q / s: the bytes of the two windows; bnd_a / bnd_b: 2 x AN_BAND words of the wavefront.  The
-// strip routine of ph_align (hite_pairhsp.hip): lane l is on row first + d - 1 - l at step d; the cell above is the lane's own last
-// value, the cell to the left the last value of lane l - 1, the diagonal cell what lane l - 1 handed over one step earlier.  All lanes
-// return the same value; a == 0: no cell has a positive score.
-__device__ __forceinline__ AnBest an_align(const uint8_t *q, int m, const uint8_t *s, int dlo, int dhi, int r0, int r1, int c0, int c1,
-                                           long long *bnd_a, uint32_t *bnd_b) {
-    const int lane = lane_id();
-    AnBest best = {0, 0, 0};
-    const int cs = max(c0, r0 + dlo), ce = min(c1, r1 + dhi);      // the columns the band reaches inside the rectangle
-    int buf = 0;
-    for (int js = cs; js <= ce; js += 64, buf ^= 1) {
-        const int nl = min(64, ce - js + 1);
-        const bool more = js + 64 <= ce;
-        const int first = max(r0, js - dhi), last = min(r1, js + nl - 1 - dlo);      // the rows where the band meets the strip
-        const int ib = first - 1, j = js + lane;
-        const int cb = lane < nl ? an_code(s[j - 1]) : 4;
-        const long long *rd_a = bnd_a + (buf ^ 1) * AN_BAND;
-        const uint32_t *rd_b = bnd_b + (buf ^ 1) * AN_BAND;
-        long long *wr_a = bnd_a + buf * AN_BAND;
-        uint32_t *wr_b = bnd_b + buf * AN_BAND;
-        // V(row, js - 1): the last column of the strip before, the empty value outside the band or the rectangle
-        auto edge = [&](int row) {
-            AnVal v = {0, 0};
-            const int dd = js - 1 - row;
-            if (js > cs && row >= r0 && row <= r1 && dd >= dlo && dd <= dhi) { v.a = (int64_t)rd_a[dhi - dd]; v.b = rd_b[dhi - dd]; }
-            return v;
-        };
-        AnVal cur = {0, 0}, diag = {0, 0};
-        if (lane == 0) diag = edge(ib);
-        AnVal ahead = edge(ib + 1);      // lane 0's left neighbour of the next step
-        int ca = 4, a64 = 4;             // the lane's base of Q; Q[ib + 64 k + lane] of the current 64 rows
-        const int steps = last - ib + nl - 1;
-        for (int d = 1; d <= steps; d++) {
-            const int i = ib + d - lane;
-            if (((d - 1) & 63) == 0) {
-                const int r = ib + d + lane;
-                a64 = (r >= 1 && r <= m) ? an_code(q[r - 1]) : 4;
-            }
-            const int a_new = __builtin_amdgcn_readlane(a64, (d - 1) & 63);      // the code of row ib + d
-            ca = wave_shr1(ca);
-            AnVal left = an_up1(cur);
-            if (lane == 0) { ca = a_new; left = ahead; }
-            ahead = edge(ib + d + 1);
-            const bool on = lane < nl && i >= r0 && i <= r1 && j - i >= dlo && j - i <= dhi;
-            AnVal v = an_cell(diag, cur, left, ca, cb, i, j);
-            diag = left;
-            if (!on) { v.a = 0; v.b = 0; }
-            cur = v;
-            if (on) {
-                const uint32_t e = (uint32_t)i << 16 | (uint32_t)j;
-                if (v.a > 0 && an_best_better(v.a, v.b, e, best)) { best.a = v.a; best.b = v.b; best.e = e; }
-                if (more && lane == 63) { wr_a[dhi - (j - i)] = (long long)v.a; wr_b[dhi - (j - i)] = v.b; }
-            }
-        }
-        __threadfence_block();          // lane 0 of the next strip reads what lane 63 wrote
-    }
-    return an_wave_best(best);
-}
-
 // wavefront per run: step 4 of the header with its redo loop.  A window that would leave the bytes the batch holds of the sequence is
 // not read: the run is marked (out[11]) and the call fails -- the margins are sized so that this cannot happen.
 __global__ __launch_bounds__(AN_WAVES * 64) void an_extend_kernel(const AnTask *__restrict__ tasks, int64_t n_tasks, const uint8_t *__restrict__ seqs,
                                                                   const AnPiece *__restrict__ pc, const uint8_t *__restrict__ text,
                                                                   const int64_t *__restrict__ text_off, int32_t *__restrict__ out) {
-    __shared__ long long s_bnd_a[AN_WAVES][2 * AN_BAND];
-    __shared__ uint32_t s_bnd_b[AN_WAVES][2 * AN_BAND];
+    __shared__ long long s_bnd_a[AN_WAVES][2 * HSP_BAND];
+    __shared__ uint32_t s_bnd_b[AN_WAVES][2 * HSP_BAND];
     const int lane = lane_id(), w = wave_id();
     for (int64_t k = (int64_t)blockIdx.x * AN_WAVES + w; k < n_tasks; k += (int64_t)gridDim.x * AN_WAVES) {
         const AnTask T = tasks[k];
@@ -463,7 +288,7 @@ __global__ __launch_bounds__(AN_WAVES * 64) void an_extend_kernel(const AnTask *
         const int64_t dc = ((int64_t)T.d_lo + T.d_hi) >> 1;
         int pl = 0, pr = 0, n_align = 0, found = 0, fault = 0;
         int64_t qs = 0, qe = 0, gs = 0, ge = 0;
-        AnBest h = {0, 0, 0};
+        HspBest h = {0, 0, 0};
         for (;;) {
             const AnWin W = an_window(L, P.seq_len, T.g_lo, T.g_hi, dc, pl, pr);
             const int m = (int)(W.qe - W.qb), n = (int)(W.se - W.sb);
@@ -471,11 +296,11 @@ __global__ __launch_bounds__(AN_WAVES * 64) void an_extend_kernel(const AnTask *
             found = 0;
             if (W.qe - W.qb < 1 || W.se - W.sb < 1 || W.qe - W.qb >= HITE_PAIRHSP_MAX_LEN || W.se - W.sb >= HITE_PAIRHSP_MAX_LEN || W.sb < have_lo ||
                 W.se > have_hi) { fault = 1; break; }
-            h = an_align(q + W.qb, m, s + W.sb, W.dlo, W.dlo + AN_BAND - 1, 1, m, 1, n, s_bnd_a[w], s_bnd_b[w]);
-            if ((int)(h.a >> 40) < HITE_PAIRHSP_MIN_SCORE) break;
+            h = hsp_align(q + W.qb, m, s + W.sb, W.dlo, W.dlo + HSP_BAND - 1, 1, m, 1, n, s_bnd_a[w], s_bnd_b[w]);
+            if (hsp_score(h.a) < HITE_PAIRHSP_MIN_SCORE) break;
             found = 1;
-            qs = W.qb + (int64_t)(h.b >> 16) - 1; qe = W.qb + (int64_t)(h.e >> 16);
-            gs = W.sb + (int64_t)(h.b & 0xFFFFu) - 1; ge = W.sb + (int64_t)(h.e & 0xFFFFu);
+            qs = W.qb + hsp_q_start(h.b) - 1; qe = W.qb + hsp_q_end(h.e);
+            gs = W.sb + hsp_s_start(h.b) - 1; ge = W.sb + hsp_s_end(h.e);
             const int step = an_pad_steps(W, L, qs, qe, pl, pr);
             if (step == 0 || n_align > HITE_ANNOT_MAX_REDO) break;
             pl += step & 1;
@@ -484,14 +309,13 @@ __global__ __launch_bounds__(AN_WAVES * 64) void an_extend_kernel(const AnTask *
         if (lane == 0) {
             int32_t *o = out + k * AN_OUT_WORDS;
             o[0] = found; o[1] = P.seq; o[2] = (int32_t)gs; o[3] = (int32_t)ge; o[4] = T.t; o[5] = (int32_t)qs; o[6] = (int32_t)qe;
-            o[7] = (int32_t)(h.a >> 40); o[8] = (int32_t)((h.a >> 20) & 0xFFFFF); o[9] = (int32_t)(h.a & 0xFFFFF); o[10] = n_align; o[11] = fault;
+            o[7] = hsp_score(h.a); o[8] = hsp_matches(h.a); o[9] = hsp_columns(h.a); o[10] = n_align; o[11] = fault;
         }
     }
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 #define AN_ALLOC(pool, ptr, bytes) HITE_CHECK(ctx, (pool).alloc(ptr, (size_t)(bytes)))
-static inline unsigned an_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // the table of a call on the device
 struct AnTable {
@@ -522,7 +346,8 @@ static int an_table(hite_ctx *ctx, const std::vector<uint8_t> &text, const std::
     int rc = sorter_init(G.S, ctx, stream, nb);
     if (rc) return rc;
     int tk = hite_prof_begin(ctx, "annot_table", stream);
-    hipLaunchKernelGGL(an_table_kernel, dim3(an_grid(nb)), dim3(256), 0, stream, T.d_text, T.d_off, T.n_text, nb, T.d_keys, T.d_vals, d_cnt);
+    hipLaunchKernelGGL(hsp_word_kernel<HITE_ANNOT_WORD>, dim3(grid256(nb)), dim3(256), 0, stream, T.d_text, T.d_off, T.n_text, nb, T.d_keys, T.d_vals,
+                       d_cnt + AN_C_WORDS);
     HITE_CHECK(ctx, hipGetLastError());
     rc = sorter_sort_bits(G.S, T.d_keys, T.d_vals, nb, 0, AN_WORD_BITS);
     if (rc) return rc;
@@ -531,7 +356,7 @@ static int an_table(hite_ctx *ctx, const std::vector<uint8_t> &text, const std::
     HITE_CHECK(ctx, hipStreamSynchronize(stream));
     T.nw = (int64_t)h_cnt[AN_C_WORDS];
     if (T.nw > 0) {
-        hipLaunchKernelGGL(an_silent_kernel, dim3(an_grid(T.nw)), dim3(256), 0, stream, T.d_keys, T.nw, d_cnt);
+        hipLaunchKernelGGL(an_silent_kernel, dim3(grid256(T.nw)), dim3(256), 0, stream, T.d_keys, T.nw, d_cnt);
         HITE_CHECK(ctx, hipGetLastError());
         HITE_CHECK(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, stream));
     }
@@ -561,7 +386,7 @@ static int an_batch(hite_ctx *ctx, const AnTable &T, const std::vector<AnPiece> 
         AN_ALLOC(B, d_hits, hit_cap * 8);
         HITE_CHECK(ctx, hipMemsetAsync(d_cnt, 0, AN_C_N * 8, stream));
         const int tk = hite_prof_begin(ctx, "annot_hits", stream);
-        hipLaunchKernelGGL(an_hit_kernel, dim3(an_grid(nb)), dim3(256), 0, stream, d_seq, nb, d_pc, n_piece, T.d_keys, T.d_vals, T.nw, T.d_off, T.n_text,
+        hipLaunchKernelGGL(an_hit_kernel, dim3(grid256(nb)), dim3(256), 0, stream, d_seq, nb, d_pc, n_piece, T.d_keys, T.d_vals, T.nw, T.d_off, T.n_text,
                            d_hits, hit_cap, d_cnt);
         hite_prof_end(ctx, tk, stream);
         HITE_CHECK(ctx, hipGetLastError());
@@ -587,17 +412,17 @@ static int an_batch(hite_ctx *ctx, const AnTable &T, const std::vector<AnPiece> 
     if (rc) return rc;
     int64_t widest = 0;
     for (const AnPiece &P : pieces) widest = std::max<int64_t>(widest, P.end - P.begin);
-    const int pos_bits = an_bits((unsigned long long)(nb - 1));
-    const int bin_bits = an_bits((unsigned long long)((widest + HITE_ANNOT_MAX_LIB_LEN + HITE_ANNOT_LATTICE) >> HITE_ANNOT_BIN_SHIFT));
-    const int t_bits = an_bits((unsigned long long)(T.n_text - 1));
+    const int pos_bits = hsp_bits((unsigned long long)(nb - 1));
+    const int bin_bits = hsp_bits((unsigned long long)((widest + HITE_ANNOT_MAX_LIB_LEN + HITE_ANNOT_LATTICE) >> HITE_ANNOT_BIN_SHIFT));
+    const int t_bits = hsp_bits((unsigned long long)(T.n_text - 1));
     if (pos_bits + bin_bits + t_bits > 64) { snprintf(ctx->err, sizeof(ctx->err), "hite_annotate: a key of %d bits", pos_bits + bin_bits + t_bits); return HITE_EHIP; }
     HITE_CHECK(ctx, hipMemsetAsync(d_cnt, 0, AN_C_N * 8, stream));
     int tk = hite_prof_begin(ctx, "annot_runs", stream);
     for (int lam = 0; lam <= HITE_ANNOT_LATTICE; lam += HITE_ANNOT_LATTICE) {
-        hipLaunchKernelGGL(an_run_key_kernel, dim3(an_grid(nh)), dim3(256), 0, stream, d_hits, nh, d_pc, n_piece, lam, bin_bits, pos_bits, d_keys, d_vals);
+        hipLaunchKernelGGL(an_run_key_kernel, dim3(grid256(nh)), dim3(256), 0, stream, d_hits, nh, d_pc, n_piece, lam, bin_bits, pos_bits, d_keys, d_vals);
         HITE_CHECK(ctx, hipGetLastError());
         if ((rc = sorter_sort_bits(G.S, d_keys, d_vals, nh, 0, pos_bits + bin_bits + t_bits))) return rc;
-        hipLaunchKernelGGL(an_run_kernel, dim3(an_grid(nh)), dim3(256), 0, stream, d_keys, d_vals, nh, bin_bits, pos_bits, d_pc, n_piece, d_tasks, task_cap,
+        hipLaunchKernelGGL(an_run_kernel, dim3(grid256(nh)), dim3(256), 0, stream, d_keys, d_vals, nh, bin_bits, pos_bits, d_pc, n_piece, d_tasks, task_cap,
                            d_cnt);
         HITE_CHECK(ctx, hipGetLastError());
     }

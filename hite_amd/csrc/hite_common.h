@@ -148,6 +148,48 @@ __device__ __forceinline__ uint8_t comp_sym(uint8_t c) {
 #define HITE_DPP_WAVE_SHR1 0x138
 __device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, HITE_DPP_WAVE_SHR1, 0xF, 0xF, false); }
 
+// the last x in 0 .. n - 1 with off[x] <= p (off ascending, off[0] <= p): the sequence of a batch that holds byte p, given the
+// sequences' offsets -- empty ones share an offset with their successor and are stepped over
+template <class I>
+__device__ __forceinline__ I last_le(const int64_t *__restrict__ off, I n, int64_t p) {
+    I lo = 0, hi = n;          // off[lo] <= p < off[hi] (off[n] taken as +inf)
+    while (hi - lo > 1) {
+        const I mid = (lo + hi) >> 1;
+        if (off[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// adds the number of lanes with `flag` to *counter with one atomic per wavefront; returns the lane's place among them (every lane of
+// the wavefront must come here)
+__device__ __forceinline__ unsigned long long wave_take_flag(bool flag, unsigned long long *counter) {
+    const unsigned long long mask = __ballot(flag);
+    const int lane = lane_id();
+    unsigned long long base = 0;
+    if (lane == 0 && mask) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+    base = (unsigned long long)__shfl((long long)base, 0, 64);
+    return base + (unsigned long long)__popcll(mask & (((unsigned long long)1 << lane) - 1));
+}
+// adds v of every lane to *counter with one atomic per wavefront; returns the sum of the lanes before this one plus the counter's
+// value before (every lane of the wavefront must come here)
+__device__ __forceinline__ unsigned long long wave_take_count(unsigned v, unsigned long long *counter) {
+    const int lane = lane_id();
+    unsigned incl = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const unsigned y = __shfl_up(incl, s, 64);
+        if (lane >= s) incl += y;
+    }
+    const unsigned total = __shfl(incl, 63, 64);
+    unsigned long long base = 0;
+    if (lane == 0 && total) base = atomicAdd(counter, (unsigned long long)total);
+    base = (unsigned long long)__shfl((long long)base, 0, 64);
+    return base + (incl - v);
+}
+
+// blocks of 256 threads that give n items a thread each
+static inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
 // exclusive scan over the 256 threads of a block (s_tmp: >= 8 ints of LDS); returns the
 // exclusive prefix of v and the block total in *total.  Contains __syncthreads().
 __device__ __forceinline__ int block_excl_scan(int v, int *s_tmp, int *total) {

@@ -111,21 +111,11 @@ static bool heli_compile(const hite_lcv &r, bool tail, HeliPat *out) {
 }
 // <<< helitron_score
 
-// the sequence that holds byte i: the last s with off[s] <= i (empty sequences share an offset with their successor and are skipped)
-__device__ __forceinline__ int64_t heli_seq_of(const int64_t *__restrict__ off, int64_t n, int64_t i) {
-    int64_t lo = 0, hi = n;          // off[lo] <= i < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void heli_anchor_count_kernel(const uint8_t *__restrict__ s, const int64_t *__restrict__ off, int64_t n,
                                                                 int64_t nb, int32_t *__restrict__ cnt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nb) return;
-    const int64_t q = heli_seq_of(off, n, i);
+    const int64_t q = last_le(off, n, i);
     cnt[i] = __popc(heli_anchor_kinds(s, i, off[q], off[q + 1]));
 }
 
@@ -134,7 +124,7 @@ __global__ __launch_bounds__(256) void heli_anchor_fill_kernel(const uint8_t *__
                                                                int32_t *__restrict__ seq) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nb) return;
-    const int64_t q = heli_seq_of(off, n, i);
+    const int64_t q = last_le(off, n, i);
     const int k = heli_anchor_kinds(s, i, off[q], off[q + 1]);
     int64_t at = pos[i];
     for (int kind = 0; kind < 4; kind++)
@@ -296,8 +286,6 @@ __global__ __launch_bounds__(256) void heli_dense_kernel(const int64_t *__restri
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 #define HELI_ALLOC(ptr, bytes) HITE_CHECK(ctx, B.alloc(ptr, (size_t)(bytes)))
 
-static inline unsigned heli_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 struct HeliArgs {
     int64_t n; const int64_t *seq_off; int32_t n_head, n_tail; const hite_lcv *head, *tail;
 };
@@ -333,7 +321,7 @@ static int heli_score(hite_ctx *ctx, DevPool &B, const uint8_t *d_s, const std::
     if (!hp.empty()) HITE_CHECK(ctx, hipMemcpyAsync(d_hp, hp.data(), hp.size() * sizeof(HeliPat), hipMemcpyHostToDevice, st));
     if (!tp.empty()) HITE_CHECK(ctx, hipMemcpyAsync(d_tp, tp.data(), tp.size() * sizeof(HeliPat), hipMemcpyHostToDevice, st));
     int tk = hite_prof_begin(ctx, "heli_anchor_kernels", st);
-    hipLaunchKernelGGL(heli_anchor_count_kernel, dim3(heli_grid(nb)), dim3(256), 0, st, d_s, S->d_off, n, nb, d_cnt);
+    hipLaunchKernelGGL(heli_anchor_count_kernel, dim3(grid256(nb)), dim3(256), 0, st, d_s, S->d_off, n, nb, d_cnt);
     HITE_CHECK(ctx, hipGetLastError());
     int rc = scan_excl_buf<int32_t>(ctx, d_bs, d_cnt, nb, d_pos, st);
     if (rc) return rc;
@@ -345,7 +333,7 @@ static int heli_score(hite_ctx *ctx, DevPool &B, const uint8_t *d_s, const std::
     HELI_ALLOC(S->d_seq, A * 4);
     HELI_ALLOC(S->d_score, A * 4);
     if (A == 0) { hite_prof_end(ctx, tk, st); return HITE_OK; }
-    hipLaunchKernelGGL(heli_anchor_fill_kernel, dim3(heli_grid(nb)), dim3(256), 0, st, d_s, S->d_off, n, nb, d_pos, S->d_key, S->d_seq);
+    hipLaunchKernelGGL(heli_anchor_fill_kernel, dim3(grid256(nb)), dim3(256), 0, st, d_s, S->d_off, n, nb, d_pos, S->d_key, S->d_seq);
     hite_prof_end(ctx, tk, st);
     int64_t blocks = (A + HELI_WAVES - 1) / HELI_WAVES;
     if (blocks > 256 * 8) blocks = 256 * 8;
@@ -401,7 +389,7 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
         int tk = hite_prof_begin(ctx, "heli_list_kernels", st);
         for (int pass = 0; pass < 2; pass++) {
             const int32_t thr = pass ? tail_threshold : head_threshold;
-            hipLaunchKernelGGL(heli_flag_kernel, dim3(heli_grid(A)), dim3(256), 0, st, S.d_key, S.d_score, A, pass, thr, d_val);
+            hipLaunchKernelGGL(heli_flag_kernel, dim3(grid256(A)), dim3(256), 0, st, S.d_key, S.d_score, A, pass, thr, d_val);
             if ((rc = scan_excl_buf<int64_t>(ctx, d_bs, d_val, A, d_pre, st))) return rc;
             int64_t tot = 0;
             HITE_CHECK(ctx, hipMemcpyAsync(&tot, d_pre + A, 8, hipMemcpyDeviceToHost, st));
@@ -409,7 +397,7 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
             cnt[2 * pass] = tot & 0xFFFFFFFFll; cnt[2 * pass + 1] = tot >> 32;
             if ((rc = heli_list_alloc(ctx, B, cnt[2 * pass], &L[2 * pass]))) return rc;
             if ((rc = heli_list_alloc(ctx, B, cnt[2 * pass + 1], &L[2 * pass + 1]))) return rc;
-            hipLaunchKernelGGL(heli_list_kernel, dim3(heli_grid(A)), dim3(256), 0, st, S.d_key, S.d_score, S.d_seq, A, pass, thr, d_pre,
+            hipLaunchKernelGGL(heli_list_kernel, dim3(grid256(A)), dim3(256), 0, st, S.d_key, S.d_score, S.d_seq, A, pass, thr, d_pre,
                                L[2 * pass], L[2 * pass + 1]);
             HITE_CHECK(ctx, hipGetLastError());
         }
@@ -427,7 +415,7 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
         HELI_ALLOC(d_pre_m, (n_hm + 1) * 8);
         HELI_ALLOC(d_bs2, scan_tmp_elems(nh) * 8);
         tk = hite_prof_begin(ctx, "heli_pair_kernels", st);
-        hipLaunchKernelGGL(heli_pair_kernel, dim3(heli_grid(nh)), dim3(256), 0, st, L[0], n_hp, L[1], n_hm, L[2], n_tp, L[3], n_tm, S.d_off,
+        hipLaunchKernelGGL(heli_pair_kernel, dim3(grid256(nh)), dim3(256), 0, st, L[0], n_hp, L[1], n_hm, L[2], n_tp, L[3], n_tm, S.d_off,
                            len_min, len_max, d_partner, d_fp, d_fm);
         HITE_CHECK(ctx, hipGetLastError());
         if ((rc = scan_excl_buf<int32_t>(ctx, d_bs2, d_fp, n_hp, d_pre_p, st))) return rc;
@@ -443,7 +431,7 @@ extern "C" int hite_helitron_scan_dev(hite_ctx *ctx, int64_t n, const uint8_t *d
             HeliOut o;
             HELI_ALLOC(o.seq, w * 4); HELI_ALLOC(o.start, w * 4); HELI_ALLOC(o.end, w * 4);
             HELI_ALLOC(o.hscore, w * 4); HELI_ALLOC(o.tscore, w * 4); HELI_ALLOC(o.strand, w);
-            hipLaunchKernelGGL(heli_place_kernel, dim3(heli_grid(nh)), dim3(256), 0, st, L[0], n_hp, L[1], n_hm, L[2], L[3], S.d_off, d_partner,
+            hipLaunchKernelGGL(heli_place_kernel, dim3(grid256(nh)), dim3(256), 0, st, L[0], n_hp, L[1], n_hm, L[2], L[3], S.d_off, d_partner,
                                d_pre_p, d_pre_m, w, o);
             HITE_CHECK(ctx, hipGetLastError());
             HITE_CHECK(ctx, hipMemcpyAsync(seq_out, o.seq, (size_t)w * 4, hipMemcpyDeviceToHost, st));
@@ -514,7 +502,7 @@ extern "C" int hite_helitron_scores(hite_ctx *ctx, int64_t n, const uint8_t *seq
         HELI_ALLOC(d_dense, nb * 16);
         HITE_CHECK(ctx, hipMemsetAsync(d_dense, 0, (size_t)nb * 16, st));
         if (S.n_anchor > 0)
-            hipLaunchKernelGGL(heli_dense_kernel, dim3(heli_grid(S.n_anchor)), dim3(256), 0, st, S.d_key, S.d_seq, S.d_score, S.n_anchor,
+            hipLaunchKernelGGL(heli_dense_kernel, dim3(grid256(S.n_anchor)), dim3(256), 0, st, S.d_key, S.d_seq, S.d_score, S.n_anchor,
                                S.d_off, nb, d_dense);
         HITE_CHECK(ctx, hipGetLastError());
         HITE_CHECK(ctx, hipMemcpy(scores_out, d_dense, (size_t)nb * 16, hipMemcpyDeviceToHost));

@@ -13,22 +13,21 @@
 //      the other in gp, so the chains of equal (seq, bin) are those of the header's order (seq, bin, i) --, head flags and a scan give
 //      every hit its run, a segmented wavefront minimum / maximum of d gives one atomic per run and wavefront, one thread per run
 //      applies the hit count and the span limit and emits the run as a task;
-//   4. extension: ONE WAVEFRONT PER RUN in the lane layout of ph_align (hite_pairhsp.hip): 64 columns of a strip across the lanes,
-//      wave shifts for the neighbours, the last column of a strip in 2 x 192 LDS cells of the wavefront; the redo loop of the pads
-//      runs inside the wavefront.
-// The filters, the order and the duplicates (steps 5 and 6) are host code.  hite_pairhsp.hip is left as it is: this file carries its
-// own copy of the cell and of the strip routine.
+//   4. extension: ONE WAVEFRONT PER RUN through hsp_align (hite_hsp.h: the cell and the strip routine of hite_pair_hsps, which the
+//      word key and the word kernel of step 1 come from as well); the redo loop of the pads runs inside the wavefront.
+// The filters, the order and the duplicates (steps 5 and 6) are host code.
 #include "hite_common.h"
 #include "hite_hostbuf.h"
+#include "hite_hsp.h"
 #include "hite_sort.h"
 #include <algorithm>
 #include <new>
 #include <vector>
 
 #define LS_WAVES 4
-#define LS_BAND (HITE_LTRSCAN_BAND_BELOW + HITE_LTRSCAN_BAND_ABOVE)      // diagonals of the band
+static_assert(HITE_LTRSCAN_BAND_BELOW + HITE_LTRSCAN_BAND_ABOVE == HSP_BAND, "the band of a run is the band of hsp_align");
 #define LS_BATCH_BYTES ((int64_t)64 << 20)       // sequence bytes per batch ($HITE_LTRSCAN_BATCH_BYTES overrides)
-#define LS_NO_WORD ((unsigned long long)1 << 26)
+#define LS_NO_WORD ((unsigned long long)1 << 2 * HITE_LTRSCAN_WORD)      // what hsp_word_key gives a position without a word
 #define LS_WORD_BITS 27
 #define LS_OUT_WORDS 10                           // per run: seq, found, ls, le, rs, re, score, matches, columns, alignments
 #define LS_MAX_BLOCKS 2048
@@ -36,62 +35,13 @@
 #define __host__
 #endif
 
-// >>> ltrscan_cell
-// The cell of hite_pair_hsps, step 4 (a copy of the pairhsp_cell block of hite_pairhsp.hip).  A cell value (score, matches, columns,
-// q_start, s_start) is TWO words.  a = score * 2^40 + matches * 2^20 + columns, signed: matches and columns stay below 2^20 (a window
-// holds at most 3 * 8192 + 192 bases), so the integer order of a is the lexicographic order of the first three fields, a step is one
-// addition and "score <= 0" is a < 2^40.  b = q_start * 2^16 + s_start (both < 32 768): on equal a the smaller b wins.  The empty
-// value is (0, 0).
-#define LS_SCORE_ONE ((int64_t)1 << 40)
-#define LS_STEP_MATCH (HITE_PAIRHSP_MATCH * LS_SCORE_ONE + ((int64_t)1 << 20) + 1)
-#define LS_STEP_MISMATCH (HITE_PAIRHSP_MISMATCH * LS_SCORE_ONE + 1)
-#define LS_STEP_GAP (HITE_PAIRHSP_GAP * LS_SCORE_ONE + 1)
-struct LsVal { int64_t a; uint32_t b; };
-// a byte (either case) as a base code A 0 / C 1 / G 2 / T 3 / anything else 4
-__device__ __forceinline__ int ls_code(uint8_t c) {
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-__device__ __forceinline__ bool ls_better(int64_t a1, uint32_t b1, int64_t a2, uint32_t b2) { return a1 > a2 || (a1 == a2 && b1 < b2); }
-__device__ __forceinline__ LsVal ls_cell(LsVal diag, LsVal up, LsVal left, int ca, int cb, int i, int j) {
-    LsVal v;
-    v.a = diag.a + ((ca == cb && ca < 4) ? LS_STEP_MATCH : LS_STEP_MISMATCH);
-    v.b = diag.a == 0 ? ((uint32_t)i << 16 | (uint32_t)j) : diag.b;
-    const int64_t ua = up.a + LS_STEP_GAP, la = left.a + LS_STEP_GAP;
-    if (ls_better(ua, up.b, v.a, v.b)) { v.a = ua; v.b = up.b; }
-    if (ls_better(la, left.b, v.a, v.b)) { v.a = la; v.b = left.b; }
-    if (v.a < LS_SCORE_ONE) { v.a = 0; v.b = 0; }
-    return v;
-}
-// the best cell so far: its value and e = i * 2^16 + j; a later cell takes its place when its value is better, or equal at a smaller e
-struct LsBest { int64_t a; uint32_t b, e; };
-__device__ __forceinline__ bool ls_best_better(int64_t a, uint32_t b, uint32_t e, const LsBest &o) {
-    return a > o.a || (a == o.a && (b < o.b || (b == o.b && e < o.e)));
-}
-// <<< ltrscan_cell
-
 // >>> ltrscan_key
-// the word of 13 base codes (the first one in the highest bits), or LS_NO_WORD when one of them is not in ACGT
-__host__ __device__ __forceinline__ unsigned long long ls_word_key(const int *codes) {
-    unsigned long long w = 0;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < HITE_LTRSCAN_WORD; k++) { ok = ok && codes[k] < 4; w = w * 4 + (unsigned long long)(codes[k] & 3); }
-    return ok ? w : ((unsigned long long)1 << 26);
-}
 // a hit on lattice lam (0 or HITE_LTRSCAN_LATTICE) as one key: its bin above the pos_bits bits of its position in the batch
 __host__ __device__ __forceinline__ unsigned long long ls_hit_key(uint32_t gp, uint32_t d, int lam, int pos_bits) {
     return (((unsigned long long)d + (unsigned long long)lam) >> HITE_LTRSCAN_BIN_SHIFT) << pos_bits | (unsigned long long)gp;
 }
 __host__ __device__ __forceinline__ int64_t ls_key_pos(unsigned long long key, int pos_bits) { return (int64_t)(key & (((unsigned long long)1 << pos_bits) - 1)); }
 __host__ __device__ __forceinline__ int64_t ls_key_bin(unsigned long long key, int pos_bits) { return (int64_t)(key >> pos_bits); }
-// bits that hold every value 0 .. v
-__host__ __device__ __forceinline__ int ls_bits(unsigned long long v) { int b = 1; while (b < 64 && (v >> b) != 0) b++; return b; }
 // the pad of level k = 0 .. 3
 __host__ __device__ __forceinline__ int ls_pad(int k, int max_ltr) {
     const int p = k == 0 ? HITE_LTRSCAN_PAD_0 : k == 1 ? HITE_LTRSCAN_PAD_1 : k == 2 ? HITE_LTRSCAN_PAD_2 : max_ltr;
@@ -147,46 +97,6 @@ __host__ __device__ __forceinline__ bool ls_rec_same_place(const int32_t *x, con
 struct LsTask { int32_t seq, i_lo, i_hi, d_lo, d_hi; };      // a run: the sequence of the batch, positions inside it
 enum { LS_C_WORDS = 0, LS_C_HITS, LS_C_RUNS, LS_C_SPAN, LS_C_TASKS, LS_C_N };
 
-// the sequence of the batch that holds byte gp: the last q with off[q] <= gp (off[0] = 0 <= gp < off[n]; empty sequences are stepped over)
-__device__ __forceinline__ int ls_seq_of(const int64_t *__restrict__ off, int n, int64_t gp) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= gp) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// adds the number of lanes with `flag` to *counter with one atomic per wavefront; returns the lane's place among them (every lane of
-// the wavefront must come here)
-__device__ __forceinline__ unsigned long long ls_wave_take(bool flag, unsigned long long *counter) {
-    const unsigned long long mask = __ballot(flag);
-    const int lane = lane_id();
-    unsigned long long base = 0;
-    if (lane == 0 && mask) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
-    base = (unsigned long long)__shfl((long long)base, 0, 64);
-    return base + (unsigned long long)__popcll(mask & (((unsigned long long)1 << lane) - 1));
-}
-
-__global__ __launch_bounds__(256) void ls_word_kernel(const uint8_t *__restrict__ seqs, const int64_t *__restrict__ off, int n_seq, int64_t nb,
-                                                      unsigned long long *__restrict__ keys, unsigned *__restrict__ vals,
-                                                      unsigned long long *__restrict__ counters) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned long long key = LS_NO_WORD;
-    if (p < nb) {
-        const int q = ls_seq_of(off, n_seq, p);
-        if (p + HITE_LTRSCAN_WORD <= off[q + 1]) {
-            int codes[HITE_LTRSCAN_WORD];
-#pragma unroll
-            for (int k = 0; k < HITE_LTRSCAN_WORD; k++) codes[k] = ls_code(seqs[p + k]);
-            key = ls_word_key(codes);
-        }
-        keys[p] = key;
-        vals[p] = (unsigned)p;
-    }
-    (void)ls_wave_take(key != LS_NO_WORD, &counters[LS_C_WORDS]);
-}
-
 // entry e of the sorted words: the first of the next HITE_LTRSCAN_MAX_OCC entries of the same word and sequence at a distance >= dmin is
 // its link, a hit when the distance is <= dmax
 __global__ __launch_bounds__(256) void ls_link_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ vals, int64_t nb,
@@ -200,7 +110,7 @@ __global__ __launch_bounds__(256) void ls_link_kernel(const unsigned long long *
         const unsigned long long w = keys[e];
         if (w != LS_NO_WORD) {
             i = vals[e];
-            const int64_t end = off[ls_seq_of(off, n_seq, i) + 1];
+            const int64_t end = off[last_le(off, n_seq, i) + 1];
             for (int t = 1; t <= HITE_LTRSCAN_MAX_OCC; t++) {
                 if (e + t >= nb || keys[e + t] != w) break;
                 const int64_t j = vals[e + t];
@@ -210,7 +120,7 @@ __global__ __launch_bounds__(256) void ls_link_kernel(const unsigned long long *
             }
         }
     }
-    const unsigned long long at = ls_wave_take(hit, &counters[LS_C_HITS]);
+    const unsigned long long at = wave_take_flag(hit, &counters[LS_C_HITS]);
     if (hit) { hit_gp[at] = (unsigned)i; hit_d[at] = (unsigned)d; }      // at most one hit per entry: at < nb
 }
 
@@ -232,7 +142,7 @@ __global__ __launch_bounds__(256) void ls_head_kernel(const unsigned long long *
         const unsigned long long k = keys[h], kp = keys[h - 1];
         const int64_t gp = ls_key_pos(k, pos_bits), gpp = ls_key_pos(kp, pos_bits);
         head = ls_key_bin(k, pos_bits) != ls_key_bin(kp, pos_bits) || gp - gpp > HITE_LTRSCAN_GAP ||
-               off[ls_seq_of(off, n_seq, gp)] > gpp;
+               off[last_le(off, n_seq, gp)] > gpp;
     }
     flags[h] = head ? 1 : 0;
 }
@@ -277,103 +187,22 @@ __global__ __launch_bounds__(256) void ls_run_emit_kernel(const unsigned long lo
             counted = true;
             const int64_t g_lo = ls_key_pos(keys[a], pos_bits), g_hi = ls_key_pos(keys[b - 1], pos_bits);
             wide = g_hi - g_lo + HITE_LTRSCAN_WORD > max_ltr;
-            const int q = ls_seq_of(off, n_seq, g_lo);
+            const int q = last_le(off, n_seq, g_lo);
             T.seq = q; T.i_lo = (int32_t)(g_lo - off[q]); T.i_hi = (int32_t)(g_hi - off[q]); T.d_lo = d_lo[r]; T.d_hi = d_hi[r];
         }
     }
-    (void)ls_wave_take(counted, &counters[LS_C_RUNS]);
-    (void)ls_wave_take(wide, &counters[LS_C_SPAN]);
+    (void)wave_take_flag(counted, &counters[LS_C_RUNS]);
+    (void)wave_take_flag(wide, &counters[LS_C_SPAN]);
     const bool go = counted && !wide;
-    const unsigned long long at = ls_wave_take(go, &counters[LS_C_TASKS]);
+    const unsigned long long at = wave_take_flag(go, &counters[LS_C_TASKS]);
     if (go && (int64_t)at < task_cap) tasks[at] = T;
-}
-
-// lane l takes the value of lane l - 1 (wave_shr1), lane 0 gets 0 and the caller puts its own value there
-__device__ __forceinline__ LsVal ls_up1(LsVal v) {
-    LsVal r;
-    const uint32_t lo = (uint32_t)wave_shr1((int)(uint32_t)v.a), hi = (uint32_t)wave_shr1((int)(uint32_t)((uint64_t)v.a >> 32));
-    r.a = (int64_t)((uint64_t)hi << 32 | lo);
-    r.b = (uint32_t)wave_shr1((int)v.b);
-    return r;
-}
-
-__device__ __forceinline__ LsBest ls_wave_best(LsBest v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        LsBest y;
-        y.a = __shfl_xor((long long)v.a, d, 64);
-        y.b = __shfl_xor(v.b, d, 64);
-        y.e = __shfl_xor(v.e, d, 64);
-        if (ls_best_better(y.a, y.b, y.e, v)) v = y;
-    }
-    return v;
-}
-
-// The best cell of rows r0 .. r1 and columns c0 .. c1 (1-based, inside [1, m] x [1, n]) within the band dlo <= j - i <= dhi
-// (dhi - dlo < LS_BAND), by one wavefront; q / s: the bytes of the two windows; bnd_a / bnd_b: 2 x LS_BAND words of the wavefront.  The
-// strip routine of ph_align (hite_pairhsp.hip): lane l is on row first + d - 1 - l at step d; the cell above is the lane's own last
-// value, the cell to the left the last value of lane l - 1, the diagonal cell what lane l - 1 handed over one step earlier.  All lanes
-// return the same value; a == 0: no cell has a positive score.
-__device__ __forceinline__ LsBest ls_align(const uint8_t *q, int m, const uint8_t *s, int dlo, int dhi, int r0, int r1, int c0, int c1,
-                                           long long *bnd_a, uint32_t *bnd_b) {
-    const int lane = lane_id();
-    LsBest best = {0, 0, 0};
-    const int cs = max(c0, r0 + dlo), ce = min(c1, r1 + dhi);      // the columns the band reaches inside the rectangle
-    int buf = 0;
-    for (int js = cs; js <= ce; js += 64, buf ^= 1) {
-        const int nl = min(64, ce - js + 1);
-        const bool more = js + 64 <= ce;
-        const int first = max(r0, js - dhi), last = min(r1, js + nl - 1 - dlo);      // the rows where the band meets the strip
-        const int ib = first - 1, j = js + lane;
-        const int cb = lane < nl ? ls_code(s[j - 1]) : 4;
-        const long long *rd_a = bnd_a + (buf ^ 1) * LS_BAND;
-        const uint32_t *rd_b = bnd_b + (buf ^ 1) * LS_BAND;
-        long long *wr_a = bnd_a + buf * LS_BAND;
-        uint32_t *wr_b = bnd_b + buf * LS_BAND;
-        // V(row, js - 1): the last column of the strip before, the empty value outside the band or the rectangle
-        auto edge = [&](int row) {
-            LsVal v = {0, 0};
-            const int dd = js - 1 - row;
-            if (js > cs && row >= r0 && row <= r1 && dd >= dlo && dd <= dhi) { v.a = (int64_t)rd_a[dhi - dd]; v.b = rd_b[dhi - dd]; }
-            return v;
-        };
-        LsVal cur = {0, 0}, diag = {0, 0};
-        if (lane == 0) diag = edge(ib);
-        LsVal ahead = edge(ib + 1);      // lane 0's left neighbour of the next step
-        int ca = 4, a64 = 4;             // the lane's base of Q; Q[ib + 64 k + lane] of the current 64 rows
-        const int steps = last - ib + nl - 1;
-        for (int d = 1; d <= steps; d++) {
-            const int i = ib + d - lane;
-            if (((d - 1) & 63) == 0) {
-                const int r = ib + d + lane;
-                a64 = (r >= 1 && r <= m) ? ls_code(q[r - 1]) : 4;
-            }
-            const int a_new = __builtin_amdgcn_readlane(a64, (d - 1) & 63);      // the code of row ib + d
-            ca = wave_shr1(ca);
-            LsVal left = ls_up1(cur);
-            if (lane == 0) { ca = a_new; left = ahead; }
-            ahead = edge(ib + d + 1);
-            const bool on = lane < nl && i >= r0 && i <= r1 && j - i >= dlo && j - i <= dhi;
-            LsVal v = ls_cell(diag, cur, left, ca, cb, i, j);
-            diag = left;
-            if (!on) { v.a = 0; v.b = 0; }
-            cur = v;
-            if (on) {
-                const uint32_t e = (uint32_t)i << 16 | (uint32_t)j;
-                if (v.a > 0 && ls_best_better(v.a, v.b, e, best)) { best.a = v.a; best.b = v.b; best.e = e; }
-                if (more && lane == 63) { wr_a[dhi - (j - i)] = (long long)v.a; wr_b[dhi - (j - i)] = v.b; }
-            }
-        }
-        __threadfence_block();          // lane 0 of the next strip reads what lane 63 wrote
-    }
-    return ls_wave_best(best);
 }
 
 // wavefront per run: step 4 of the header with its redo loop
 __global__ __launch_bounds__(LS_WAVES * 64) void ls_extend_kernel(const LsTask *__restrict__ tasks, int64_t n_tasks, const uint8_t *__restrict__ seqs,
                                                                   const int64_t *__restrict__ off, int max_ltr, int32_t *__restrict__ out) {
-    __shared__ long long s_bnd_a[LS_WAVES][2 * LS_BAND];
-    __shared__ uint32_t s_bnd_b[LS_WAVES][2 * LS_BAND];
+    __shared__ long long s_bnd_a[LS_WAVES][2 * HSP_BAND];
+    __shared__ uint32_t s_bnd_b[LS_WAVES][2 * HSP_BAND];
     const int lane = lane_id(), w = wave_id();
     for (int64_t t = (int64_t)blockIdx.x * LS_WAVES + w; t < n_tasks; t += (int64_t)gridDim.x * LS_WAVES) {
         const LsTask T = tasks[t];
@@ -382,18 +211,18 @@ __global__ __launch_bounds__(LS_WAVES * 64) void ls_extend_kernel(const LsTask *
         const int64_t dc = ((int64_t)T.d_lo + T.d_hi) >> 1;
         int pl = 0, pr = 0, n_align = 0, found = 0;
         int64_t ls = 0, le = 0, rs = 0, re = 0;
-        LsBest h = {0, 0, 0};
+        HspBest h = {0, 0, 0};
         for (;;) {
             const LsWin W = ls_window(len, T.i_lo, T.i_hi, dc, pl, pr, max_ltr);
             const int m = (int)(W.qe - W.qb), n = (int)(W.se - W.sb);
             n_align++;
             found = 0;
             if (m < 1 || n < 1 || m >= HITE_PAIRHSP_MAX_LEN || n >= HITE_PAIRHSP_MAX_LEN) break;      // (m, n >= 1 by construction, < 32 768 by the limits)
-            h = ls_align(s + W.qb, m, s + W.sb, W.dlo, W.dlo + LS_BAND - 1, 1, m, 1, n, s_bnd_a[w], s_bnd_b[w]);
-            if ((int)(h.a >> 40) < HITE_PAIRHSP_MIN_SCORE) break;
+            h = hsp_align(s + W.qb, m, s + W.sb, W.dlo, W.dlo + HSP_BAND - 1, 1, m, 1, n, s_bnd_a[w], s_bnd_b[w]);
+            if (hsp_score(h.a) < HITE_PAIRHSP_MIN_SCORE) break;
             found = 1;
-            ls = W.qb + (int64_t)(h.b >> 16) - 1; le = W.qb + (int64_t)(h.e >> 16);
-            rs = W.sb + (int64_t)(h.b & 0xFFFFu) - 1; re = W.sb + (int64_t)(h.e & 0xFFFFu);
+            ls = W.qb + hsp_q_start(h.b) - 1; le = W.qb + hsp_q_end(h.e);
+            rs = W.sb + hsp_s_start(h.b) - 1; re = W.sb + hsp_s_end(h.e);
             const int step = ls_pad_steps(W, len, ls, le, pl, pr);
             if (step == 0 || n_align > HITE_LTRSCAN_MAX_REDO) break;
             pl += step & 1;
@@ -402,14 +231,13 @@ __global__ __launch_bounds__(LS_WAVES * 64) void ls_extend_kernel(const LsTask *
         if (lane == 0) {
             int32_t *o = out + t * LS_OUT_WORDS;
             o[0] = T.seq; o[1] = found; o[2] = (int32_t)ls; o[3] = (int32_t)le; o[4] = (int32_t)rs; o[5] = (int32_t)re;
-            o[6] = (int32_t)(h.a >> 40); o[7] = (int32_t)((h.a >> 20) & 0xFFFFF); o[8] = (int32_t)(h.a & 0xFFFFF); o[9] = n_align;
+            o[6] = hsp_score(h.a); o[7] = hsp_matches(h.a); o[8] = hsp_columns(h.a); o[9] = n_align;
         }
     }
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 #define LS_ALLOC(ptr, bytes) HITE_CHECK(ctx, B.alloc(ptr, (size_t)(bytes)))
-static inline unsigned ls_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 struct LsRec { int32_t f[8]; };
 
 // one batch: the sequences first .. last - 1 of the call, nb > 0 bytes in all; appends the unfiltered records, adds to st[0 .. 6]
@@ -438,7 +266,8 @@ static int ls_batch(hite_ctx *ctx, const uint8_t *seqs, const int64_t *seq_off, 
     if (rc) return rc;
 
     int tk = hite_prof_begin(ctx, "ltrscan_words", stream);
-    hipLaunchKernelGGL(ls_word_kernel, dim3(ls_grid(nb)), dim3(256), 0, stream, d_seq, d_off, n_seq, nb, d_keys, d_vals, d_cnt);
+    hipLaunchKernelGGL(hsp_word_kernel<HITE_LTRSCAN_WORD>, dim3(grid256(nb)), dim3(256), 0, stream, d_seq, d_off, n_seq, nb, d_keys, d_vals,
+                       d_cnt + LS_C_WORDS);
     hite_prof_end(ctx, tk, stream);
     HITE_CHECK(ctx, hipGetLastError());
     tk = hite_prof_begin(ctx, "ltrscan_word_sort", stream);
@@ -447,7 +276,7 @@ static int ls_batch(hite_ctx *ctx, const uint8_t *seqs, const int64_t *seq_off, 
     if (rc) return rc;
     const int64_t dmin = min_ltr, dmax = (int64_t)max_len - min_ltr;
     tk = hite_prof_begin(ctx, "ltrscan_links", stream);
-    hipLaunchKernelGGL(ls_link_kernel, dim3(ls_grid(nb)), dim3(256), 0, stream, d_keys, d_vals, nb, d_off, n_seq, dmin, dmax, d_hgp, d_hd, d_cnt);
+    hipLaunchKernelGGL(ls_link_kernel, dim3(grid256(nb)), dim3(256), 0, stream, d_keys, d_vals, nb, d_off, n_seq, dmin, dmax, d_hgp, d_hd, d_cnt);
     hite_prof_end(ctx, tk, stream);
     HITE_CHECK(ctx, hipGetLastError());
     unsigned long long h_cnt[LS_C_N];
@@ -468,14 +297,14 @@ static int ls_batch(hite_ctx *ctx, const uint8_t *seqs, const int64_t *seq_off, 
     LS_ALLOC(d_dlo, nh * 4);
     LS_ALLOC(d_dhi, nh * 4);
     LS_ALLOC(d_tasks, task_cap * sizeof(LsTask));
-    const int pos_bits = ls_bits((unsigned long long)(nb - 1));
-    const int bin_bits = ls_bits((unsigned long long)((std::max<int64_t>(dmax, 0) + HITE_LTRSCAN_LATTICE) >> HITE_LTRSCAN_BIN_SHIFT));
+    const int pos_bits = hsp_bits((unsigned long long)(nb - 1));
+    const int bin_bits = hsp_bits((unsigned long long)((std::max<int64_t>(dmax, 0) + HITE_LTRSCAN_LATTICE) >> HITE_LTRSCAN_BIN_SHIFT));
     tk = hite_prof_begin(ctx, "ltrscan_runs", stream);
     for (int lam = 0; lam <= HITE_LTRSCAN_LATTICE; lam += HITE_LTRSCAN_LATTICE) {
-        hipLaunchKernelGGL(ls_hit_key_kernel, dim3(ls_grid(nh)), dim3(256), 0, stream, d_hgp, d_hd, nh, lam, pos_bits, d_keys, d_vals);
+        hipLaunchKernelGGL(ls_hit_key_kernel, dim3(grid256(nh)), dim3(256), 0, stream, d_hgp, d_hd, nh, lam, pos_bits, d_keys, d_vals);
         HITE_CHECK(ctx, hipGetLastError());
         if ((rc = sorter_sort_bits(G.S, d_keys, d_vals, nh, 0, pos_bits + bin_bits))) return rc;
-        hipLaunchKernelGGL(ls_head_kernel, dim3(ls_grid(nh)), dim3(256), 0, stream, d_keys, nh, pos_bits, d_off, n_seq, d_flags);
+        hipLaunchKernelGGL(ls_head_kernel, dim3(grid256(nh)), dim3(256), 0, stream, d_keys, nh, pos_bits, d_off, n_seq, d_flags);
         HITE_CHECK(ctx, hipGetLastError());
         if ((rc = scan_excl_buf<int32_t>(ctx, d_bs, d_flags, nh, d_excl, stream))) return rc;
         int64_t n_runs = 0;
@@ -484,8 +313,8 @@ static int ls_batch(hite_ctx *ctx, const uint8_t *seqs, const int64_t *seq_off, 
         if (n_runs < 1 || n_runs > nh) { snprintf(ctx->err, sizeof(ctx->err), "hite_ltr_scan: %lld runs of %lld hits", (long long)n_runs, (long long)nh); return HITE_EHIP; }
         HITE_CHECK(ctx, hipMemsetAsync(d_dlo, 0x7f, (size_t)n_runs * 4, stream));
         HITE_CHECK(ctx, hipMemsetAsync(d_dhi, 0, (size_t)n_runs * 4, stream));
-        hipLaunchKernelGGL(ls_run_fill_kernel, dim3(ls_grid(nh)), dim3(256), 0, stream, d_vals, d_flags, d_excl, nh, n_runs, d_start, d_dlo, d_dhi);
-        hipLaunchKernelGGL(ls_run_emit_kernel, dim3(ls_grid(n_runs)), dim3(256), 0, stream, d_keys, pos_bits, d_start, d_dlo, d_dhi, n_runs, d_off,
+        hipLaunchKernelGGL(ls_run_fill_kernel, dim3(grid256(nh)), dim3(256), 0, stream, d_vals, d_flags, d_excl, nh, n_runs, d_start, d_dlo, d_dhi);
+        hipLaunchKernelGGL(ls_run_emit_kernel, dim3(grid256(n_runs)), dim3(256), 0, stream, d_keys, pos_bits, d_start, d_dlo, d_dhi, n_runs, d_off,
                            n_seq, (int)max_ltr, d_tasks, task_cap, d_cnt);
         HITE_CHECK(ctx, hipGetLastError());
     }

@@ -9,23 +9,19 @@
 //      a chain of positions; integer atomics, the counts do not depend on the order); every position of S looks its word up, passes the
 //      frequency cap and adds one to a bin of diagonals in LDS per occurrence;
 //   2. windows: wavefront 0 picks up to four bins (a wavefront maximum over packed (votes, lowest bin) keys per pick);
-//   3. alignment: WAVEFRONT w TAKES BAND w.  ph_align runs the recurrence of the header inside the band and a rectangle: the lanes are
-//      64 columns of a strip, lane l on row first + d - 1 - l at step d, so that the cell above is the lane's own last value, the cell to
-//      the left the last value of lane l - 1 and the diagonal cell what lane l - 1 handed over one step earlier (data-parallel moves, no
-//      LDS).  Only the rows where the band meets the strip are visited (at most 255).  The last column of a strip stays in LDS, indexed
-//      by its diagonal (192 values, two buffers in turn), and is what lane 0 of the next strip reads.  The wavefront then runs the
-//      rectangle before and the one after its first HSP through the same routine.
-// A cell value is two words: score, matches and columns in one signed 64-bit integer (one addition per step, one compare), the two
-// start coordinates in an unsigned 32-bit one that only ties look at.  The raw HSPs (at most 12 per pair) leave by ordinary vector
-// stores; the host orders them and applies the containment rule.
+//   3. alignment: WAVEFRONT w TAKES BAND w.  hsp_align (hite_hsp.h: the cell, the recurrence and the strip routine) runs the recurrence
+//      of the header inside the band and a rectangle.  The wavefront then runs the rectangle before and the one after its first HSP
+//      through the same routine.
+// The raw HSPs (at most 12 per pair) leave by ordinary vector stores; the host orders them and applies the containment rule.
 #include "hite_common.h"
 #include "hite_hostbuf.h"
+#include "hite_hsp.h"
 #include <algorithm>
 #include <new>
 #include <vector>
 
 #define PH_WAVES HITE_PAIRHSP_MAX_WINDOWS          // wavefront w aligns band w
-#define PH_BAND (HITE_PAIRHSP_BAND_BELOW + HITE_PAIRHSP_BAND_ABOVE)      // diagonals of a band
+static_assert(HITE_PAIRHSP_BAND_BELOW + HITE_PAIRHSP_BAND_ABOVE == HSP_BAND, "the band of a window is the band of hsp_align");
 #define PH_MAX_BINS (((2 * HITE_PAIRHSP_MAX_LEN - 2) >> HITE_PAIRHSP_BIN_SHIFT) + 2)
 #define PH_BATCH_PAIRS 8192                        // pairs per launch ($HITE_PAIRHSP_BATCH_PAIRS overrides: the tests run several batches)
 #define PH_BATCH_BYTES ((int64_t)64 << 20)         // interval bytes per launch
@@ -33,126 +29,7 @@
 #define PH_TABLE_BYTES ((size_t)256 << 20)         // all word tables of a launch together
 #define PH_OUT_WORDS (7 * HITE_PAIRHSP_MAX_HSPS)   // per pair: 4 bands x (first, before, after) x 7; score 0: no HSP there
 
-// >>> pairhsp_cell
-// A cell value (score, matches, columns, q_start, s_start) is TWO words.  a = score * 2^40 + matches * 2^20 + columns, signed: matches
-// <= 32 768 and columns <= 65 536 are never negative and stay below 2^20, so the integer order of a is the lexicographic order of the
-// first three fields, a step is one addition and "score <= 0" is a < 2^40.  b = q_start * 2^16 + s_start (both <= 32 768): on equal a
-// the smaller b wins.  The empty value is (0, 0).
-#define PH_SCORE_ONE ((int64_t)1 << 40)
-#define PH_STEP_MATCH (HITE_PAIRHSP_MATCH * PH_SCORE_ONE + ((int64_t)1 << 20) + 1)
-#define PH_STEP_MISMATCH (HITE_PAIRHSP_MISMATCH * PH_SCORE_ONE + 1)
-#define PH_STEP_GAP (HITE_PAIRHSP_GAP * PH_SCORE_ONE + 1)
-struct PhVal { int64_t a; uint32_t b; };
-// a byte (either case) as a base code A 0 / C 1 / G 2 / T 3 / anything else 4
-__device__ __forceinline__ int ph_code(uint8_t c) {
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-__device__ __forceinline__ bool ph_better(int64_t a1, uint32_t b1, int64_t a2, uint32_t b2) { return a1 > a2 || (a1 == a2 && b1 < b2); }
-// V(i, j) from diag = V(i-1, j-1), up = V(i-1, j), left = V(i, j-1); a path that leaves the empty value starts at (i, j) (only a
-// match can: every other step from the empty value has a score <= 0)
-__device__ __forceinline__ PhVal ph_cell(PhVal diag, PhVal up, PhVal left, int ca, int cb, int i, int j) {
-    PhVal v;
-    v.a = diag.a + ((ca == cb && ca < 4) ? PH_STEP_MATCH : PH_STEP_MISMATCH);
-    v.b = diag.a == 0 ? ((uint32_t)i << 16 | (uint32_t)j) : diag.b;
-    const int64_t ua = up.a + PH_STEP_GAP, la = left.a + PH_STEP_GAP;
-    if (ph_better(ua, up.b, v.a, v.b)) { v.a = ua; v.b = up.b; }
-    if (ph_better(la, left.b, v.a, v.b)) { v.a = la; v.b = left.b; }
-    if (v.a < PH_SCORE_ONE) { v.a = 0; v.b = 0; }
-    return v;
-}
-// the best cell so far: its value and e = i * 2^16 + j; a later cell takes its place when its value is better, or equal at a smaller e
-struct PhBest { int64_t a; uint32_t b, e; };
-__device__ __forceinline__ bool ph_best_better(int64_t a, uint32_t b, uint32_t e, const PhBest &o) {
-    return a > o.a || (a == o.a && (b < o.b || (b == o.b && e < o.e)));
-}
-// <<< pairhsp_cell
-
 struct PhTask { int64_t q0, s0; int32_t m, n; };      // byte offsets of the two intervals in the batch's bytes
-
-// lane l takes the value of lane l - 1 (wave_shr1), lane 0 gets 0 and the caller puts its own value there
-__device__ __forceinline__ PhVal ph_up1(PhVal v) {
-    PhVal r;
-    const uint32_t lo = (uint32_t)wave_shr1((int)(uint32_t)v.a), hi = (uint32_t)wave_shr1((int)(uint32_t)((uint64_t)v.a >> 32));
-    r.a = (int64_t)((uint64_t)hi << 32 | lo);
-    r.b = (uint32_t)wave_shr1((int)v.b);
-    return r;
-}
-
-__device__ __forceinline__ PhBest ph_wave_best(PhBest v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        PhBest y;
-        y.a = __shfl_xor((long long)v.a, d, 64);
-        y.b = __shfl_xor(v.b, d, 64);
-        y.e = __shfl_xor(v.e, d, 64);
-        if (ph_best_better(y.a, y.b, y.e, v)) v = y;
-    }
-    return v;
-}
-
-// The best cell of rows r0 .. r1 and columns c0 .. c1 (1-based, inside [1, m] x [1, n]) within the band dlo <= j - i <= dhi
-// (dhi - dlo < PH_BAND), by one wavefront; q / s: the bytes of the two intervals; bnd_a / bnd_b: 2 x PH_BAND words of the wavefront.
-// All lanes return the same value; a == 0: no cell has a positive score.
-__device__ __forceinline__ PhBest ph_align(const uint8_t *q, int m, const uint8_t *s, int dlo, int dhi, int r0, int r1, int c0, int c1,
-                                           long long *bnd_a, uint32_t *bnd_b) {
-    const int lane = lane_id();
-    PhBest best = {0, 0, 0};
-    const int cs = max(c0, r0 + dlo), ce = min(c1, r1 + dhi);      // the columns the band reaches inside the rectangle
-    int buf = 0;
-    for (int js = cs; js <= ce; js += 64, buf ^= 1) {
-        const int nl = min(64, ce - js + 1);
-        const bool more = js + 64 <= ce;
-        const int first = max(r0, js - dhi), last = min(r1, js + nl - 1 - dlo);      // the rows where the band meets the strip
-        const int ib = first - 1, j = js + lane;
-        const int cb = lane < nl ? ph_code(s[j - 1]) : 4;
-        const long long *rd_a = bnd_a + (buf ^ 1) * PH_BAND;
-        const uint32_t *rd_b = bnd_b + (buf ^ 1) * PH_BAND;
-        long long *wr_a = bnd_a + buf * PH_BAND;
-        uint32_t *wr_b = bnd_b + buf * PH_BAND;
-        // V(row, js - 1): the last column of the strip before, the empty value outside the band or the rectangle
-        auto edge = [&](int row) {
-            PhVal v = {0, 0};
-            const int dd = js - 1 - row;
-            if (js > cs && row >= r0 && row <= r1 && dd >= dlo && dd <= dhi) { v.a = (int64_t)rd_a[dhi - dd]; v.b = rd_b[dhi - dd]; }
-            return v;
-        };
-        PhVal cur = {0, 0}, diag = {0, 0};
-        if (lane == 0) diag = edge(ib);
-        PhVal ahead = edge(ib + 1);      // lane 0's left neighbour of the next step
-        int ca = 4, a64 = 4;             // the lane's base of Q; Q[ib + 64 k + lane] of the current 64 rows
-        const int steps = last - ib + nl - 1;
-        for (int d = 1; d <= steps; d++) {
-            const int i = ib + d - lane;
-            if (((d - 1) & 63) == 0) {
-                const int r = ib + d + lane;
-                a64 = r <= m ? ph_code(q[r - 1]) : 4;
-            }
-            const int a_new = __builtin_amdgcn_readlane(a64, (d - 1) & 63);      // the code of row ib + d
-            ca = wave_shr1(ca);
-            PhVal left = ph_up1(cur);
-            if (lane == 0) { ca = a_new; left = ahead; }
-            ahead = edge(ib + d + 1);
-            const bool on = lane < nl && i >= r0 && i <= r1 && j - i >= dlo && j - i <= dhi;
-            PhVal v = ph_cell(diag, cur, left, ca, cb, i, j);
-            diag = left;
-            if (!on) { v.a = 0; v.b = 0; }
-            cur = v;
-            if (on) {
-                const uint32_t e = (uint32_t)i << 16 | (uint32_t)j;
-                if (v.a > 0 && ph_best_better(v.a, v.b, e, best)) { best.a = v.a; best.b = v.b; best.e = e; }
-                if (more && lane == 63) { wr_a[dhi - (j - i)] = (long long)v.a; wr_b[dhi - (j - i)] = v.b; }
-            }
-        }
-        __threadfence_block();          // lane 0 of the next strip reads what lane 63 wrote
-    }
-    return ph_wave_best(best);
-}
 
 // the word that begins at position i of the len bytes at p, or -1 (past the end, or a byte outside ACGT)
 __device__ __forceinline__ int ph_word(const uint8_t *p, int len, int i) {
@@ -160,7 +37,7 @@ __device__ __forceinline__ int ph_word(const uint8_t *p, int len, int i) {
     int w = 0;
 #pragma unroll
     for (int k = 0; k < HITE_PAIRHSP_WORD; k++) {
-        const int c = ph_code(p[i + k]);
+        const int c = hsp_code(p[i + k]);
         if (c > 3) return -1;
         w = w * 4 + c;
     }
@@ -168,14 +45,14 @@ __device__ __forceinline__ int ph_word(const uint8_t *p, int len, int i) {
 }
 __device__ __forceinline__ uint32_t ph_hash(int w) { return ((uint32_t)w * 2654435761u) >> 8; }
 
-__device__ __forceinline__ void ph_store(int32_t *o, const PhBest &h) {
-    const int score = (int)(h.a >> 40);
+__device__ __forceinline__ void ph_store(int32_t *o, const HspBest &h) {
+    const int score = hsp_score(h.a);
     if (score < HITE_PAIRHSP_MIN_SCORE) {
         for (int k = 0; k < 7; k++) o[k] = 0;
         return;
     }
-    o[0] = (int32_t)(h.b >> 16); o[1] = (int32_t)(h.e >> 16); o[2] = (int32_t)(h.b & 0xFFFFu); o[3] = (int32_t)(h.e & 0xFFFFu);
-    o[4] = score; o[5] = (int32_t)((h.a >> 20) & 0xFFFFF); o[6] = (int32_t)(h.a & 0xFFFFF);
+    o[0] = hsp_q_start(h.b); o[1] = hsp_q_end(h.e); o[2] = hsp_s_start(h.b); o[3] = hsp_s_end(h.e);
+    o[4] = score; o[5] = hsp_matches(h.a); o[6] = hsp_columns(h.a);
 }
 
 // tables: per workgroup table_words 32-bit words -- keys[slots] (word + 1; 0: free), count[slots], head[slots] (position + 1; 0: end),
@@ -185,8 +62,8 @@ __global__ __launch_bounds__(PH_WAVES * 64) void ph_pair_kernel(const PhTask *__
                                                                 int32_t *__restrict__ out) {
     __shared__ int s_vote[PH_MAX_BINS];
     __shared__ int s_band[PH_WAVES], s_nband;
-    __shared__ long long s_bnd_a[PH_WAVES][2 * PH_BAND];
-    __shared__ uint32_t s_bnd_b[PH_WAVES][2 * PH_BAND];
+    __shared__ long long s_bnd_a[PH_WAVES][2 * HSP_BAND];
+    __shared__ uint32_t s_bnd_b[PH_WAVES][2 * HSP_BAND];
     const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
     uint32_t *tb = tables + (size_t)blockIdx.x * table_words;
     for (int k = blockIdx.x; k < n_tasks; k += gridDim.x) {
@@ -261,18 +138,18 @@ __global__ __launch_bounds__(PH_WAVES * 64) void ph_pair_kernel(const PhTask *__
         }
         __syncthreads();
         int32_t *o = out + (size_t)k * PH_OUT_WORDS + w * 21;
-        PhBest h = {0, 0, 0}, before = {0, 0, 0}, after = {0, 0, 0};
+        HspBest h = {0, 0, 0}, before = {0, 0, 0}, after = {0, 0, 0};
         if (w < s_nband) {
             const int b = s_band[w];
             const int dlo = max((b << HITE_PAIRHSP_BIN_SHIFT) - HITE_PAIRHSP_BAND_BELOW - (m - 1), diag_min);
             const int dhi = (b << HITE_PAIRHSP_BIN_SHIFT) + HITE_PAIRHSP_BAND_ABOVE - 1 - (m - 1);
-            h = ph_align(q, m, s, dlo, dhi, 1, m, 1, n, s_bnd_a[w], s_bnd_b[w]);
-            if ((int)(h.a >> 40) >= HITE_PAIRHSP_MIN_SCORE) {
-                const int qs = (int)(h.b >> 16), ss = (int)(h.b & 0xFFFFu), qe = (int)(h.e >> 16), se = (int)(h.e & 0xFFFFu);
+            h = hsp_align(q, m, s, dlo, dhi, 1, m, 1, n, s_bnd_a[w], s_bnd_b[w]);
+            if (hsp_score(h.a) >= HITE_PAIRHSP_MIN_SCORE) {
+                const int qs = hsp_q_start(h.b), ss = hsp_s_start(h.b), qe = hsp_q_end(h.e), se = hsp_s_end(h.e);
                 if (qs - 1 >= HITE_PAIRHSP_MIN_RECT && ss - 1 >= HITE_PAIRHSP_MIN_RECT)
-                    before = ph_align(q, m, s, dlo, dhi, 1, qs - 1, 1, ss - 1, s_bnd_a[w], s_bnd_b[w]);
+                    before = hsp_align(q, m, s, dlo, dhi, 1, qs - 1, 1, ss - 1, s_bnd_a[w], s_bnd_b[w]);
                 if (m - qe >= HITE_PAIRHSP_MIN_RECT && n - se >= HITE_PAIRHSP_MIN_RECT)
-                    after = ph_align(q, m, s, dlo, dhi, qe + 1, m, se + 1, n, s_bnd_a[w], s_bnd_b[w]);
+                    after = hsp_align(q, m, s, dlo, dhi, qe + 1, m, se + 1, n, s_bnd_a[w], s_bnd_b[w]);
             }
         }
         if (lane == 0) {

@@ -146,16 +146,6 @@ __device__ __forceinline__ int prot_ungapped(const uint8_t *x, int lx, int i, co
 
 #define PROT_WAVES 4
 
-// largest k in [0, n) with off[k] <= v (off ascending, off[0] <= v)
-__device__ __forceinline__ int64_t prot_owner(const int64_t *__restrict__ off, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;          // off[lo] <= v < off[hi] (off[n] taken as +inf)
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ void prot_fill_tab(int8_t *tab) {
     for (int k = threadIdx.x; k < PROT_TABW * PROT_TABW; k += blockDim.x) {
         const int a = k / PROT_TABW, b = k % PROT_TABW;
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(256) void prot_translate_kernel(const uint8_t *__re
                                                              uint8_t *__restrict__ out) {
     const int64_t R = frame_off[n_frames];
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < R; r += (int64_t)gridDim.x * 256) {
-        const int64_t gf = prot_owner(frame_off, n_frames, r);
+        const int64_t gf = last_le(frame_off, n_frames, r);
         const int64_t q = gf / 6;
         const int f = (int)(gf % 6);
         const int64_t L = nt_off[q + 1] - nt_off[q], p = (f % 3) + 3 * (r - frame_off[gf]);
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(256) void prot_kmer_kernel(const uint8_t *__restric
                                                         unsigned *__restrict__ vals, int32_t *__restrict__ cnt) {
     const int64_t N = aa_off[n_prot];
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < N; g += (int64_t)gridDim.x * 256) {
-        const int64_t p = prot_owner(aa_off, n_prot, g);
+        const int64_t p = last_le(aa_off, n_prot, g);
         prot_of[g] = (int32_t)p;
         int key = -1;
         if (g + 3 < aa_off[p + 1]) key = prot_seed_key(aa[g], aa[g + 1], aa[g + 2], aa[g + 3]);
@@ -209,7 +199,7 @@ __global__ __launch_bounds__(256) void prot_seed_count_kernel(const uint8_t *__r
                                                               int32_t *__restrict__ cnt_out) {
     const int64_t R = frame_off[n_frames];
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < R; r += (int64_t)gridDim.x * 256) {
-        const int64_t gf = prot_owner(frame_off, n_frames, r);
+        const int64_t gf = last_le(frame_off, n_frames, r);
         int key = -1;
         if (r + 3 < frame_off[gf + 1]) key = prot_seed_key(fr[r], fr[r + 1], fr[r + 2], fr[r + 3]);
         key_out[r] = key;
@@ -229,9 +219,9 @@ __global__ __launch_bounds__(256) void prot_ungapped_kernel(ProtUngapArgs a) {
     __shared__ int8_t tab[PROT_TABW * PROT_TABW];
     prot_fill_tab(tab);
     for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < a.n_hits; h += (int64_t)gridDim.x * 256) {
-        const int64_t r = prot_owner(a.hit_off, a.n_res, h);
+        const int64_t r = last_le(a.hit_off, a.n_res, h);
         const int64_t g = a.ent[a.dir[a.key[r]] + (h - a.hit_off[r])];
-        const int64_t gf = prot_owner(a.frame_off, a.n_frames, r);
+        const int64_t gf = last_le(a.frame_off, a.n_frames, r);
         const int32_t p = a.prot_of[g];
         const int i = (int)(r - a.frame_off[gf]), j = (int)(g - a.aa_off[p]);
         const int lx = (int)(a.frame_off[gf + 1] - a.frame_off[gf]), ly = (int)(a.aa_off[p + 1] - a.aa_off[p]);

@@ -1,118 +1,55 @@
-"""CPU-only: the integer-only parts of the genome annotation (hite_amd/csrc/hite_annotate.hip, the blocks between `// >>> annotate_cell`,
-`// >>> annotate_key`, `// >>> annotate_resolve` and their `// <<<` lines) compiled for the HOST, as tests/test_host_compiled_ltrscan.py
-does for the LTR scan: the cell inside a host copy of the kernel's strip loop and of its redo loop against the twin's step 4 on the
-runs of the small cases, the word code, the packed hit and the sort key against the twin's words and its order of the hits, the chain
-walk against the twin's runs, the resolve against the twin's.  What only the device has -- the sort, the compaction, the look-up,
-the data-parallel moves, the batches -- is left to tests/test_gpu_annotate.py."""
+"""CPU-only: the integer-only parts of the genome annotation (hite_amd/csrc/hite_annotate.hip, the blocks between `// >>> annotate_key`,
+`// >>> annotate_resolve` and their `// <<<` lines, with the `hsp_cell` and `hsp_key` blocks of hite_hsp.h) compiled for the HOST, as
+tests/test_host_compiled_ltrscan.py does for the LTR scan: the cell inside the host copy of the strip loop (tests/hsp_host.py) and of
+the kernel's redo loop against the twin's step 4 on the runs of the small cases, the word code, the packed hit and the sort key
+against the twin's words and its order of the hits, the chain walk against the twin's runs, the resolve against the twin's.  What only
+the device has -- the sort, the compaction, the look-up, the data-parallel moves, the batches -- is left to tests/test_gpu_annotate.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import annotate_cases as AC
 import annotate_twin as AT
+import hsp_host as H
 import pairhsp_twin as PT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-PRELUDE = r"""
-#include <stdint.h>
-#include <string.h>
-#include <algorithm>
-#include <vector>
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#include "hite_gpu.h"
-#define AN_BAND (HITE_ANNOT_BAND_BELOW + HITE_ANNOT_BAND_ABOVE)
-"""
+ROOT = H.ROOT
 
 WRAPPER = r"""
-// the strip loop of an_align, lane by lane
-static AnBest host_align(const uint8_t *q, int m, const uint8_t *s, int dlo, int dhi, int r0, int r1, int c0, int c1) {
-    static int64_t bnd_a[2 * AN_BAND];
-    static uint32_t bnd_b[2 * AN_BAND];
-    AnBest best = {0, 0, 0};
-    const int cs = std::max(c0, r0 + dlo), ce = std::min(c1, r1 + dhi);
-    int buf = 0;
-    for (int js = cs; js <= ce; js += 64, buf ^= 1) {
-        const int nl = std::min(64, ce - js + 1);
-        const bool more = js + 64 <= ce;
-        const int first = std::max(r0, js - dhi), last = std::min(r1, js + nl - 1 - dlo);
-        const int ib = first - 1;
-        const int64_t *rd_a = bnd_a + (buf ^ 1) * AN_BAND;
-        const uint32_t *rd_b = bnd_b + (buf ^ 1) * AN_BAND;
-        auto edge = [&](int row) {
-            AnVal v = {0, 0};
-            const int dd = js - 1 - row;
-            if (js > cs && row >= r0 && row <= r1 && dd >= dlo && dd <= dhi) { v.a = rd_a[dhi - dd]; v.b = rd_b[dhi - dd]; }
-            return v;
-        };
-        AnVal cur[64], diag[64], left[64];
-        int ca[64], cb[64];
-        for (int lane = 0; lane < 64; lane++) {
-            cur[lane] = diag[lane] = AnVal{0, 0};
-            ca[lane] = 4;
-            cb[lane] = lane < nl ? an_code(s[js + lane - 1]) : 4;
-        }
-        diag[0] = edge(ib);
-        const int steps = last - ib + nl - 1;
-        for (int d = 1; d <= steps; d++) {
-            for (int lane = 63; lane >= 1; lane--) { left[lane] = cur[lane - 1]; ca[lane] = ca[lane - 1]; }
-            left[0] = edge(ib + d);
-            ca[0] = ib + d <= m ? an_code(q[ib + d - 1]) : 4;
-            for (int lane = 0; lane < 64; lane++) {
-                const int i = ib + d - lane, j = js + lane;
-                const bool on = lane < nl && i >= r0 && i <= r1 && j - i >= dlo && j - i <= dhi;
-                AnVal v = an_cell(diag[lane], cur[lane], left[lane], ca[lane], cb[lane], i, j);
-                diag[lane] = left[lane];
-                if (!on) v = AnVal{0, 0};
-                cur[lane] = v;
-                if (on) {
-                    const uint32_t e = (uint32_t)i << 16 | (uint32_t)j;
-                    if (v.a > 0 && an_best_better(v.a, v.b, e, best)) { best.a = v.a; best.b = v.b; best.e = e; }
-                    if (more && lane == 63) { bnd_a[buf * AN_BAND + dhi - (j - i)] = v.a; bnd_b[buf * AN_BAND + dhi - (j - i)] = v.b; }
-                }
-            }
-        }
-    }
-    return best;
-}
-
 // the redo loop of an_extend_kernel on one run: q the text of L bytes, s the sequence of len bytes;
 // out = found, gs, ge, qs, qe, score, matches, columns, alignments
 extern "C" void host_extend(const uint8_t *q, int64_t L, const uint8_t *s, int64_t len, int g_lo, int g_hi, int d_lo, int d_hi, int32_t *out) {
     const int64_t dc = ((int64_t)d_lo + d_hi) >> 1;
     int pl = 0, pr = 0, n_align = 0, found = 0;
     int64_t qs = 0, qe = 0, gs = 0, ge = 0;
-    AnBest h = {0, 0, 0};
+    HspBest h = {0, 0, 0};
     for (;;) {
         const AnWin W = an_window(L, len, g_lo, g_hi, dc, pl, pr);
         const int m = (int)(W.qe - W.qb), n = (int)(W.se - W.sb);
         n_align++;
         found = 0;
         if (m < 1 || n < 1 || m >= HITE_PAIRHSP_MAX_LEN || n >= HITE_PAIRHSP_MAX_LEN) break;
-        h = host_align(q + W.qb, m, s + W.sb, W.dlo, W.dlo + AN_BAND - 1, 1, m, 1, n);
-        if ((int)(h.a >> 40) < HITE_PAIRHSP_MIN_SCORE) break;
+        h = host_align(q + W.qb, m, s + W.sb, W.dlo, W.dlo + HSP_BAND - 1, 1, m, 1, n);
+        if (hsp_score(h.a) < HITE_PAIRHSP_MIN_SCORE) break;
         found = 1;
-        qs = W.qb + (int64_t)(h.b >> 16) - 1; qe = W.qb + (int64_t)(h.e >> 16);
-        gs = W.sb + (int64_t)(h.b & 0xFFFFu) - 1; ge = W.sb + (int64_t)(h.e & 0xFFFFu);
+        qs = W.qb + hsp_q_start(h.b) - 1; qe = W.qb + hsp_q_end(h.e);
+        gs = W.sb + hsp_s_start(h.b) - 1; ge = W.sb + hsp_s_end(h.e);
         const int step = an_pad_steps(W, L, qs, qe, pl, pr);
         if (step == 0 || n_align > HITE_ANNOT_MAX_REDO) break;
         pl += step & 1;
         pr += step >> 1;
     }
     out[0] = found; out[1] = (int32_t)gs; out[2] = (int32_t)ge; out[3] = (int32_t)qs; out[4] = (int32_t)qe;
-    out[5] = (int32_t)(h.a >> 40); out[6] = (int32_t)((h.a >> 20) & 0xFFFFF); out[7] = (int32_t)(h.a & 0xFFFFF); out[8] = n_align;
+    out[5] = hsp_score(h.a); out[6] = hsp_matches(h.a); out[7] = hsp_columns(h.a); out[8] = n_align;
 }
 
 extern "C" uint64_t host_word_key(const uint8_t *p) {
     int codes[HITE_ANNOT_WORD];
-    for (int k = 0; k < HITE_ANNOT_WORD; k++) codes[k] = an_code(p[k]);
-    return an_word_key(codes);
+    for (int k = 0; k < HITE_ANNOT_WORD; k++) codes[k] = hsp_code(p[k]);
+    return hsp_word_key<HITE_ANNOT_WORD>(codes);
 }
 extern "C" void host_revcomp(const uint8_t *p, int64_t n, uint8_t *out) { for (int64_t k = 0; k < n; k++) out[k] = an_comp(p[n - 1 - k]); }
 extern "C" uint64_t host_hit_pack(uint32_t t, uint32_t q, uint32_t gp) { return an_hit_pack(t, q, gp); }
@@ -123,7 +60,7 @@ extern "C" uint32_t host_diag(int64_t g_rel, uint32_t q) { return an_diag(g_rel,
 extern "C" uint64_t host_run_key(uint32_t t, uint32_t diag, uint32_t gp, int lam, int bin_bits, int pos_bits) { return an_run_key(t, diag, gp, lam, bin_bits, pos_bits); }
 extern "C" int64_t host_key_pos(uint64_t key, int pos_bits) { return an_key_pos(key, pos_bits); }
 extern "C" uint64_t host_key_group(uint64_t key, int pos_bits) { return an_key_group(key, pos_bits); }
-extern "C" int host_bits(uint64_t v) { return an_bits(v); }
+extern "C" int host_bits(uint64_t v) { return hsp_bits(v); }
 extern "C" int host_pad(int k) { return an_pad(k); }
 
 // the walk of an_run_kernel over n hits of one (piece, t, bin) in ascending g: out gets (g_first, g_last, d_lo, d_hi, hits) per run
@@ -158,18 +95,8 @@ extern "C" int64_t host_resolve(int64_t n, int32_t *recs, int64_t *dup, int64_t 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    src = open(os.path.join(ROOT, "hite_amd", "csrc", "hite_annotate.hip")).read()
-    blocks = []
-    for name in ("cell", "key", "resolve"):
-        m = re.search(r"// >>> annotate_%s.*?\n(.*?)// <<< annotate_%s" % (name, name), src, re.S)
-        assert m, name
-        blocks.append(m.group(1))
-    d = tmp_path_factory.mktemp("annotate_host")
-    cpp, so = d / "an.cpp", d / "an.so"
-    cpp.write_text(PRELUDE + "".join(blocks) + WRAPPER)
-    extra = os.environ.get("HITE_HOST_CXXFLAGS", "").split()
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include")] + extra + ["-o", str(so), str(cpp)], check=True)
-    lb = C.CDLL(str(so))
+    src = H.blocks("hite_hsp.h", "hsp_cell", "hsp_key") + H.blocks("hite_annotate.hip", "annotate_key", "annotate_resolve")
+    lb = H.compile_host(tmp_path_factory.mktemp("annotate_host"), "an", src + H.HOST_ALIGN + WRAPPER)
     for f in ("host_word_key", "host_hit_pack", "host_run_key", "host_key_group"):
         getattr(lb, f).restype = C.c_uint64
     for f in ("host_key_pos", "host_chains", "host_resolve"):
@@ -181,18 +108,6 @@ def lib(tmp_path_factory):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
-
-
-def test_the_cell_is_the_one_of_the_pair_search():
-    """the block is a copy of pairhsp_cell: the same text but for the names"""
-    def block(path, name):
-        src = open(os.path.join(ROOT, "hite_amd", "csrc", path)).read()
-        code = re.search(r"// >>> %s.*?\n(.*?)// <<< %s" % (name, name), src, re.S).group(1)
-        code = "\n".join(ln for ln in code.splitlines() if not ln.lstrip().startswith("//"))
-        return re.sub(r"\s+", " ", code)
-
-    ours = block("hite_annotate.hip", "annotate_cell").replace("AN_", "PH_").replace("An", "Ph").replace("an_", "ph_")
-    assert ours == block("hite_pairhsp.hip", "pairhsp_cell")
 
 
 def test_header_constants_are_the_twin_s():

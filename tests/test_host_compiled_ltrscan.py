@@ -1,120 +1,55 @@
-"""CPU-only: the integer-only parts of the LTR candidate scan (hite_amd/csrc/hite_ltrscan.hip, the blocks between `// >>> ltrscan_cell`,
-`// >>> ltrscan_key`, `// >>> ltrscan_filter` and their `// <<<` lines) compiled for the HOST, as tests/test_host_compiled_pairhsp.py
-does for the pair search: the cell inside a host copy of the kernel's strip loop and of its redo loop against the twin's step 4 on
-the runs of the small cases, the word and hit keys against the twin's words and its order of the hits, the filter and the record
-order against the twin's.  What only the device has -- the sort, the compaction, the segmented scan, the data-parallel moves, the
-batches -- is left to tests/test_gpu_ltrscan.py."""
+"""CPU-only: the integer-only parts of the LTR candidate scan (hite_amd/csrc/hite_ltrscan.hip, the blocks between `// >>> ltrscan_key`,
+`// >>> ltrscan_filter` and their `// <<<` lines, with the `hsp_cell` and `hsp_key` blocks of hite_hsp.h) compiled for the HOST, as
+tests/test_host_compiled_pairhsp.py does for the pair search: the cell inside the host copy of the strip loop (tests/hsp_host.py) and
+of the kernel's redo loop against the twin's step 4 on the runs of the small cases, the word and hit keys against the twin's words and
+its order of the hits, the filter and the record order against the twin's.  What only the device has -- the sort, the compaction, the
+segmented scan, the data-parallel moves, the batches -- is left to tests/test_gpu_ltrscan.py."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import hsp_host as H
 import ltrscan_cases as LC
 import ltrscan_twin as LT
 import pairhsp_twin as PT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-PRELUDE = r"""
-#include <stdint.h>
-#include <algorithm>
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#include "hite_gpu.h"
-#define LS_BAND (HITE_LTRSCAN_BAND_BELOW + HITE_LTRSCAN_BAND_ABOVE)
-"""
-
 WRAPPER = r"""
-// the strip loop of ls_align, lane by lane
-static LsBest host_align(const uint8_t *q, int m, const uint8_t *s, int dlo, int dhi, int r0, int r1, int c0, int c1) {
-    static int64_t bnd_a[2 * LS_BAND];
-    static uint32_t bnd_b[2 * LS_BAND];
-    LsBest best = {0, 0, 0};
-    const int cs = std::max(c0, r0 + dlo), ce = std::min(c1, r1 + dhi);
-    int buf = 0;
-    for (int js = cs; js <= ce; js += 64, buf ^= 1) {
-        const int nl = std::min(64, ce - js + 1);
-        const bool more = js + 64 <= ce;
-        const int first = std::max(r0, js - dhi), last = std::min(r1, js + nl - 1 - dlo);
-        const int ib = first - 1;
-        const int64_t *rd_a = bnd_a + (buf ^ 1) * LS_BAND;
-        const uint32_t *rd_b = bnd_b + (buf ^ 1) * LS_BAND;
-        auto edge = [&](int row) {
-            LsVal v = {0, 0};
-            const int dd = js - 1 - row;
-            if (js > cs && row >= r0 && row <= r1 && dd >= dlo && dd <= dhi) { v.a = rd_a[dhi - dd]; v.b = rd_b[dhi - dd]; }
-            return v;
-        };
-        LsVal cur[64], diag[64], left[64];
-        int ca[64], cb[64];
-        for (int lane = 0; lane < 64; lane++) {
-            cur[lane] = diag[lane] = LsVal{0, 0};
-            ca[lane] = 4;
-            cb[lane] = lane < nl ? ls_code(s[js + lane - 1]) : 4;
-        }
-        diag[0] = edge(ib);
-        const int steps = last - ib + nl - 1;
-        for (int d = 1; d <= steps; d++) {
-            for (int lane = 63; lane >= 1; lane--) { left[lane] = cur[lane - 1]; ca[lane] = ca[lane - 1]; }
-            left[0] = edge(ib + d);
-            ca[0] = ib + d <= m ? ls_code(q[ib + d - 1]) : 4;
-            for (int lane = 0; lane < 64; lane++) {
-                const int i = ib + d - lane, j = js + lane;
-                const bool on = lane < nl && i >= r0 && i <= r1 && j - i >= dlo && j - i <= dhi;
-                LsVal v = ls_cell(diag[lane], cur[lane], left[lane], ca[lane], cb[lane], i, j);
-                diag[lane] = left[lane];
-                if (!on) v = LsVal{0, 0};
-                cur[lane] = v;
-                if (on) {
-                    const uint32_t e = (uint32_t)i << 16 | (uint32_t)j;
-                    if (v.a > 0 && ls_best_better(v.a, v.b, e, best)) { best.a = v.a; best.b = v.b; best.e = e; }
-                    if (more && lane == 63) { bnd_a[buf * LS_BAND + dhi - (j - i)] = v.a; bnd_b[buf * LS_BAND + dhi - (j - i)] = v.b; }
-                }
-            }
-        }
-    }
-    return best;
-}
-
 // the redo loop of ls_extend_kernel on one run of a sequence of len bytes: out = found, ls, le, rs, re, score, matches, columns, alignments
 extern "C" void host_extend(const uint8_t *s, int64_t len, int i_lo, int i_hi, int d_lo, int d_hi, int max_ltr, int32_t *out) {
     const int64_t dc = ((int64_t)d_lo + d_hi) >> 1;
     int pl = 0, pr = 0, n_align = 0, found = 0;
     int64_t ls = 0, le = 0, rs = 0, re = 0;
-    LsBest h = {0, 0, 0};
+    HspBest h = {0, 0, 0};
     for (;;) {
         const LsWin W = ls_window(len, i_lo, i_hi, dc, pl, pr, max_ltr);
         const int m = (int)(W.qe - W.qb), n = (int)(W.se - W.sb);
         n_align++;
         found = 0;
         if (m < 1 || n < 1 || m >= HITE_PAIRHSP_MAX_LEN || n >= HITE_PAIRHSP_MAX_LEN) break;
-        h = host_align(s + W.qb, m, s + W.sb, W.dlo, W.dlo + LS_BAND - 1, 1, m, 1, n);
-        if ((int)(h.a >> 40) < HITE_PAIRHSP_MIN_SCORE) break;
+        h = host_align(s + W.qb, m, s + W.sb, W.dlo, W.dlo + HSP_BAND - 1, 1, m, 1, n);
+        if (hsp_score(h.a) < HITE_PAIRHSP_MIN_SCORE) break;
         found = 1;
-        ls = W.qb + (int64_t)(h.b >> 16) - 1; le = W.qb + (int64_t)(h.e >> 16);
-        rs = W.sb + (int64_t)(h.b & 0xFFFFu) - 1; re = W.sb + (int64_t)(h.e & 0xFFFFu);
+        ls = W.qb + hsp_q_start(h.b) - 1; le = W.qb + hsp_q_end(h.e);
+        rs = W.sb + hsp_s_start(h.b) - 1; re = W.sb + hsp_s_end(h.e);
         const int step = ls_pad_steps(W, len, ls, le, pl, pr);
         if (step == 0 || n_align > HITE_LTRSCAN_MAX_REDO) break;
         pl += step & 1;
         pr += step >> 1;
     }
     out[0] = found; out[1] = (int32_t)ls; out[2] = (int32_t)le; out[3] = (int32_t)rs; out[4] = (int32_t)re;
-    out[5] = (int32_t)(h.a >> 40); out[6] = (int32_t)((h.a >> 20) & 0xFFFFF); out[7] = (int32_t)(h.a & 0xFFFFF); out[8] = n_align;
+    out[5] = hsp_score(h.a); out[6] = hsp_matches(h.a); out[7] = hsp_columns(h.a); out[8] = n_align;
 }
 
 extern "C" uint64_t host_word_key(const uint8_t *p) {
     int codes[HITE_LTRSCAN_WORD];
-    for (int k = 0; k < HITE_LTRSCAN_WORD; k++) codes[k] = ls_code(p[k]);
-    return ls_word_key(codes);
+    for (int k = 0; k < HITE_LTRSCAN_WORD; k++) codes[k] = hsp_code(p[k]);
+    return hsp_word_key<HITE_LTRSCAN_WORD>(codes);
 }
 extern "C" uint64_t host_hit_key(uint32_t gp, uint32_t d, int lam, int pos_bits) { return ls_hit_key(gp, d, lam, pos_bits); }
 extern "C" int64_t host_key_pos(uint64_t key, int pos_bits) { return ls_key_pos(key, pos_bits); }
 extern "C" int64_t host_key_bin(uint64_t key, int pos_bits) { return ls_key_bin(key, pos_bits); }
-extern "C" int host_bits(uint64_t v) { return ls_bits(v); }
+extern "C" int host_bits(uint64_t v) { return hsp_bits(v); }
 extern "C" int host_pad(int k, int max_ltr) { return ls_pad(k, max_ltr); }
 extern "C" int host_filter(const int32_t *r, int min_len, int max_len, int min_ltr, int max_ltr, int identity) {
     return ls_filter(r, min_len, max_len, min_ltr, max_ltr, identity);
@@ -126,35 +61,13 @@ extern "C" int host_rec_same_place(const int32_t *x, const int32_t *y) { return 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    src = open(os.path.join(ROOT, "hite_amd", "csrc", "hite_ltrscan.hip")).read()
-    blocks = []
-    for name in ("cell", "key", "filter"):
-        m = re.search(r"// >>> ltrscan_%s.*?\n(.*?)// <<< ltrscan_%s" % (name, name), src, re.S)
-        assert m, name
-        blocks.append(m.group(1))
-    d = tmp_path_factory.mktemp("ltrscan_host")
-    cpp, so = d / "ls.cpp", d / "ls.so"
-    cpp.write_text(PRELUDE + "".join(blocks) + WRAPPER)
-    extra = os.environ.get("HITE_HOST_CXXFLAGS", "").split()
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include")] + extra + ["-o", str(so), str(cpp)], check=True)
-    lb = C.CDLL(str(so))
+    src = H.blocks("hite_hsp.h", "hsp_cell", "hsp_key") + H.blocks("hite_ltrscan.hip", "ltrscan_key", "ltrscan_filter")
+    lb = H.compile_host(tmp_path_factory.mktemp("ltrscan_host"), "ls", src + H.HOST_ALIGN + WRAPPER)
     for f in ("host_word_key", "host_hit_key"):
         getattr(lb, f).restype = C.c_uint64
     for f in ("host_key_pos", "host_key_bin"):
         getattr(lb, f).restype = C.c_int64
     return lb
-
-
-def test_the_cell_is_the_one_of_the_pair_search():
-    """the block is a copy of pairhsp_cell: the same text but for the names"""
-    def block(path, name):
-        src = open(os.path.join(ROOT, "hite_amd", "csrc", path)).read()
-        code = re.search(r"// >>> %s.*?\n(.*?)// <<< %s" % (name, name), src, re.S).group(1)
-        code = "\n".join(ln for ln in code.splitlines() if not ln.lstrip().startswith("//"))
-        return re.sub(r"\s+", " ", code)
-
-    ours = block("hite_ltrscan.hip", "ltrscan_cell").replace("LS_", "PH_").replace("Ls", "Ph").replace("ls_", "ph_")
-    assert ours == block("hite_pairhsp.hip", "pairhsp_cell")
 
 
 def test_strip_and_redo_loops_vs_twin_on_the_runs_of_the_small_cases(lib):
