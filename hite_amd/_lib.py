@@ -12,6 +12,7 @@ SO_PATH = os.path.join(_HERE, "libhite_gpu.so")
 HITE_TE = {"tir": 0, "helitron": 1, "non_ltr": 2}
 INFO = {0: "", 1: "nb", 2: "fl1", 3: "EXC"}
 HITE_SUBCLUSTER_CHUNK = 64   # include/hite_gpu.h: rows per chunk of hite_msa_subcluster
+LTRDEEP_PARAMS, LTRDEEP_ROWS, LTRDEEP_COLS, LTRDEEP_KMER = 40026, 100, 200, 3872   # include/hite_gpu.h: HITE_LTRDEEP_*
 
 
 class HiteError(RuntimeError):
@@ -48,6 +49,8 @@ def load():
         lib.hite_host_free.argtypes = [C.c_void_p]
         lib.hite_protein_lib_release.restype = None
         lib.hite_protein_lib_release.argtypes = [C.c_void_p]
+        lib.hite_ltr_model_release.restype = None
+        lib.hite_ltr_model_release.argtypes = [C.c_void_p]
         _lib = lib
     return _lib
 
@@ -108,7 +111,7 @@ class Context:
 
     def close(self):
         self.release_copy_index()
-        for lib in list(getattr(self, "_prot_libs", ())):      # before the context, like the copy-finder state
+        for lib in list(getattr(self, "_prot_libs", ())) + list(getattr(self, "_ltr_models", ())):      # before the context, like the copy-finder state
             lib.release()
         if getattr(self, "_pipe_state", None) is not None and getattr(self, "h", None):
             self.lib.hite_pipeline_release(self._pipe_state)
@@ -990,6 +993,54 @@ class Context:
             out.append(cls)
         return out
 
+    # ---- high-copy LTR vote of FiLTR's hybrid CNN (hite_ltr_deep) ---------------------------------------------------------------
+    def ltr_model(self, params):
+        """the canonical flat fp32 array of HITE_LTRDEEP_PARAMS parameters (util.ltr_model_params / util.load_ltr_model) -> a model
+        resident on the device (hite_ltr_model_build folds the batch norms); released with the context or by .release()"""
+        return LtrModel(self, params)
+
+    @staticmethod
+    def _ltr_deep_rows(matrices):
+        """matrices: {name: rows} or a list of them, a row being (left frame, right frame) or one string -> (bytes of the rows of
+        200, row offsets).  A matrix with a row that is not 200 wide goes up without rows: it is not scored."""
+        mats = list(matrices.values()) if isinstance(matrices, dict) else list(matrices)
+        flat, counts = [], []
+        for m in mats:
+            rb = [("".join(r) if isinstance(r, (tuple, list)) else r) for r in m]
+            rb = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in rb]
+            if any(len(r) != LTRDEEP_COLS for r in rb):
+                rb = []
+            flat.extend(rb)
+            counts.append(len(rb))
+        roff = np.zeros(len(mats) + 1, dtype=np.int64)
+        np.cumsum(counts, out=roff[1:])
+        return np.frombuffer(b"".join(flat) + b"\0" * 16, dtype=np.uint8), roff
+
+    def ltr_deep(self, model, matrices, pooled=False):
+        """the two logits of FiLTR's hybrid CNN for every matrix (in the order of `matrices`): float32 [n, 2], (with pooled=True the
+        64 pooled values [n, 64],) int8 status [n]: 0 scored, 1 not scored (fewer than 5 or more than 100 rows, or a row that is not
+        200 wide; its logits are 0).  include/hite_gpu.h, "high-copy LTR vote"."""
+        buf, roff = self._ltr_deep_rows(matrices)
+        n = len(roff) - 1
+        logits = np.zeros((n, 2), dtype=np.float32)
+        pool = np.zeros((n, 64), dtype=np.float32)
+        status = np.zeros(n, dtype=np.int8)
+        self._check(self.lib.hite_ltr_deep(self.h, model.h, C.c_int64(n), _p(buf), _p(roff), _p(logits), _p(pool) if pooled else None,
+                                           _p(status)), "hite_ltr_deep")
+        return (logits, pool, status) if pooled else (logits, status)
+
+    def ltr_deep_features(self, matrices):
+        """the integer features of hite_ltr_deep by themselves: uint8 image [n, 3, 100, 200], int32 k-mer counts [n, 2, 3872], int8
+        status [n] (the features of a matrix that is not scored are 0)"""
+        buf, roff = self._ltr_deep_rows(matrices)
+        n = len(roff) - 1
+        img = np.zeros((n, 3, LTRDEEP_ROWS, LTRDEEP_COLS), dtype=np.uint8)
+        kmer = np.zeros((n, 2, LTRDEEP_KMER), dtype=np.int32)
+        status = np.zeros(n, dtype=np.int8)
+        self._check(self.lib.hite_ltr_deep_features(self.h, C.c_int64(n), _p(buf), _p(roff), _p(img), _p(kmer), _p(status)),
+                    "hite_ltr_deep_features")
+        return img, kmer, status
+
     def ltr_both_ends(self, alignments, cur_seqs, flank):
         """FiLTR get_both_ends_frame on a batch: alignments = lists of equal-length rows, cur_seqs = terminal sequences ->
         per alignment None (boundary not found) or (frames [(left, right)], full rows, new_start, new_end)"""
@@ -1252,3 +1303,26 @@ class ProteinLib:
         self.h = None
         if self in getattr(self.ctx, "_prot_libs", ()):
             self.ctx._prot_libs.remove(self)
+
+
+class LtrModel:
+    """the parameters of FiLTR's hybrid CNN resident on the device (hite_ltr_model_build): batch norms folded, weights laid out for
+    the convolution kernels"""
+
+    def __init__(self, ctx, params):
+        self.ctx = ctx
+        self.h = None
+        params = _arr(params, np.float32).reshape(-1)
+        h = C.c_void_p(None)
+        ctx._check(ctx.lib.hite_ltr_model_build(ctx.h, _p(params), C.c_int64(params.size), C.byref(h)), "hite_ltr_model_build")
+        self.h = h
+        if not hasattr(ctx, "_ltr_models"):
+            ctx._ltr_models = []
+        ctx._ltr_models.append(self)
+
+    def release(self):
+        if self.h is not None and getattr(self.ctx, "h", None):
+            self.ctx.lib.hite_ltr_model_release(self.h)
+        self.h = None
+        if self in getattr(self.ctx, "_ltr_models", ()):
+            self.ctx._ltr_models.remove(self)

@@ -92,6 +92,7 @@ struct hite_ctx {
     int64_t pairhsp_batch_pairs;      // pairs hite_pair_hsps sends up at a time ($HITE_PAIRHSP_BATCH_PAIRS; 0: its default)
     int64_t ltrscan_batch_bytes;      // sequence bytes hite_ltr_scan sends up at a time ($HITE_LTRSCAN_BATCH_BYTES; 0: its default)
     int64_t annot_batch_bytes;        // bases of pieces hite_annotate sends up at a time ($HITE_ANNOT_BATCH_BYTES; 0: its default)
+    int64_t ltrdeep_batch;            // candidates hite_ltr_deep takes at a time ($HITE_LTRDEEP_BATCH; 0: its default)
 };
 void hite_fmea_release(hite_ctx *ctx);
 int hite_aux_streams(hite_ctx *ctx, int k, hipStream_t *st, hipEvent_t *fork_ev, hipEvent_t *join_ev);

@@ -52,6 +52,10 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
         const long long v = strtoll(e, nullptr, 10);
         if (v >= 1 && v <= ((long long)1 << 26)) c->annot_batch_bytes = (int64_t)v;
     }
+    if (const char *e = getenv("HITE_LTRDEEP_BATCH")) {                 // test knob of hite_ltr_deep (hite_ltrdeep.hip)
+        const long long v = strtoll(e, nullptr, 10);
+        if (v >= 1 && v <= 4096) c->ltrdeep_batch = (int64_t)v;
+    }
     if (hipSetDevice(device_id) != hipSuccess) { free(c); return HITE_EHIP; }
     *out = c;
     return HITE_OK;

@@ -1915,17 +1915,178 @@ def _ltr_vote_batch(mats, flanking_len, window, frame_vote):
     return ok
 
 
+# ---- the high-copy vote of FiLTR's hybrid CNN (bin/FiLTR-main/src/Deep_Learning; LTR_filter.py:146-170 runs it on every matrix of more
+# than 5 rows, threshold 0.5) -- PINNED to the reference: Context.ltr_deep computes what include/hite_gpu.h defines ("high-copy LTR
+# vote"), tests/golden/ltr_deep.json.gz holds the reference's features, logits and decisions.  The trained weights are FiLTR's data and
+# are not shipped with the package (as head.lcvs is not): load_ltr_model finds them.  deep= replaces the device stage (the signature of
+# Context.ltr_deep; the CPU tests pass the twin with the flat parameter array as the model).
+def _ltr_model_spec():
+    """(state-dict key, shape) of every parameter in the canonical order of include/hite_gpu.h"""
+    bn = lambda key, c: [(key + "." + f, (c,)) for f in ("weight", "bias", "running_mean", "running_var")]  # noqa: E731
+    spec = []
+    for branch, c0 in (("model", 3), ("model_kmer", 2)):
+        for k, (cin, cout) in enumerate(((c0, 8), (8, 16), (16, 32))):
+            b = "%s.%d" % (branch, k)
+            spec += [(b + ".conv1.weight", (cout, cin, 3, 3))] + bn(b + ".bn1", cout) + [(b + ".conv2.weight", (cout, cout, 3, 3))] + bn(b + ".bn2", cout)
+            spec += [(b + ".shortcut.0.weight", (cout, cin, 1, 1))] + bn(b + ".shortcut.1", cout)
+    spec += [("fc_layers.0.weight", (16, 64)), ("fc_layers.0.bias", (16,))] + bn("fc_layers.1", 16)
+    spec += [("fc_layers.4.weight", (8, 16)), ("fc_layers.4.bias", (8,))] + bn("fc_layers.5", 8)
+    spec += [("fc_layers.8.weight", (2, 8)), ("fc_layers.8.bias", (2,))]
+    return spec
+
+
+LTR_MODEL_PARAMS = 40026        # HITE_LTRDEEP_PARAMS
+
+
+def ltr_model_params(state):
+    """the canonical flat float32 array (LTR_MODEL_PARAMS values) from {key: array} with the keys of the reference's state dict (class
+    CNNCAT; a `module.` prefix is stripped, the `num_batches_tracked` counters are not used); ValueError for a missing key or a wrong shape"""
+    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    parts = []
+    for key, shape in _ltr_model_spec():
+        if key not in state:
+            raise ValueError("ltr_model_params: no %r in the state dict" % key)
+        a = np.asarray(state[key], dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("ltr_model_params: %r has shape %r, not %r" % (key, a.shape, shape))
+        parts.append(a.reshape(-1))
+    flat = np.concatenate(parts)
+    assert flat.size == LTR_MODEL_PARAMS
+    return flat
+
+
+def ltr_model_state(params):
+    """the inverse of ltr_model_params: {key: float32 array} from the flat array"""
+    params = np.asarray(params, dtype=np.float32).reshape(-1)
+    if params.size != LTR_MODEL_PARAMS:
+        raise ValueError("ltr_model_state: %d values, not %d" % (params.size, LTR_MODEL_PARAMS))
+    state, at = {}, 0
+    for key, shape in _ltr_model_spec():
+        n = int(np.prod(shape))
+        state[key] = params[at:at + n].reshape(shape)
+        at += n
+    return state
+
+
+def _ltr_model_places(path=None):
+    places = [path, os.environ.get("HITE_LTR_MODEL")]
+    if os.environ.get("HITE_FILTR_DIR"):
+        places.append(os.path.join(os.environ["HITE_FILTR_DIR"], "models", "production_model.pth"))
+    return [p for p in places if p]
+
+
+def load_ltr_model(path=None):
+    """the flat parameter array of FiLTR's hybrid CNN from the first file that exists of: path, $HITE_LTR_MODEL,
+    $HITE_FILTR_DIR/models/production_model.pth; a `.npy` file holds the flat array, anything else is a checkpoint of the reference
+    (torch.load(..., weights_only=True)['model_state_dict']; torch is imported only then).  -> None when there is no such file."""
+    for p in _ltr_model_places(path):
+        if not os.path.isfile(p):
+            continue
+        if p.endswith(".npy"):
+            flat = np.load(p).astype(np.float32).reshape(-1)
+            if flat.size != LTR_MODEL_PARAMS:
+                raise ValueError("load_ltr_model: %s holds %d values, not %d" % (p, flat.size, LTR_MODEL_PARAMS))
+            return flat
+        import torch
+
+        ckpt = torch.load(p, map_location="cpu", weights_only=True)
+        return ltr_model_params({k: v.numpy() for k, v in ckpt["model_state_dict"].items()})
+    return None
+
+
+def ltr_deep_probs(matrices, model, ctx=None, deep=None):
+    """{name: probability of the LTR class} of the scored matrices of {name: rows}: ONE batched call of deep(model, matrices)
+    (Context.ltr_deep; model is a handle of Context.ltr_model or the flat parameter array), then 1 / (1 + exp(l0 - l1)) in binary64"""
+    names = list(matrices)
+    if not names:
+        return {}
+    own = None
+    if deep is None:
+        ctx = ctx or get_ctx()
+        deep = ctx.ltr_deep
+        if isinstance(model, np.ndarray):
+            model = own = ctx.ltr_model(model)
+    try:
+        logits, status = deep(model, [matrices[n] for n in names])
+    finally:
+        if own is not None:
+            own.release()
+    return {n: 1.0 / (1.0 + math.exp(float(l[0]) - float(l[1]))) for n, l, s in zip(names, np.asarray(logits, dtype=np.float64), status) if s == 0}
+
+
+def ltr_deep_votes(matrices, model, threshold=0.5, ctx=None, deep=None):
+    """hybridLTR_deep_main.py on {name: rows}: {name: 0 | 1} of the SCORED matrices only (5 .. 100 rows of 200 columns), 1 when the
+    probability of the LTR class is above threshold (CNNPredictor.predict_and_save)"""
+    return {n: 1 if p > threshold else 0 for n, p in ltr_deep_probs(matrices, model, ctx, deep).items()}
+
+
+def alter_deep_learning_results(deep_table, homology_table, high_copy_names):
+    """bin/FiLTR-main/src/Util.py:10711-10757 on dicts {name: 0 | 1}: both tables empty -> every high-copy name is 1; one empty -> the
+    other; else the model's table with 0 written for every name the homology rule answers 0.  A name the homology rule passes and
+    the model did not score is ABSENT from the result, as in the reference."""
+    if not deep_table and not homology_table:
+        return {n: 1 for n in high_copy_names}
+    if not deep_table:
+        return dict(homology_table)
+    if not homology_table:
+        return dict(deep_table)
+    out = dict(deep_table)
+    for n, is_ltr in homology_table.items():
+        if not is_ltr:
+            out[n] = is_ltr
+    return out
+
+
+def hybrid_ltr_deep(matrix_dir, model_path, output_dir, threshold=0.5, ctx=None, deep=None):
+    """the directory contract of hybridLTR_deep_main.py: every `*.matrix` of matrix_dir (its name up to the first '.') is scored in ONE
+    batched call; output_dir/is_LTR_deep.txt receives `name<TAB>0|1` and output_dir/deep_probs.csv `name<TAB>probability` of the
+    scored matrices, in the order of the names.  -> {name: 0 | 1}"""
+    model = load_ltr_model(model_path)
+    if model is None:
+        raise FileNotFoundError("hybrid_ltr_deep: no model at %r" % (model_path,))
+    mats = {}
+    for f in sorted(os.listdir(matrix_dir)):
+        if f.endswith(".matrix"):
+            with open(os.path.join(matrix_dir, f)) as fh:
+                mats[f.split(".")[0]] = [line.replace("\t", "").strip() for line in fh]
+    probs = ltr_deep_probs(mats, model, ctx, deep)
+    os.makedirs(output_dir, exist_ok=True)
+    votes = {n: 1 if p > threshold else 0 for n, p in probs.items()}
+    with open(os.path.join(output_dir, "is_LTR_deep.txt"), "w") as f:
+        for n, v in votes.items():
+            f.write("%s\t%d\n" % (n, v))
+    with open(os.path.join(output_dir, "deep_probs.csv"), "w") as f:
+        for n, p in probs.items():
+            f.write("%s\t%r\n" % (n, p))
+    return votes
+
+
+def _ltr_default_model(model):
+    """model, or with HITE_LTR_DEEP=gpu what load_ltr_model finds (an error when it finds nothing)"""
+    if model is None and os.environ.get("HITE_LTR_DEEP") == "gpu":
+        model = load_ltr_model()
+        if model is None:
+            raise FileNotFoundError("HITE_LTR_DEEP=gpu and no model: searched $HITE_LTR_MODEL (%r) and $HITE_FILTR_DIR/models/production_model.pth "
+                                    "($HITE_FILTR_DIR = %r); the path argument was not given" %
+                                    (os.environ.get("HITE_LTR_MODEL"), os.environ.get("HITE_FILTR_DIR")))
+    return model
+
+
 def ltr_flank_decide(matrices, flanking_len=100, ctx=None, cluster=None, frame_vote=None, copy_num_threshold=5, sliding_window_size=20,
-                     seconds=None):
+                     seconds=None, model=None, deep=None, threshold=0.5):
     """The decision rules of FiLTR's step 3 on `.matrix` contents, batched over all candidates: matrices = {name: [(left frame, right
     frame), ...]}.  In the reference's order: the sort rule (sort_matrix_dir), the joined-flank rule (filter_ltr_by_flanking_cluster),
     the split at copy_num_threshold rows (get_low_copy_LTR / get_high_copy_LTR; LTR_filter.py passes 5) and the frame vote on both
-    sides (judge_ltr_from_both_ends_frame), merged as alter_deep_learning_results does without a deep-learning table: the homology
-    rule alone.  cluster(groups, **options) and frame_vote(matrices, flank, window, side) default to ctx.frame_cluster and
-    ctx.ltr_frame (the CPU suite passes the twins).
+    sides (judge_ltr_from_both_ends_frame), merged as alter_deep_learning_results does.  Without a model (model=None and no
+    HITE_LTR_DEEP=gpu) there is no deep-learning table: the homology rule alone.  With one (the flat parameter array or a handle of
+    Context.ltr_model) the high-copy answers are alter_deep_learning_results(ltr_deep_votes(kept high-copy matrices), frame votes).
+    cluster(groups, **options), frame_vote(matrices, flank, window, side) and deep(model, matrices) default to ctx.frame_cluster,
+    ctx.ltr_frame and ctx.ltr_deep (the CPU suite passes the twins).
     -> ({name: (is_ltr, "low" | "high" | None, dropped_by)}, {name: kept matrix of every high-copy candidate}); dropped_by is None
-    for a true LTR, else "sort", "flank_cluster" or "frame_vote"."""
-    if cluster is None or frame_vote is None:
+    for a true LTR, else "sort", "flank_cluster", "frame_vote", "deep" (the model rejects what the homology rule passes) or
+    "deep_missing" (the homology rule passes it and the model did not score it: absent from the reference's merged table)."""
+    model = _ltr_default_model(model)
+    if cluster is None or frame_vote is None or (model is not None and deep is None):
         ctx = ctx or get_ctx()
     cluster, frame_vote = cluster or ctx.frame_cluster, frame_vote or ctx.ltr_frame
     names = list(matrices)
@@ -1946,6 +2107,17 @@ def ltr_flank_decide(matrices, flanking_len=100, ctx=None, cluster=None, frame_v
         table[n] = (bool(ok), label, None if ok else "frame_vote")
         if label == "high":
             high[n] = m
+    if model is not None:
+        t0 = time.perf_counter()
+        homology = {n: int(table[n][0]) for n in high}
+        merged = alter_deep_learning_results(ltr_deep_votes(high, model, threshold, ctx, deep), homology, list(high))
+        for n in high:
+            if n not in merged:
+                table[n] = (False, "high", "deep_missing")
+            elif homology[n] and not merged[n]:
+                table[n] = (False, "high", "deep")
+        if seconds is not None:
+            seconds["deep"] = time.perf_counter() - t0
     return table, high
 
 
@@ -2000,18 +2172,21 @@ def ltr_terminal_frames(terminals, reference, flanking_len=100, max_copy_num=100
     return frames, full
 
 
-def ltr_flank_filter(terminals, reference, flanking_len=100, max_copy_num=100, ctx=None, cluster=None, frame_vote=None, seconds=None):
+def ltr_flank_filter(terminals, reference, flanking_len=100, max_copy_num=100, ctx=None, cluster=None, frame_vote=None, seconds=None,
+                     model=None, deep=None, threshold=0.5):
     """FiLTR's "Step 3: filter out false positive sequences based on the flanking regions of the terminal sequences"
     (bin/FiLTR-main/src/LTR_filter.py:44-170) for a set of LTR terminal sequences (a FASTA path or {name: sequence}) against
-    `reference`, without the deep model: ltr_terminal_frames, then ltr_flank_decide.  A true LTR is a candidate whose copies' flanks
-    are mostly not alike.  seconds: a dict that receives the wall seconds of every step.
+    `reference`: ltr_terminal_frames, then ltr_flank_decide (model / deep / threshold: its high-copy vote of the hybrid CNN; without
+    a model the homology rule alone).  A true LTR is a candidate whose copies' flanks are mostly not alike.  seconds: a dict that
+    receives the wall seconds of every step.
     -> ({name: (is_ltr, "low" | "high" | None, dropped_by)}, {name: kept high-copy matrix}); dropped_by "frames" = no copy window
     or no boundary in the alignment (the reference writes no `.matrix` for such a candidate), else as ltr_flank_decide."""
     if not isinstance(terminals, dict):
         t_names, t_contigs = read_fasta(terminals)
         terminals = {n: t_contigs[n] for n in t_names}
     frames, _full = ltr_terminal_frames(terminals, reference, flanking_len, max_copy_num, ctx, seconds)
-    table, high = ltr_flank_decide(frames, flanking_len, ctx or get_ctx(), cluster, frame_vote, seconds=seconds)
+    table, high = ltr_flank_decide(frames, flanking_len, ctx or get_ctx(), cluster, frame_vote, seconds=seconds, model=model, deep=deep,
+                                   threshold=threshold)
     return {n: table.get(n, (False, None, "frames")) for n in terminals}, high
 
 
@@ -2456,13 +2631,14 @@ def ltr_candidate_scan(reference, scn_file, ctx=None, scan=None, **limits):
 
 
 def ltr_detect(reference, out_dir, flanking_len=100, max_copy_num=100, ctx=None, scan=None, hsps=None, cluster=None, frame_vote=None,
-               seconds=None):
+               seconds=None, model=None, deep=None, threshold=0.5):
     """FiLTR from the genome to the is_LTR table, in-tree: ltr_candidate_scan -> out_dir/total.scn, ltr_scn_filter (steps 1 and 2) ->
     out_dir/filter_terminal_align.scn and the left terminals, ltr_flank_filter (step 3) -> the is_LTR table;
     out_dir/confident_ltr.scn receives the lines of filter_terminal_align.scn whose left terminal step 3 kept.  reference is a FASTA
     path.  The reference is NOT cut into pieces of 10 Mb as FiLTR cuts it for LtrDetector: the scan has no such limit, so an element
     that lies across such a cut is found.  scan / hsps / cluster / frame_vote replace the device stages (the signatures of
-    Context.ltr_scan, .pair_hsps, .frame_cluster, .ltr_frame); seconds: a dict that receives the wall seconds of every step.
+    Context.ltr_scan, .pair_hsps, .frame_cluster, .ltr_frame); model / deep / threshold: the high-copy vote of the hybrid CNN in step 3
+    (ltr_flank_decide; without a model the homology rule alone); seconds: a dict that receives the wall seconds of every step.
     -> (path of confident_ltr.scn, {chr-start-end of a left terminal: (is_ltr, "low" | "high" | None, dropped_by)})"""
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.perf_counter()
@@ -2471,8 +2647,10 @@ def ltr_detect(reference, out_dir, flanking_len=100, max_copy_num=100, ctx=None,
     if seconds is not None:
         seconds["scan"] = time.perf_counter() - t0
     final_scn, _dirty, terminals = ltr_scn_filter(total_scn, reference, out_dir, ctx=ctx, hsps=hsps, seconds=seconds)
+    model = _ltr_default_model(model)
+    vote = dict(model=model, deep=deep, threshold=threshold) if model is not None else {}          # without a model the call of before
     table, _high = ltr_flank_filter(terminals, reference, flanking_len, max_copy_num, ctx=ctx, cluster=cluster, frame_vote=frame_vote,
-                                    seconds=seconds)
+                                    seconds=seconds, **vote)
     _ref_names, ref_contigs = read_fasta(reference)
     _terminals, candidate_of = left_ltr_terminals(final_scn, ref_contigs)
     _candidates, lines = read_scn(final_scn, None)

@@ -312,6 +312,57 @@ int hite_ltr_both_ends(hite_ctx *ctx, int32_t n, const uint8_t *msa, const int64
                        const uint8_t *cand, const int64_t *cand_off, int32_t flank, uint8_t *frames, const int64_t *frame_off,
                        uint8_t *full, const int64_t *full_off, int32_t *full_cols, int32_t *new_pos, int32_t *status);
 
+/* ---- high-copy LTR vote of the vendored FiLTR's hybrid CNN --- bin/FiLTR-main/src/Deep_Learning/hybridLTR_feature_extractor.py,
+ * hybridLTR_model.py (class CNNCAT), hybridLTR_predicter.py; run by LTR_filter.py:146-170 on every matrix of more than 5 rows.
+ * PINNED to the reference: the features are integers and equal the reference's, the logits are fp32 and are held to the
+ * reference's within the bound recorded in tests/golden/ltr_deep.json.gz (twin tests/ltrdeep_twin.py).
+ * Input per candidate: row_off[c+1] - row_off[c] rows of HITE_LTRDEEP_COLS bytes at rows + row_off[c] * HITE_LTRDEEP_COLS, each the
+ * left frame of 100 bytes followed by the right frame of 100 bytes.  A candidate of fewer than 5 or more than HITE_LTRDEEP_ROWS rows
+ * is NOT SCORED: status 1, logits (pooled, img, kmer) 0; the others are unaffected.  A scored candidate has status 0.
+ *  - Characters: anything other than upper-case A C G T is '-'.  Fewer than 100 rows are padded below with all-'-' rows.
+ *  - img [3][100][200] (uint8): `block` 100 on a base, 0 on '-'; `support` on a base (int)(((double)count / (double)total) * 100.0),
+ *    count = rows with that base in the column, total = rows with any base in the column (binary64, from a 101 x 101 table the
+ *    host builds: it differs from floor(100 count / total) at (29, 50), (29, 100), (57, 100), (58, 100)), 0 on '-'; `base` G 100,
+ *    C 75, A 50, T 25, '-' 0.
+ *  - kmer [2][HITE_LTRDEEP_KMER] (int32), left half then right half: for k = 3, 4, 5 the count of every word of k consecutive columns
+ *    of every row of the half (100 - k + 1 words per row), the word read as a base-5 number over A 0, G 1, C 2, T 3, '-' 4, first
+ *    column most significant; the all-'-' word (the last number) has no slot: 124 + 624 + 3124 slots, the three k one after another.
+ *  - Both are L2-normalised over the channel axis (the 3 planes of a pixel, the 2 halves of a slot), x / max(|x|_2, 1e-12) in
+ *    binary64 rounded to fp32.
+ *  - Model (eval mode): two branches (img with 3 input planes on 100 x 200, kmer with 2 on 1 x 3872) of three residual blocks
+ *    in -> 8 -> 16 -> 32; a block is conv 3x3 (pad 1, no bias) -> BN -> ReLU -> conv 3x3 -> BN, plus BN(conv 1x1 of the block's
+ *    input), -> ReLU; the mean over H x W of each of the 32 + 32 planes is `pooled`; then Linear 64 -> 16, BN, ReLU, Linear 16 -> 8,
+ *    BN, ReLU, Linear 8 -> 2: the logits.  All in fp32 FMAs in a fixed order -- a convolution sums over (input plane, ky, kx)
+ *    ascending, a mean sums the pixels of a tile in a fixed tree and the tiles in ascending order -- so a candidate's result is the
+ *    same bits at every batch size and at every place of a batch.
+ * params: HITE_LTRDEEP_PARAMS floats, every tensor in PyTorch's element order: the img branch, then the kmer branch, each block
+ * after block as conv1.weight [out][in][3][3], bn1 (weight, bias, running_mean, running_var), conv2.weight, bn2, shortcut
+ * conv.weight [out][in][1][1], shortcut bn; then Linear1 (weight [16][64], bias), its bn, Linear2 ([8][16], bias), its bn, Linear3
+ * ([2][8], bias).  hite_ltr_model_build folds every batch norm (eps 1e-5) into a scale and a shift in binary64, rounds to fp32 and
+ * uploads; the handle goes to hite_ltr_model_release before the context is destroyed.  n_params != HITE_LTRDEEP_PARAMS or a
+ * parameter that is not finite: HITE_EINVAL.
+ * hite_ltr_deep_features runs the feature kernel of hite_ltr_deep alone (tests, diagnosis).  n = 0 is valid; HITE_EINVAL for a
+ * negative count, a missing buffer and descending offsets.  The candidates go to the device in batches of HITE_LTRDEEP_BATCH_DEFAULT
+ * ($HITE_LTRDEEP_BATCH, read by hite_ctx_create, sets another size: a test knob that never changes a result); a candidate of a batch
+ * holds about 5.8 MB of the context's scratch (features 0.11 MB, fp32 planes 59 x 80 000 + 58 x 15 488 bytes, partial sums).
+ * The convolution kernels take tiles of HITE_LTRDEEP_TILE_H x HITE_LTRDEEP_TILE_W pixels of the image and of HITE_LTRDEEP_KMER_TILE
+ * slots of the k-mer axis. */
+#define HITE_LTRDEEP_PARAMS   40026
+#define HITE_LTRDEEP_ROWS     100
+#define HITE_LTRDEEP_COLS     200
+#define HITE_LTRDEEP_KMER     3872
+#define HITE_LTRDEEP_TILE_H   8
+#define HITE_LTRDEEP_TILE_W   32
+#define HITE_LTRDEEP_KMER_TILE 256
+#define HITE_LTRDEEP_BATCH_DEFAULT 64
+int hite_ltr_model_build(hite_ctx *ctx, const float *params, int64_t n_params, void **model_out);
+void hite_ltr_model_release(void *model);
+int hite_ltr_deep(hite_ctx *ctx, void *model, int64_t n, const uint8_t *rows /* 200 bytes per row */,
+                  const int64_t *row_off /* n + 1, in rows */, float *logits /* n x 2 */, float *pooled /* n x 64, may be NULL */,
+                  int8_t *status /* 0 scored, 1 not scored */);
+int hite_ltr_deep_features(hite_ctx *ctx, int64_t n, const uint8_t *rows, const int64_t *row_off,
+                           uint8_t *img /* n x 3 x 100 x 200 */, int32_t *kmer /* n x 2 x 3872 */, int8_t *status);
+
 /* ---- k-mer TSD seed matching --- search_confident_tir_v4  Util.py:7734-7845 -------------------------
  * batch of flanked candidates (CSR); the raw boundaries are (flank+1, len-flank), 1-based, as
  * search_confident_tir_batch_v1 passes them (Util.py:6550), tsd_search_distance = flank (<= 63).
