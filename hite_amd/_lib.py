@@ -97,6 +97,12 @@ class Context:
         Both write the same bytes."""
         self._check(self.lib.hite_fill_config_ctx(self.h, -1 if tiles is None else int(bool(tiles))), "hite_fill_config_ctx")
 
+    def fallback_overlap(self, mode):
+        """whether the star alignment of THIS context runs its fall-back alignment beside the layout of the candidates the fall-back does
+        not touch (include/hite_gpu.h hite_fallback_overlap_ctx): True / 1 = beside (the default), False / 0 = one after the other,
+        None / -1 = follow the process default again (HITE_FALLBACK_OVERLAP=0: one after the other).  Both give the same bytes."""
+        self._check(self.lib.hite_fallback_overlap_ctx(self.h, -1 if mode is None or int(mode) < 0 else int(bool(mode))), "hite_fallback_overlap_ctx")
+
     def fill_tile_limits(self):
         """(positions of a tile, window-range bytes that fit the LDS slot, rows of a workgroup per trip, row slices) of the tile form"""
         out = (C.c_int32 * 4)()

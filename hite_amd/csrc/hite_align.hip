@@ -1460,12 +1460,19 @@ __global__ void __launch_bounds__(64) align_tb_strips_kernel(AlignArgs P, const 
 // ---------------------------------------------------------------------------------------------
 // what: 0 = pairs to re-run with a band of `level` words (exact mode), 1 = pairs whose traceback left the slice,
 // 2 / 3 = pairs that will / will not be re-run with a wider band at all (asked after the 4-word run)
+// dead (what == 1 only, may be NULL): counts the rows that are dead whatever the fall-back does -- status 2 from a forward kernel, or
+// an empty non-centre row (align_stats_kernel) -- for the caller that lays candidates out beside the fall-back
 __global__ void align_flag_kernel(int64_t nrows, const int32_t *__restrict__ order, const int32_t *__restrict__ strips, AlignArgs P,
-                                  int what, int level, int cap, int32_t *__restrict__ flag, int32_t *__restrict__ cols) {
+                                  int what, int level, int cap, int32_t *__restrict__ flag, int32_t *__restrict__ cols,
+                                  unsigned long long *__restrict__ dead = nullptr) {
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= nrows) return;
     const int g = order[x];
     int f = 0;
+    if (dead) {
+        const int st = P.st[g];
+        if (strips[g] > 0 ? (st != 0 && st != 1) : g != P.row_first[P.row_cand[g]]) atomicAdd(dead, 1ull);      // (rare: no reduction)
+    }
     if (strips[g] > 0) {
         if (what == 0) {
             const int u4 = P.U4[g];
@@ -1495,6 +1502,27 @@ __global__ void align_compact_kernel(int64_t nrows, const int32_t *__restrict__ 
         out[pos[x]] = g;
         if (full_off) { full_off[g] = colpos[x]; st[g] = 0; }
     }
+}
+// ---- the fall-back beside the caller's work on the other candidates (hite_align_begin / hite_align_finish) ----
+// the candidates that own a row of the fall-back's list: a flag per candidate, and each of them once in pend_list (in no fixed order)
+__global__ void align_pending_kernel(int cnt, const int32_t *__restrict__ list, const int32_t *__restrict__ row_cand,
+                                     int32_t *__restrict__ pending, int32_t *__restrict__ pend_list, int32_t *__restrict__ pend_count) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= cnt) return;
+    const int c = row_cand[list[x]];
+    if (atomicExch(&pending[c], 1) == 0) pend_list[atomicAdd(pend_count, 1)] = c;
+}
+// row_dead and the candidate's flag as align_stats_kernel will write them, for the rows of the candidates that are NOT pending: their
+// status is final.  (The rows of a pending candidate are left alone: the fall-back is writing their status.)
+__global__ void align_dead_mark_kernel(int64_t total_rows, const int32_t *__restrict__ strips, AlignArgs P, const int32_t *__restrict__ pending,
+                                       int32_t *__restrict__ row_dead, int32_t *__restrict__ cand_status) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= total_rows) return;
+    const int c = P.row_cand[g];
+    if (pending[c]) return;
+    const bool dead = strips[g] > 0 ? P.st[g] != 0 : g != P.row_first[c];
+    row_dead[g] = dead;
+    if (dead) atomicExch(&cand_status[c], 2);
 }
 // strips of the longest pair of every block of 64 list entries (= the strips the block's wavefront runs), and -- after the
 // exclusive scan of those -- the record address of every pair of the list
@@ -1617,6 +1645,13 @@ struct AlignState {
     hipStream_t st2 = nullptr;     // the wider bands run here, beside the traceback of the pairs that are already final; the longest pairs' lane-parallel kernels
     hipEvent_t ev = nullptr, ev_fork = nullptr, ev_join = nullptr;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // a run between hite_align_begin and hite_align_finish: what the finish half needs
+    bool open = false, forked = false;
+    AlignArgs P;
+    int64_t total_rows = 0;
+    const int32_t *strips = nullptr;
+    int32_t *row_dead = nullptr, *cand_flag = nullptr, *info = nullptr;
+    hipStream_t st = nullptr;
 };
 
 // the second stream gets the highest priority: its few long-running waves are the critical path and must not queue behind the
@@ -1699,19 +1734,24 @@ static int aalloc(hite_ctx *ctx, Arena &A, size_t count, T **out) {
 // order-preserving compaction of the rows flagged for `what`; returns the count (host) and the list (device)
 static int build_list(hite_ctx *ctx, AlignState *S, hipStream_t st, int64_t nrows, const int32_t *order, const int32_t *strips,
                       AlignArgs &P, int what, int level, int cap, int32_t *flag, int32_t *cols, int64_t *pos, int64_t *colpos,
-                      int64_t *scan_tmp, int32_t *list, int64_t *full_off, int64_t *count, int64_t *total_cols, int slot = 0) {
+                      int64_t *scan_tmp, int32_t *list, int64_t *full_off, int64_t *count, int64_t *total_cols, int slot = 0,
+                      int64_t *dead = nullptr) {
     const unsigned nb = (unsigned)((nrows + 255) / 256);
-    hipLaunchKernelGGL(align_flag_kernel, dim3(nb), dim3(256), 0, st, nrows, order, strips, P, what, level, cap, flag, cols);
+    // *dead (with what == 1): the rows that are dead already and not on the list, counted by the flag kernel; it rides on the read-back
+    if (dead) HITE_CHECK(ctx, hipMemsetAsync(S->d_scal + slot + 2, 0, 8, st));
+    hipLaunchKernelGGL(align_flag_kernel, dim3(nb), dim3(256), 0, st, nrows, order, strips, P, what, level, cap, flag, cols,
+                       dead ? (unsigned long long *)(S->d_scal + slot + 2) : nullptr);
     ACHK(scan_excl_buf<int32_t>(ctx, scan_tmp, flag, nrows, pos, st));
     if (cols) ACHK(scan_excl_buf<int32_t>(ctx, scan_tmp, cols, nrows, colpos, st));
     hipLaunchKernelGGL(align_compact_kernel, dim3(nb), dim3(256), 0, st, nrows, order, flag, pos, list, cols ? colpos : nullptr,
                        cols ? full_off : nullptr, P.st);
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + slot, pos + nrows, 8, hipMemcpyDeviceToDevice, st));
     if (cols) HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + slot + 1, colpos + nrows, 8, hipMemcpyDeviceToDevice, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + slot, S->d_scal + slot, 16, hipMemcpyDeviceToHost, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + slot, S->d_scal + slot, dead ? 24 : 16, hipMemcpyDeviceToHost, st));
     HITE_CHECK(ctx, hipStreamSynchronize(st));
     *count = S->h_pin[slot];
     if (total_cols) *total_cols = cols ? S->h_pin[slot + 1] : 0;
+    if (dead) *dead = S->h_pin[slot + 2];
     return HITE_OK;
 }
 
@@ -1753,10 +1793,15 @@ static int assign_records(hite_ctx *ctx, AlignState *S, hipStream_t st, const in
 // d_row_dead (total_rows, may be NULL): 1 for rows that could not be aligned (0 for centres); d_cand_flag (n_cand, may be
 // NULL): set to 2 for candidates that lost a row.  d_info (5 x total_rows int32, may be NULL): per row U, certified, status,
 // k*, band words | 0x100 (fall-back).
-int hite_align_run(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const int64_t *d_win_off, const int32_t *d_win_len,
-                   const int32_t *d_row_first, int64_t total_rows, const int64_t *d_ops_base, uint16_t *d_ops,
-                   int32_t *d_row_dead, int32_t *d_cand_flag, int32_t *d_info, const char *tag, hipStream_t st) {
+// The begin half: everything up to the fall-back's list, and the fall-back itself -- on `st`, or (fork != NULL and the list is not
+// empty) on the high-priority stream beside whatever the caller enqueues on `st` before hite_align_finish (hite_align.h).
+int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const int64_t *d_win_off, const int32_t *d_win_len,
+                     const int32_t *d_row_first, int64_t total_rows, const int64_t *d_ops_base, uint16_t *d_ops,
+                     int32_t *d_row_dead, int32_t *d_cand_flag, int32_t *d_info, const char *tag, hipStream_t st, HiteAlignFork *fork) {
+    if (fork) memset(fork, 0, sizeof *fork);
     if (!ctx || n_cand < 0 || total_rows < 0 || total_rows > 0x7fffffff) return HITE_EINVAL;
+    if (fork && (!d_row_dead || !d_cand_flag)) return HITE_EINVAL;
+    if (ctx->align_state) { ((AlignState *)ctx->align_state)->open = false; ((AlignState *)ctx->align_state)->forked = false; }
     if (n_cand == 0 || total_rows == 0) return HITE_OK;
     AlignState *S = align_state(ctx);
     if (!S) return HITE_ENOMEM;
@@ -1934,17 +1979,70 @@ int hite_align_run(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const in
     HITE_CHECK(ctx, hipGetLastError());
     // ---- fall-back: the pairs whose path left the slice
     {
-        int64_t cnt = 0, tcols = 0;
-        ACHK(build_list(ctx, S, st, total_rows, order, strips, P, 1, 0, cap, flag, cols, pos, colpos, scan_tmp, list, full_off, &cnt, &tcols));
-        if (cnt > 0) {
+        int64_t cnt = 0, tcols = 0, dead = 0;
+        ACHK(build_list(ctx, S, st, total_rows, order, strips, P, 1, 0, cap, flag, cols, pos, colpos, scan_tmp, list, full_off, &cnt, &tcols, 0,
+                        fork ? &dead : nullptr));
+        if (cnt > 0 && !fork) {
             tk = hite_prof_begin(ctx, "align_fallback", st);
             ACHK(aalloc(ctx, A, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
             ACHK(aalloc(ctx, A, (size_t)tcols + 16, &P.fullt));
             hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
             hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
             hite_prof_end(ctx, tk, st);
+        } else if (cnt > 0) {
+            // ---- the fork.  The fall-back's ~50 wavefronts run on the high-priority stream while the caller works, on `st`, on the
+            // candidates that own none of its rows.  From here to hite_align_finish:
+            //   * the fall-back kernels WRITE the ops rows of the pending candidates' listed rows and P.U, P.kst, P.st, P.lvl of those
+            //     rows, and read `list`, full_off, the planes and the windows.  Nothing on `st` may read or write anything of a pending
+            //     candidate: its ops, its layout words, its entries of the caller's per-candidate outputs, the status of its rows
+            //     (align_dead_mark_kernel and the caller's kernels return at once for a candidate whose pending flag is set);
+            //   * row_dead and cand_flag of the rows that are NOT pending are final now and are written here when any is dead (`dead`,
+            //     counted by the flag kernel and read back with the list's length); align_stats_kernel writes the same values again
+            //     in the finish half, and those of the pending candidates for the first time;
+            //   * fullbuf, fullt, the list and the pending arrays live in this arena: nothing resets it before the finish half (only
+            //     the next hite_align_begin does).
+            int32_t *pending, *pend_list, *pend_count;
+            ACHK(aalloc(ctx, A, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
+            ACHK(aalloc(ctx, A, (size_t)tcols + 16, &P.fullt));
+            ACHK(aalloc(ctx, A, (size_t)n_cand, &pending));
+            ACHK(aalloc(ctx, A, (size_t)cnt, &pend_list));
+            ACHK(aalloc(ctx, A, (size_t)1, &pend_count));
+            HITE_CHECK(ctx, hipEventRecord(S->ev_fork, st));
+            HITE_CHECK(ctx, hipStreamWaitEvent(s2, S->ev_fork, 0));
+            const int tl = hite_prof_begin(ctx, "align_fallback", s2);
+            hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
+            hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
+            hite_prof_end(ctx, tl, s2);
+            HITE_CHECK(ctx, hipEventRecord(S->ev_join, s2));
+            HITE_CHECK(ctx, hipMemsetAsync(pending, 0, (size_t)n_cand * 4, st));
+            HITE_CHECK(ctx, hipMemsetAsync(pend_count, 0, 4, st));
+            hipLaunchKernelGGL(align_pending_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (int)cnt, list, row_cand, pending, pend_list, pend_count);
+            if (dead > 0)
+                hipLaunchKernelGGL(align_dead_mark_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, strips, P, pending,
+                                   d_row_dead, d_cand_flag);
+            S->forked = true;
+            fork->cnt = cnt; fork->dead_before = dead; fork->d_pending = pending; fork->d_pend_list = pend_list; fork->d_pend_count = pend_count;
         }
     }
+    HITE_CHECK(ctx, hipGetLastError());
+    S->P = P; S->total_rows = total_rows; S->strips = strips; S->row_dead = d_row_dead; S->cand_flag = d_cand_flag; S->info = d_info; S->st = st;
+    S->open = true;
+    return HITE_OK;
+}
+
+// The finish half: waits for the fall-back where it ran on the side, then the statistics, row_dead / cand_flag, the info records.
+int hite_align_finish(hite_ctx *ctx) {
+    if (!ctx) return HITE_EINVAL;
+    AlignState *S = (AlignState *)ctx->align_state;
+    if (!S || !S->open) return HITE_OK;          // (an empty run)
+    S->open = false;
+    const AlignArgs &P = S->P;
+    const int64_t total_rows = S->total_rows;
+    const int32_t *strips = S->strips;
+    int32_t *d_row_dead = S->row_dead, *d_cand_flag = S->cand_flag, *d_info = S->info;
+    hipStream_t st = S->st;
+    if (S->forked) HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev_join, 0));
+    S->forked = false;
     HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
     hipLaunchKernelGGL(align_stats_kernel, dim3((unsigned)(total_rows + 255 < 1024 * 256 ? (total_rows + 255) / 256 : 1024)), dim3(256), 0, st, total_rows, strips, P, d_row_dead, d_cand_flag,
                        (unsigned long long *)S->d_scal);
@@ -1954,4 +2052,12 @@ int hite_align_run(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const in
     for (int q = 0; q < 7; q++) S->stats[q] += S->h_pin[q];
     HITE_CHECK(ctx, hipGetLastError());
     return HITE_OK;
+}
+
+int hite_align_run(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const int64_t *d_win_off, const int32_t *d_win_len,
+                   const int32_t *d_row_first, int64_t total_rows, const int64_t *d_ops_base, uint16_t *d_ops,
+                   int32_t *d_row_dead, int32_t *d_cand_flag, int32_t *d_info, const char *tag, hipStream_t st) {
+    ACHK(hite_align_begin(ctx, n_cand, d_win, d_win_off, d_win_len, d_row_first, total_rows, d_ops_base, d_ops, d_row_dead, d_cand_flag, d_info,
+                          tag, st, nullptr));
+    return hite_align_finish(ctx);
 }

@@ -26,6 +26,7 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
     c->device = device_id;
     c->copy_interval = -1;
     c->fill_tiles = -1;
+    c->fallback_overlap = -1;
     // test knobs of hite_msa_subcluster (hite_subcluster.hip), read here so that two contexts of a process may differ
     c->subcluster_chunk = HITE_SUBCLUSTER_CHUNK;
     if (const char *e = getenv("HITE_SUBCLUSTER_CHUNK_ROWS")) {
@@ -95,6 +96,26 @@ extern "C" void hite_ctx_destroy(hite_ctx *c) {
 }
 
 extern "C" const char *hite_last_error(hite_ctx *c) { return c ? c->err : "null ctx"; }
+
+// whether the star alignment runs its fall-back alignment beside the layout of the candidates the fall-back does not touch
+// (hite_msa.hip, star_msa_launch): 1 = beside, 0 = one after the other, -1 = the process default, taken from the environment once
+// (HITE_FALLBACK_OVERLAP=0: one after the other).  Both routes give the same bytes.
+static int g_fallback_overlap = -1;
+int hite_fallback_overlap_mode(const hite_ctx *ctx) {
+    if (ctx->fallback_overlap >= 0) return ctx->fallback_overlap;
+    int v = __atomic_load_n(&g_fallback_overlap, __ATOMIC_RELAXED);
+    if (v < 0) {
+        const char *e = getenv("HITE_FALLBACK_OVERLAP");
+        v = (e && !strcmp(e, "0")) ? 0 : 1;
+        __atomic_store_n(&g_fallback_overlap, v, __ATOMIC_RELAXED);
+    }
+    return v;
+}
+extern "C" int hite_fallback_overlap_ctx(hite_ctx *ctx, int32_t mode) {
+    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
+    ctx->fallback_overlap = mode;
+    return HITE_OK;
+}
 
 // Byte order of the contig NAMES (each followed by ':'): the rows of an alignment are named "<contig>:<start>-<end>(<strand>)" and
 // tools/ready_for_MSA.sh breaks length ties by name (hite_pipeline.hip, select_rows_kernel).  rank[i] = position of contig i in

@@ -45,6 +45,17 @@ __device__ __forceinline__ int msa_src(const int32_t *__restrict__ row_map, int6
     return row_map ? row_map[g0 + r] - (int)g0 : r;
 }
 
+// The candidate a workgroup of the per-candidate kernels between aligner and fill takes (star_msa_launch).  All three pointers NULL:
+// candidate blockIdx.x.  pending: the same, but nothing for a candidate whose flag is set (the fall-back alignment is still writing
+// its ops).  pend_list / pend_count: entry blockIdx.x of the list of those candidates, nothing at or beyond the count.  -1: nothing.
+__device__ __forceinline__ int msa_block_cand(int n, const int32_t *__restrict__ pending, const int32_t *__restrict__ pend_list,
+                                              const int32_t *__restrict__ pend_count) {
+    const int b = blockIdx.x;
+    if (pend_list) return b < *pend_count ? pend_list[b] : -1;
+    if (b >= n || (pending && pending[b])) return -1;
+    return b;
+}
+
 // insertions of row r before centre position p (p = 0..m), from two neighbouring ops entries.  The full (non-sparse) kernels keep their
 // column widths in the centre's ops row, spare entry included: they take the row's first base as an argument instead
 __device__ __forceinline__ int row_ins_s(const uint16_t *__restrict__ rop, int p, int m, int nrow, int start) {
@@ -63,10 +74,11 @@ __device__ __forceinline__ int row_ins(const uint16_t *__restrict__ rop, int p, 
 }
 
 // column layout: one block per candidate.  insmax -> row-0 slot of ops, block starts -> slot R.
-__global__ void __launch_bounds__(256) star_layout_kernel(MsaParams P) {
+__global__ void __launch_bounds__(256) star_layout_kernel(MsaParams P, const int32_t *__restrict__ pending, const int32_t *__restrict__ pend_list,
+                                                          const int32_t *__restrict__ pend_count) {
     __shared__ int s_scan[8];
-    const int c = blockIdx.x;
-    if (c >= P.n) return;
+    const int c = msa_block_cand(P.n, pending, pend_list, pend_count);
+    if (c < 0) return;
     const int64_t g0 = P.row_first[c];
     const int R = msa_rows(P.rows_eff, P.row_first, c);
     if (R <= 0) { if (threadIdx.x == 0) P.cols_out[c] = 0; return; }
@@ -168,11 +180,12 @@ __global__ void __launch_bounds__(256) star_fill_kernel(FillParams P) {
 __device__ __forceinline__ unsigned long long lay_ld8(const uint16_t *p) { unsigned long long v; __builtin_memcpy(&v, p, 8); return v; }
 
 __global__ void __launch_bounds__(256) star_layout_sparse_kernel(MsaParams P, int32_t *__restrict__ new_cols,
-                                                                 int32_t *__restrict__ last_extra) {
+                                                                 int32_t *__restrict__ last_extra, const int32_t *__restrict__ pending,
+                                                                 const int32_t *__restrict__ pend_list, const int32_t *__restrict__ pend_count) {
     __shared__ int s_scan[8];
     __shared__ int s_mxm;
-    const int c = blockIdx.x;
-    if (c >= P.n) return;
+    const int c = msa_block_cand(P.n, pending, pend_list, pend_count);
+    if (c < 0) return;
     const int64_t g0 = P.row_first[c];
     const int R = msa_rows(P.rows_eff, P.row_first, c);
     if (R <= 0 || P.status[c]) { if (threadIdx.x == 0) { P.cols_out[c] = 0; new_cols[c] = 0; last_extra[c] = -1; } return; }
@@ -538,9 +551,10 @@ __global__ void __launch_bounds__(256) msa_compact_rows_kernel(int n, const int3
                                                                const int32_t *__restrict__ win_len, const int64_t *__restrict__ ops_base,
                                                                uint16_t *__restrict__ ops_all, const int32_t *__restrict__ cand_flag,
                                                                const int32_t *__restrict__ row_dead, int32_t *__restrict__ row_map,
-                                                               int32_t *__restrict__ rows_eff) {
-    const int c = blockIdx.x;
-    if (c >= n) return;
+                                                               int32_t *__restrict__ rows_eff, const int32_t *__restrict__ pending,
+                                                               const int32_t *__restrict__ pend_list, const int32_t *__restrict__ pend_count) {
+    const int c = msa_block_cand(n, pending, pend_list, pend_count);
+    if (c < 0) return;
     const int g0 = row_first[c], R = row_first[c + 1] - g0;
     if (R <= 0) { if (threadIdx.x == 0) rows_eff[c] = 0; return; }
     if (cand_flag[c] != 2) {
@@ -588,9 +602,11 @@ __global__ void row_pad_scan_kernel(int64_t total_rows, const uint8_t *__restric
 __global__ void __launch_bounds__(256) ops_pad_fix_kernel(int n, const int32_t *__restrict__ row_first, const int32_t *__restrict__ win_len,
                                                           const int64_t *__restrict__ ops_base, uint16_t *__restrict__ ops_all,
                                                           const uint32_t *__restrict__ pads, const int32_t *__restrict__ row_map,
-                                                          const int32_t *__restrict__ rows_eff, int32_t *__restrict__ len2) {
-    const int c = blockIdx.x;
-    if (c >= n) return;
+                                                          const int32_t *__restrict__ rows_eff, int32_t *__restrict__ len2,
+                                                          const int32_t *__restrict__ pending, const int32_t *__restrict__ pend_list,
+                                                          const int32_t *__restrict__ pend_count) {
+    const int c = msa_block_cand(n, pending, pend_list, pend_count);
+    if (c < 0) return;
     const int g0 = row_first[c];
     const int R = rows_eff ? rows_eff[c] : row_first[c + 1] - g0;
     if (R >= 1 && threadIdx.x == 0) len2[g0] = win_len[g0];      // the centre is taken as it is
@@ -645,12 +661,23 @@ static int star_msa_launch(hite_ctx *ctx, int32_t n, const uint8_t *d_win, const
     int64_t before[8], after[8];
     rc = hite_align_stats(ctx, before, 0);
     if (rc) return rc;
-    rc = hite_align_run(ctx, n, d_win, d_win_off, d_win_len, d_row_first, total_rows, d_ops_base, (uint16_t *)opsb, row_dead, cand_flag, d_info,
-                        max_win_len > 1000 ? "_long" : "_short", st);
+    // The aligner in two halves (hite_align.h).  When its fall-back has pairs and the context's switch is on (hite_fallback_overlap_ctx),
+    // the fall-back -- a few dozen lone wavefronts, ~3 ms of a C3 step -- runs on the aligner's side stream and the three kernels below
+    // run beside it for the candidates that own none of its rows (the window), then once more for those that do.
+    HiteAlignFork F;
+    memset(&F, 0, sizeof F);
+    rc = hite_align_begin(ctx, n, d_win, d_win_off, d_win_len, d_row_first, total_rows, d_ops_base, (uint16_t *)opsb, row_dead, cand_flag, d_info,
+                          max_win_len > 1000 ? "_long" : "_short", st, hite_fallback_overlap_mode(ctx) ? &F : nullptr);
     if (rc) return rc;
-    rc = hite_align_stats(ctx, after, 0);
-    if (rc) return rc;
-    const bool dropped = after[4] > before[4];
+    const bool forked = F.cnt > 0;
+    if (!forked) {
+        rc = hite_align_finish(ctx);
+        if (rc) return rc;
+        rc = hite_align_stats(ctx, after, 0);
+        if (rc) return rc;
+    }
+    // rows were dropped: known from the counters after the aligner, or -- in the window -- from the rows dead before the fall-back
+    bool dropped = forked ? F.dead_before > 0 : after[4] > before[4];
     // rows padded with pad bytes (HITE_IS_ROW_PAD): where each begins and ends (the ops are fixed up after the compaction below)
     int32_t *len2 = (int32_t *)(base + ops_bytes + 2 * rows_bytes + 2 * cand_bytes + lay_bytes);
     uint32_t *pads = (uint32_t *)((uint8_t *)len2 + rows_bytes);
@@ -664,24 +691,58 @@ static int star_msa_launch(hite_ctx *ctx, int32_t n, const uint8_t *d_win, const
     P.row_map = nullptr; P.rows_eff = nullptr; P.pads = pads;
     P.lay = d_new_cols ? (uint32_t *)(base + ops_bytes + 2 * rows_bytes + 2 * cand_bytes) : nullptr;
     ctx->d_msa_lay = P.lay;
-    if (dropped) {
-        hipLaunchKernelGGL(msa_compact_rows_kernel, dim3(n), dim3(256), 0, st, n, d_row_first, d_win_len, d_ops_base, (uint16_t *)opsb, cand_flag,
-                           row_dead, row_map, rows_eff);
-        P.row_map = row_map; P.rows_eff = rows_eff;
+    // compaction of the rows (when `compact`), pad fix and layout of: every candidate (all NULL, grid n), every candidate that is not
+    // pending (pending, grid n), or the pending ones (list and count, grid = an upper bound of the count)
+    auto pass = [&](bool compact, const int32_t *pending, const int32_t *plist, const int32_t *pcount, unsigned grid, bool rows_out) {
+        if (compact) {
+            hipLaunchKernelGGL(msa_compact_rows_kernel, dim3(grid), dim3(256), 0, st, n, d_row_first, d_win_len, d_ops_base, (uint16_t *)opsb, cand_flag,
+                               row_dead, row_map, rows_eff, pending, plist, pcount);
+            P.row_map = row_map; P.rows_eff = rows_eff;
+        }
+        hipLaunchKernelGGL(ops_pad_fix_kernel, dim3(grid), dim3(256), 0, st, n, d_row_first, d_win_len, d_ops_base, (uint16_t *)opsb, pads, P.row_map,
+                           P.rows_eff, len2, pending, plist, pcount);
+        if (rows_out && d_rows_out) hipLaunchKernelGGL(msa_rows_out_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d_row_first, P.rows_eff, d_rows_out);
+        int tk;
+        if (d_new_cols) {
+            tk = hite_prof_begin(ctx, max_win_len > 1000 ? "star_layout_sparse_kernel_long" : "star_layout_sparse_kernel_short", st);
+            hipLaunchKernelGGL(star_layout_sparse_kernel, dim3(grid), dim3(256), 0, st, P, d_new_cols, d_last_extra, pending, plist, pcount);
+        } else {
+            tk = hite_prof_begin(ctx, "star_layout_kernel", st);
+            hipLaunchKernelGGL(star_layout_kernel, dim3(grid), dim3(256), 0, st, P, pending, plist, pcount);
+        }
+        hite_prof_end(ctx, tk, st);
+    };
+    if (!forked) pass(dropped, nullptr, nullptr, nullptr, (unsigned)n, true);
+    else {
+        // ---- the window: until hite_align_finish the fall-back kernels are writing the ops rows of the pending candidates and the
+        // cost / status words of their rows.  Every kernel here either reads the windows only (the pad scan above) or returns at once
+        // for a pending candidate (msa_block_cand): nothing of such a candidate is read or written -- not its ops, its layout words,
+        // its row map, nor its entries of d_new_cols, d_last_extra, d_cols_out and d_status.
+        // Dropped rows: align_stats_kernel writes row_dead and cand_flag only in the finish half, and whether any row of the call is
+        // dropped is known on the host only then.  Rows dead BEFORE the fall-back (status 2 from a forward kernel, empty rows) can sit
+        // in candidates that are not pending: the begin half counts them (dead_before, on the read-back of the fall-back's list) and,
+        // when there are any, writes row_dead and cand_flag of the candidates that are not pending, so those are compacted here.
+        // Rows that die IN the fall-back belong to pending candidates, which are compacted after the finish half.  Either way the row
+        // map and rows_eff that fill and judges take from the context end up valid for EVERY candidate whenever a row of the call is
+        // dropped; a call that drops nothing keeps the null row map.
+        // fullbuf / fullt of the fall-back live in the aligner's arena: nothing here resets it (only the next hite_align_begin does).
+        const bool compact_win = dropped;
+        pass(compact_win, F.d_pending, nullptr, nullptr, (unsigned)n, false);
+        rc = hite_align_finish(ctx);
+        if (rc) return rc;
+        rc = hite_align_stats(ctx, after, 0);
+        if (rc) return rc;
+        dropped = after[4] > before[4];
+        if (dropped && !compact_win) {
+            // the first dead rows of the call came out of the fall-back: the identity map for the candidates laid out in the window
+            // (none of them has a dead row: they take the kernel's short way and their ops stay put), the compaction of the others
+            hipLaunchKernelGGL(msa_compact_rows_kernel, dim3(n), dim3(256), 0, st, n, d_row_first, d_win_len, d_ops_base, (uint16_t *)opsb, cand_flag,
+                               row_dead, row_map, rows_eff, nullptr, nullptr, nullptr);
+            P.row_map = row_map; P.rows_eff = rows_eff;
+        }
+        pass(dropped && compact_win, nullptr, F.d_pend_list, F.d_pend_count, (unsigned)F.cnt, true);
     }
     ctx->d_msa_row_map = P.row_map; ctx->d_msa_rows_eff = P.rows_eff;
-    hipLaunchKernelGGL(ops_pad_fix_kernel, dim3(n), dim3(256), 0, st, n, d_row_first, d_win_len, d_ops_base, (uint16_t *)opsb, pads, P.row_map,
-                       P.rows_eff, len2);
-    if (d_rows_out) hipLaunchKernelGGL(msa_rows_out_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d_row_first, P.rows_eff, d_rows_out);
-    int tk;
-    if (d_new_cols) {
-        tk = hite_prof_begin(ctx, max_win_len > 1000 ? "star_layout_sparse_kernel_long" : "star_layout_sparse_kernel_short", st);
-        hipLaunchKernelGGL(star_layout_sparse_kernel, dim3(n), dim3(256), 0, st, P, d_new_cols, d_last_extra);
-    } else {
-        tk = hite_prof_begin(ctx, "star_layout_kernel", st);
-        hipLaunchKernelGGL(star_layout_kernel, dim3(n), dim3(256), 0, st, P);
-    }
-    hite_prof_end(ctx, tk, st);
     HITE_CHECK(ctx, hipGetLastError());
     return HITE_OK;
 }

@@ -941,6 +941,10 @@ int hite_star_msa_fill_sparse_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_win
  * (and of a tile's output columns) that fit the LDS slot, out[2] = rows a workgroup takes per trip, out[3] = row slices of a
  * candidate (a workgroup takes the rows out[2] * z + wave, stepping by out[2] * out[3]). */
 int hite_fill_config_ctx(hite_ctx *ctx, int32_t mode);
+/* The star alignment re-aligns the pairs whose traceback left its slice (the fall-back: a few dozen lone wavefronts).  mode 1: that runs
+ * beside the pad fix and the layout of the candidates it does not touch, which are then done once more for the others; mode 0: one after
+ * the other; -1 follows the process default again (on, unless HITE_FALLBACK_OVERLAP=0 in the environment).  The same bytes either way. */
+int hite_fallback_overlap_ctx(hite_ctx *ctx, int32_t mode);
 int hite_fill_tile_limits(int32_t out[4]);
 
 /* ---- the fine stage in one call --- body of flank_region_align_v5 from the copy table on ----------
