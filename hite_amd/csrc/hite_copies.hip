@@ -1088,7 +1088,9 @@ using ExtState = ExtStateT<ExtCopyMode>;
 // one LANE per (chain, end) task -- even tasks extend to the left of the first anchor, odd ones to the right of the last --
 // and a lane that has finished takes the next task from the queue while its neighbours go on (the lengths run from 0 to
 // thousands of columns: with a fixed task per thread every wavefront waited for its longest).  Refill when a quarter of
-// the lanes is idle, so that the set-up code is paid for 16 tasks at a time.
+// the lanes is idle, so that the set-up code is paid for 16 tasks at a time.  The sequence bases come out of per-lane windows
+// (hite_ext.h) that all lanes refill at the same columns, every 16th of the wavefront: a column itself neither loads nor waits
+// (with word caches that every lane rotated at its own columns, nearly every column of a wavefront waited for memory).
 __global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long long *__restrict__ counters, const ChainRec *__restrict__ tab,
                                                            const uint8_t *__restrict__ cand, const int64_t *__restrict__ cand_off,
                                                            const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask,
@@ -1107,6 +1109,8 @@ __global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long l
     E.n = 0; E.i = 1;
     bool active = false, exhausted = false;
     unsigned long long my = 0, cols_done = 0;
+    unsigned col = 0;                                  // columns this wavefront has run (the same in all lanes)
+    int prio = 0;                                      // its issue priority (s_setprio)
     for (;;) {
         const unsigned long long idle = __ballot(!active);
         if (!exhausted && (idle == ~0ull || __popcll(idle) >= 16)) {
@@ -1125,13 +1129,16 @@ __global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long l
                     const int Lq = (int)(cand_off[c + 1] - qb);
                     const long long qlo = (long long)(R.lo >> 32), glo = (long long)(R.lo & 0xffffffffull);
                     const long long qhi = (long long)(R.hi >> 32), ghi = (long long)(R.hi & 0xffffffffull);
+                    // (the contig offsets staged in LDS, as hs_chains keeps them, were measured: 2.66 -> 2.62 ms on C3, nothing on a
+                    // C4 share -- not kept)
                     const int ctg = contig_of(coff, nc, glo);
                     // the query in the orientation of the genome: rel = 1 reads the reverse complement of the candidate, x -> Lq - 1 - x
-                    if (side == 0)        // x = qlo - 1, qlo - 2, ..., 0
-                        ext_init(E, cand, rel ? qb + Lq - qlo : qb + qlo - 1, rel ? +1 : -1, rel != 0, (int)qlo, bases, nmask, glo, -1, glo - coff[ctg]);
-                    else                  // x = qhi + K, qhi + K + 1, ...
-                        ext_init(E, cand, rel ? qb + Lq - 1 - (qhi + CK) : qb + qhi + CK, rel ? -1 : +1, rel != 0, (int)(Lq - (qhi + CK)), bases, nmask,
-                                 ghi + CK, +1, coff[ctg + 1] - (ghi + CK));
+                    // side 0: x = qlo - 1, qlo - 2, ..., 0; side 1: x = qhi + K, qhi + K + 1, ...
+                    const int64_t p0 = side == 0 ? (rel ? qb + Lq - qlo : qb + qlo - 1) : (rel ? qb + Lq - 1 - (qhi + CK) : qb + qhi + CK);
+                    const int n = side == 0 ? (int)qlo : (int)(Lq - (qhi + CK));
+                    const int64_t g0 = side == 0 ? glo : ghi + CK;
+                    ext_init(E, cand, p0, (side == 0) == (rel != 0) ? +1 : -1, rel != 0, n, bases, nmask, g0, side == 0 ? -1 : +1,
+                             side == 0 ? glo - coff[ctg] : coff[ctg + 1] - (ghi + CK));
                     my = t;
                     if (E.n >= 1) active = true;
                     else { x_i[t] = 0; x_t[t] = 0; }
@@ -1139,9 +1146,27 @@ __global__ void __launch_bounds__(256) chain_extend_kernel(const unsigned long l
             }
         }
         if (__ballot(active) == 0ull) { if (exhausted) break; else continue; }
+        // the windows of all lanes are refilled together, every 16 columns of the wavefront (a lane that took its task in between
+        // starts with full windows and joins at the next multiple): the only wait for sequence words in the steady state
+        if ((col & 15u) == 0u) {
+            if (active) ext_refill(E, cand, bases, nmask);
+            // The wavefronts of a SIMD share its issue slots, so a column of each takes as many times longer as there are of
+            // them, and the longest extension (up to EXT_MAXLEN columns, one after the other) sets the length of the kernel: the
+            // wavefront that holds it goes first.  The others fill the slots it leaves
+            const int rem = active ? E.n - E.i : 0;
+            const int pr = __ballot(rem >= 1024) ? 3 : __ballot(rem >= 512) ? 2 : __ballot(rem >= 256) ? 1 : 0;
+            if (pr != prio) {
+                prio = pr;
+                if (pr == 3) __builtin_amdgcn_s_setprio(3);
+                else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+                else if (pr == 1) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
+        }
+        col++;
         if (active) {
             cols_done++;
-            if (ext_step(E, bases, nmask, lut)) { x_i[my] = E.best_i; x_t[my] = E.best_t; active = false; }
+            if (ext_step<ExtCopyMode, false>(E, bases, nmask, lut)) { x_i[my] = E.best_i; x_t[my] = E.best_t; active = false; }
         }
     }
     // statistics: DP columns computed (one atomic per wavefront)
@@ -1647,7 +1672,10 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
     {
         // persistent lanes: every lane takes (chain, end) tasks from the queue until it is empty
         unsigned long long want_blocks = (2ull * chcap + 255ull) / 256ull;
-        const unsigned eblocks = (unsigned)(want_blocks < 2048ull ? (want_blocks ? want_blocks : 1ull) : 2048ull);
+        unsigned eblocks = (unsigned)(want_blocks < 2048ull ? (want_blocks ? want_blocks : 1ull) : 2048ull);
+        // HITE_EXT_BLOCKS=<n> (tests): at most n blocks, so that lanes take several tasks each also in a small batch
+        static const int ext_blocks = [] { const char *e = getenv("HITE_EXT_BLOCKS"); return e && *e ? atoi(e) : 0; }();
+        if (ext_blocks >= 1 && (unsigned)ext_blocks < eblocks) eblocks = (unsigned)ext_blocks;
         hipLaunchKernelGGL(chain_extend_kernel, dim3(eblocks), dim3(256), 0, st, d_nchain, chain_tab, d_cand,
                            d_cand_off, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off, ctx->n_contigs, chcap, d_nchain + 2, x_i, x_t);
     }

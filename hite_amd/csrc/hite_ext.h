@@ -29,10 +29,16 @@ __device__ __forceinline__ unsigned ext_cand_code(unsigned ch, bool comp) {
 // bases p0, p0 + step, ... -- against genome bases g0, g0 + 1, ... (dir = +1) or g0 - 1, g0 - 2, ... (dir = -1), at most jmax of
 // them.  The 17 band cells live in registers (the loops over the band are unrolled), the genome bases under the band as
 // three 17-bit planes that shift by one cell per column: a column costs one new genome base, one query base and ~8 integer
-// operations per cell.  Both sequences are walked one base per column, so the words they come from are kept in registers -- 16
-// genome bases, 32 mask bits, 4 query bytes per load, each fetched a few words ahead of its use (a load per base and column
-// made the kernel a gather benchmark; one word ahead left the last long extensions of a batch -- a lane alone in its
-// wavefront -- waiting for HBM every fourth column).
+// operations per cell.  Both sequences are walked strictly one base per column, so what a lane needs 16 columns from now is known
+// now.  Copy mode keeps, per lane, a window of the next 17..32 bases of either sequence, already oriented and decoded (2-bit codes
+// in 64 bits + a "never matches" bit each), and behind it the raw words of the next 16, requested and not yet looked at.  A column
+// takes its two bases from the low bits of the windows and shifts them: no address, no compare of word indices, no load, no
+// wait.  Every 16 columns ext_refill lets every lane with at most 16 bases left append its pending chunk and request the next: the
+// one wait of the steady state, for words requested 16 columns earlier, at the same column for all lanes of a wavefront.  (History:
+// a load per base and column made the kernel a gather benchmark; word caches that each lane rotated at its own columns -- 4 query
+// bytes, 16 genome bases, 32 mask bits per load -- put a wait for the previous column's requests into nearly every column of a
+// wavefront, a round trip to memory per column for the lone lanes that end a batch.)  Tandem mode keeps word caches per stream:
+// a lane there runs one extension from start to end, and that form measured faster.
 // Bit-parallel form of the band (round 4; the copy finder's mode, every cell of the band inside the contig): the 17 cells of a
 // column are kept as the value of the centre cell c8 and the differences of neighbouring cells, -1 / 0 / +1, as two bit masks
 // (VP / VN, bit b = cell b minus cell b - 1).  A cell and its diagonal predecessor differ by 0 or 1, and "0" runs up the column
@@ -63,18 +69,18 @@ __device__ __forceinline__ uint32_t ext_lut_entry(int t, int idx) {
     return (uint32_t)tc | ((uint32_t)(best + 4) << 5) | ((uint32_t)(s + 4) << 12);
 }
 
-// (device build only) the rotated words are final HERE: without it the compiler sank the rotation below the requests as selects,
-// kept the old and the new "furthest word" alive side by side, and copied one onto the other behind the load -- a wait for the
-// request just made, in every column
+// (device build only) a refill stays a branch: as selects the pending words would be read, and so waited for, in every column
 #ifdef __HIP_DEVICE_COMPILE__
-#define EXT_PIN_ROTATED(E) asm volatile("" : "+v"((E).gw), "+v"((E).gwn), "+v"((E).mw), "+v"((E).qw), "+v"((E).qwn), "+v"((E).qwn2))
-// ... and a rotation stays a branch (as selects it reads the word requested last in EVERY column: a wait in every column; as a
-// branch the wait sits inside it, paid in the columns where some lane rotates)
 #define EXT_KEEP_BRANCH() asm volatile("")
 #else
-#define EXT_PIN_ROTATED(E)
 #define EXT_KEEP_BRANCH()
 #endif
+// 16 bases as requested from memory and not yet looked at: chunk k = bases 16 k + 1 .. 16 k + 16 of both streams (below)
+struct ExtChunk {
+    int k;
+    uint32_t g0, g1, m0, m1;                 // the two genome words and the two mask words they lie in
+    uint32_t q0, q1, q2, q3;                 // the 16 candidate bytes
+};
 template <class M>
 struct ExtStateT {
     int D[EXT_W];
@@ -84,10 +90,18 @@ struct ExtStateT {
     uint32_t W0, W1, WN;
     int i, n, best_i, best_t, best_s;
     unsigned gnext_, qnext_;                // codes of the next column
-    uint32_t gw, gwn, gwn2, mw, mwn, qw, qwn, qwn2, qwn3;   // current word and the ones fetched ahead: genome bases (2 ahead = 32 columns),
-                                                            // mask bits (1 ahead = 32 columns), query bytes (3 ahead = 12 columns)
-    int64_t gwi, mwi, qwi;                   // their word indices
-    const uint32_t *q4;                      // the candidate bytes as aligned words (base address rounded down)
+    // copy mode: the next bases of both streams in walking order, oriented and decoded.  Stream base s (1-based) is query base s
+    // and genome base s + EXT_B: both leave their window in the same column, so one count serves
+    uint64_t gwin, qwin;                    //   2-bit codes, the next base in bits 0..1
+    uint32_t gnm, qnm;                      //   "not A/C/G/T" (the genome's also: beyond jmax), the next base in bit 0
+    int cnt;                                //   bases the windows hold (<= 32)
+    ExtChunk pend;                          //   the chunk behind the windows
+    const uint8_t *q;                       //   the candidate bytes, for a refill by ext_step itself ONLY.  A pointer kept here has lost its address
+                                            //   space: a read through it is a flat load that waits for everything requested before it.  chain_extend_kernel
+                                            //   must never read it: it hands its own pointer to ext_refill and instantiates ext_step with SELF_REFILL = false
+    // tandem mode: current word and the ones fetched ahead, genome bases (2 ahead = 32 columns) and mask bits (1 ahead = 32 columns)
+    uint32_t gw, gwn, gwn2, mw, mwn;
+    int64_t gwi, mwi;                        // their word indices
     int64_t p0, g0, jmax;
     int step, dir;
     int blo, bhi;                            // DIAGLIM: band cells in use (b = j - i + EXT_B)
@@ -98,7 +112,7 @@ __device__ __forceinline__ unsigned ext_genome_code(const uint32_t *__restrict__
     const unsigned c = (bases[g >> 4] >> (2 * (int)(g & 15))) & 3u;
     return ((nmask[g >> 5] >> (int)(g & 31)) & 1u) ? 4u : c;
 }
-// the same through the word cache; g moves by one base per call in direction E.dir
+// (tandem mode) the same through the word cache; g moves by one base per call in direction E.dir
 template <class M>
 __device__ __forceinline__ unsigned ext_genome_next(ExtStateT<M> &E, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, int64_t g) {
     const int64_t wi = g >> 4, mi = g >> 5;
@@ -107,55 +121,114 @@ __device__ __forceinline__ unsigned ext_genome_next(ExtStateT<M> &E, const uint3
     const unsigned c = (E.gw >> (2 * (int)(g & 15))) & 3u;
     return ((E.mw >> (int)(g & 31)) & 1u) ? 4u : c;
 }
-// code of the query base at byte address a (relative to q4) / PACKEDQ: at genome position a; a moves by E.step per call
-template <class M>
-__device__ __forceinline__ unsigned ext_query_next(ExtStateT<M> &E, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, int64_t a) {
-    if (M::PACKEDQ) return a >= 0 ? ext_genome_code(bases, nmask, a) : 4u;
-    const int64_t wi = a >> 2;
-    if (wi != E.qwi) { E.qw = E.qwn; E.qwn = E.qwn2; E.qwn2 = E.qwn3; E.qwi = wi; const int64_t nx = wi + 3 * E.step; E.qwn3 = E.q4[nx > 0 ? nx : 0]; }
-    return ext_cand_code((E.qw >> (8 * (int)(a & 3))) & 0xffu, E.comp);
+// 16 groups of two bits / the low 16 bits in reverse order
+__device__ __forceinline__ uint32_t ext_rev16_codes(uint32_t x) {
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0f0f0f0fu) | ((x & 0x0f0f0f0fu) << 4);
+    return __builtin_bswap32(x);
 }
-// The bases of the next column, steady state: genome base g (if want_g) and the query base at a, through the word caches.  The
-// memory counter of a wavefront is in order, so a wait for a word requested 16 columns ago is also a wait for everything
-// requested since: with rotate-and-request per stream (genome words, mask words, query words) the second stream's rotation
-// waited for the first stream's request of the SAME column, a full trip to memory in nearly every column of a wavefront whose 64
-// lanes rotate at different times.  Here every rotation (which reads words requested in EARLIER columns) comes first, then all
-// the requests: they have a whole column, and the other wavefronts' columns, to arrive.
+__device__ __forceinline__ uint32_t ext_rev16_bits(uint32_t x) {
+    x = ((x >> 1) & 0x5555u) | ((x & 0x5555u) << 1);
+    x = ((x >> 2) & 0x3333u) | ((x & 0x3333u) << 2);
+    x = ((x >> 4) & 0x0f0fu) | ((x & 0x0f0fu) << 4);
+    return ((x >> 8) & 0xffu) | ((x & 0xffu) << 8);
+}
+// Genome bases number j0 .. j0 + 15 (1-based in walking order): false if none of them can be used (the last one that can is
+// min(jmax, n + EXT_B)); else the position of the lowest, the highest position any chunk of this extension uses, and how many of the
+// 16 can be used.  Words are read between word 0 and the word of `top` only: a word index outside is clamped, and the bases such
+// a word stands in for are beyond the last usable one
 template <class M>
-__device__ __forceinline__ void ext_fetch(ExtStateT<M> &E, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask,
-                                          bool want_g, int64_t g, int64_t a, unsigned &gc, unsigned &qc) {
-    const int64_t wi = g >> 4, mi = g >> 5;
-    const bool rg = want_g && wi != E.gwi, rm = want_g && mi != E.mwi;
-    const int64_t qi = a >> 2;
-    const bool rq = !M::PACKEDQ && qi != E.qwi;
-    // rotate
-    if (rg) { EXT_KEEP_BRANCH(); E.gw = E.gwn; E.gwn = E.gwn2; E.gwi = wi; }
-    if (rm) { EXT_KEEP_BRANCH(); E.mw = E.mwn; E.mwi = mi; }
-    if (rq) { EXT_KEEP_BRANCH(); E.qw = E.qwn; E.qwn = E.qwn2; E.qwn2 = E.qwn3; E.qwi = qi; }
-    EXT_PIN_ROTATED(E);
-    // request
-    if (rg) { const int64_t nx = wi + 2 * E.dir; E.gwn2 = bases[nx > 0 ? nx : 0]; }
-    if (rm) { const int64_t nx = mi + E.dir; E.mwn = nmask[nx > 0 ? nx : 0]; }
-    if (!M::PACKEDQ && rq) { const int64_t nx = qi + 3 * E.step; E.qwn3 = E.q4[nx > 0 ? nx : 0]; }
-    // decode
-    {
-        const unsigned c = (E.gw >> (2 * (int)(g & 15))) & 3u;
-        gc = want_g ? (((E.mw >> (int)(g & 31)) & 1u) ? 4u : c) : 4u;
+__device__ __forceinline__ bool ext_gchunk_place(const ExtStateT<M> &E, int j0, int64_t &glo, int64_t &top, int &nvalid) {
+    const int64_t jn = (int64_t)E.n + EXT_B, jl = E.jmax < jn ? E.jmax : jn;
+    if ((int64_t)j0 > jl) return false;
+    glo = E.dir > 0 ? E.g0 + j0 - 1 : E.g0 - j0 - 15;
+    top = E.dir > 0 ? E.g0 + jl - 1 : E.g0 - 1;
+    nvalid = jl - j0 >= 15 ? 16 : (int)(jl - j0) + 1;
+    return true;
+}
+template <class M>
+__device__ __forceinline__ void ext_gchunk_request(const ExtStateT<M> &E, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, int j0,
+                                                   uint32_t &g0, uint32_t &g1, uint32_t &m0, uint32_t &m1) {
+    int64_t glo, top;
+    int nv;
+    if (!ext_gchunk_place(E, j0, glo, top, nv)) return;
+    const int64_t w = glo >> 4, wt = top >> 4, m = glo >> 5, mt = top >> 5;
+    g0 = bases[w > 0 ? w : 0]; g1 = bases[w + 1 < wt ? w + 1 : wt];
+    m0 = nmask[m > 0 ? m : 0]; m1 = nmask[m + 1 < mt ? m + 1 : mt];
+}
+// -> the 16 codes (the first in walking order in bits 0..1) and their "never matches" bits
+template <class M>
+__device__ __forceinline__ void ext_gchunk_decode(const ExtStateT<M> &E, int j0, uint32_t g0, uint32_t g1, uint32_t m0, uint32_t m1, uint32_t &codes, uint32_t &nn) {
+    int64_t glo, top;
+    int nv;
+    codes = 0u; nn = 0xffffu;
+    if (!ext_gchunk_place(E, j0, glo, top, nv)) return;
+    uint32_t c = (uint32_t)((((uint64_t)g1 << 32) | g0) >> (2 * (int)(glo & 15)));
+    uint32_t b = (uint32_t)((((uint64_t)m1 << 32) | m0) >> (int)(glo & 31)) & 0xffffu;
+    if (E.dir < 0) { c = ext_rev16_codes(c); b = ext_rev16_bits(b); }
+    codes = c; nn = (b | (0xffffu << nv)) & 0xffffu;
+}
+// request chunk k of both streams into C: nothing here waits.  Candidate bytes are read from p0 to 15 bytes beyond the last base
+// of the extension (step > 0) and never below byte 0 (step < 0: the read is moved up, ext_append moves the bases back down)
+template <class M>
+__device__ __forceinline__ void ext_request(const ExtStateT<M> &E, ExtChunk &C, int k, const uint8_t *__restrict__ q, const uint32_t *__restrict__ bases,
+                                            const uint32_t *__restrict__ nmask) {
+    C.k = k;
+    if (16 * (int64_t)k >= (int64_t)E.n) return;
+    ext_gchunk_request(E, bases, nmask, 16 * k + 1 + EXT_B, C.g0, C.g1, C.m0, C.m1);
+    const int64_t lo = E.step > 0 ? E.p0 + 16 * (int64_t)k : E.p0 - 16 * (int64_t)k - 15;
+    uint32_t t[4];
+    __builtin_memcpy(t, q + (lo > 0 ? lo : 0), 16);
+    C.q0 = t[0]; C.q1 = t[1]; C.q2 = t[2]; C.q3 = t[3];
+}
+// decode chunk C and put it behind the windows (E.cnt <= 16).  This is where the words of C are waited for
+template <class M>
+__device__ __forceinline__ void ext_append(ExtStateT<M> &E, const ExtChunk &C) {
+    uint32_t gc = 0u, gn = 0xffffu, qc = 0u, qn = 0xffffu;
+    if (16 * (int64_t)C.k < (int64_t)E.n) {
+        ext_gchunk_decode(E, 16 * C.k + 1 + EXT_B, C.g0, C.g1, C.m0, C.m1, gc, gn);
+        const uint32_t t[4] = {C.q0, C.q1, C.q2, C.q3};
+        qn = 0u;
+#pragma unroll
+        for (int b = 0; b < 16; b++) {
+            const unsigned cd = ext_cand_code((t[b >> 2] >> (8 * (b & 3))) & 0xffu, E.comp);
+            qc |= (cd & 3u) << (2 * b); qn |= (cd >> 2) << b;
+        }
+        if (E.step < 0) {
+            const int64_t lo = E.p0 - 16 * (int64_t)C.k - 15;
+            const int sh = lo < 0 ? (int)-lo : 0;           // (<= 15: the first base of the chunk is a byte of the buffer)
+            qc = ext_rev16_codes(qc) >> (2 * sh); qn = ((ext_rev16_bits(qn) | 0xffff0000u) >> sh) & 0xffffu;
+        }
     }
-    if (M::PACKEDQ) qc = a >= 0 ? ext_genome_code(bases, nmask, a) : 4u;      // (not used: the masker keeps the per-stream form, ext_step)
-    else qc = ext_cand_code((E.qw >> (8 * (int)(a & 3))) & 0xffu, E.comp);
+    E.gwin |= (uint64_t)gc << (2 * E.cnt); E.gnm |= gn << E.cnt;
+    E.qwin |= (uint64_t)qc << (2 * E.cnt); E.qnm |= qn << E.cnt;
+    E.cnt += 16;
+}
+// Copy mode: the only place of the steady state that waits and loads.  A lane whose windows hold at most 16 bases appends the pending
+// chunk and requests the next one through q (the pointer ext_init was given); a lane with more does nothing.  Called every 16
+// columns, a lane enters the next 16 with 17..32 bases, and what it appends was requested 16 columns ago or by ext_init
+template <class M>
+__device__ __forceinline__ void ext_refill(ExtStateT<M> &E, const uint8_t *__restrict__ q, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask) {
+    if (M::PACKEDQ) return;
+    if (E.cnt <= 16) {
+        EXT_KEEP_BRANCH();
+        ext_append(E, E.pend);
+        ext_request(E, E.pend, E.pend.k + 1, q, bases, nmask);
+    }
+}
+// the next base of both streams out of the windows
+template <class M>
+__device__ __forceinline__ void ext_shift(ExtStateT<M> &E) {
+    E.gnext_ = (E.gnm & 1u) ? 4u : (unsigned)(E.gwin & 3u);
+    E.qnext_ = (E.qnm & 1u) ? 4u : (unsigned)(E.qwin & 3u);
+    E.gwin >>= 2; E.gnm >>= 1; E.qwin >>= 2; E.qnm >>= 1; E.cnt--;
 }
 // dlo .. dhi: the diagonals j - i in use (DIAGLIM only; else all of the band)
 template <class M>
 __device__ __forceinline__ void ext_init(ExtStateT<M> &E, const uint8_t *__restrict__ q, int64_t p0, int step, bool comp, int n,
                                          const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, int64_t g0, int dir, int64_t jmax,
                                          int dlo = -EXT_B, int dhi = EXT_B) {
-    if (M::PACKEDQ) { E.q4 = nullptr; E.p0 = p0; }
-    else {
-        const uintptr_t qa = (uintptr_t)q;
-        E.q4 = (const uint32_t *)(qa & ~(uintptr_t)3);
-        E.p0 = p0 + (int64_t)(qa & 3);           // byte offset of the first query base from q4
-    }
+    E.q = M::PACKEDQ ? nullptr : q; E.p0 = p0;
     E.step = step; E.comp = comp; E.n = n; E.g0 = g0; E.dir = dir; E.jmax = jmax;
     E.blo = dlo + EXT_B; E.bhi = dhi + EXT_B;
 #pragma unroll
@@ -166,21 +239,39 @@ __device__ __forceinline__ void ext_init(ExtStateT<M> &E, const uint8_t *__restr
     E.best_i = 0; E.best_t = 0; E.best_s = 0; E.i = 1;
     E.W0 = 0u; E.W1 = 0u; E.WN = (1u << EXT_W) - 1u;
     E.gnext_ = 4u; E.qnext_ = 4u;
+    E.gwin = 0ull; E.qwin = 0ull; E.gnm = 0u; E.qnm = 0u; E.cnt = 0;
+    E.pend.k = 0; E.pend.g0 = E.pend.g1 = E.pend.m0 = E.pend.m1 = 0u; E.pend.q0 = E.pend.q1 = E.pend.q2 = E.pend.q3 = 0u;
+    E.gw = E.gwn = E.gwn2 = E.mw = E.mwn = 0u; E.gwi = E.mwi = 0;
     if (n < 1) return;
-    // word caches: the first genome base read is number 1 (g0 or g0 - 1), the first query byte p0
+    if (!M::PACKEDQ) {
+        // the requests of what is used here first (the eight bases of the planes, chunks 0 and 1 for the windows), then the waits;
+        // chunk 2 is requested behind them and stays pending
+        uint32_t a0 = 0u, a1 = 0u, b0 = 0u, b1 = 0u, pc, pn;
+        ExtChunk C0 = E.pend, C1 = E.pend;
+        ext_gchunk_request(E, bases, nmask, 1, a0, a1, b0, b1);
+        ext_request(E, C0, 0, q, bases, nmask);
+        ext_request(E, C1, 1, q, bases, nmask);
+        // planes of "column 0": bit b = genome base number j = b - EXT_B (1-based in walking order); bit set in WN = never matches
+        ext_gchunk_decode(E, 1, a0, a1, b0, b1, pc, pn);
+#pragma unroll
+        for (int j = 1; j <= EXT_B; j++) {
+            const unsigned cd = ((pn >> (j - 1)) & 1u) ? 4u : ((pc >> (2 * (j - 1))) & 3u);
+            E.W0 |= (cd & 1u) << (j + EXT_B); E.W1 |= ((cd >> 1) & 1u) << (j + EXT_B); E.WN &= ~((~(cd >> 2) & 1u) << (j + EXT_B));
+        }
+        ext_append(E, C0);
+        ext_append(E, C1);
+        ext_request(E, E.pend, 2, q, bases, nmask);
+        ext_shift(E);
+        return;
+    }
+    // tandem mode.  Word caches: the first genome base read is number 1 (g0 or g0 - 1)
     {
         const int64_t g = dir > 0 ? g0 : g0 - 1;
         const int64_t gs = g > 0 ? g : 0;
         E.gwi = gs >> 4; E.gw = bases[E.gwi];
         { const int64_t n1 = E.gwi + dir, n2 = E.gwi + 2 * dir; E.gwn = bases[n1 > 0 ? n1 : 0]; E.gwn2 = bases[n2 > 0 ? n2 : 0]; }
         E.mwi = gs >> 5; E.mw = nmask[E.mwi]; { const int64_t nx = E.mwi + dir; E.mwn = nmask[nx > 0 ? nx : 0]; }
-        if (!M::PACKEDQ) {
-            E.qwi = E.p0 >> 2; E.qw = E.q4[E.qwi];
-            const int64_t n1 = E.qwi + step, n2 = E.qwi + 2 * step, n3 = E.qwi + 3 * step;
-            E.qwn = E.q4[n1 > 0 ? n1 : 0]; E.qwn2 = E.q4[n2 > 0 ? n2 : 0]; E.qwn3 = E.q4[n3 > 0 ? n3 : 0];
-        }
     }
-    // planes of "column 0": bit b = genome base number j = b - EXT_B (1-based in walking order); bit set in WN = never matches
 #pragma unroll
     for (int j = 1; j <= EXT_B; j++) {
         if (j <= jmax) {
@@ -189,7 +280,7 @@ __device__ __forceinline__ void ext_init(ExtStateT<M> &E, const uint8_t *__restr
         }
     }
     if (1 + EXT_B <= jmax) E.gnext_ = ext_genome_next(E, bases, nmask, dir > 0 ? g0 + EXT_B : g0 - 1 - EXT_B);
-    E.qnext_ = ext_query_next(E, bases, nmask, E.p0);
+    E.qnext_ = p0 >= 0 ? ext_genome_code(bases, nmask, p0) : 4u;
 }
 // the 17 cell values of the column just finished (E.i - 1) from the bit-parallel form; cells before the first genome base: EXT_INF
 template <class M>
@@ -205,8 +296,9 @@ __device__ __forceinline__ void ext_expand(ExtStateT<M> &E) {
     E.fast = false;
 }
 // one column (E.i <= E.n on entry); returns true when the extension is finished (result in best_i / best_t / best_s).
-// lut: the table of ext_lut_entry (unused, may be null, in the tandem mode)
-template <class M>
+// lut: the table of ext_lut_entry (unused, may be null, in the tandem mode).  SELF_REFILL = false: the caller keeps the windows filled
+// (ext_refill at least every 16 columns, the first time at most 15 columns after ext_init) and the column carries no check for it
+template <class M, bool SELF_REFILL = true>
 __device__ __forceinline__ bool ext_step(ExtStateT<M> &E, const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, EXT_LUT_PTR lut) {
     const int i = E.i;
     const unsigned gc = E.gnext_, qc = E.qnext_;
@@ -214,8 +306,13 @@ __device__ __forceinline__ bool ext_step(ExtStateT<M> &E, const uint32_t *__rest
         const int64_t j = (int64_t)i + 1 + EXT_B;
         if (M::PACKEDQ) {     // the masker: a lane runs one extension from start to end, rotate-and-request per stream is the faster form there (measured)
             E.gnext_ = j <= E.jmax ? ext_genome_next(E, bases, nmask, E.dir > 0 ? E.g0 + j - 1 : E.g0 - j) : 4u;
-            E.qnext_ = ext_query_next(E, bases, nmask, E.p0 + (int64_t)E.step * i);
-        } else ext_fetch(E, bases, nmask, j <= E.jmax, E.dir > 0 ? E.g0 + j - 1 : E.g0 - j, E.p0 + (int64_t)E.step * i, E.gnext_, E.qnext_);
+            const int64_t a = E.p0 + (int64_t)E.step * i;
+            E.qnext_ = a >= 0 ? ext_genome_code(bases, nmask, a) : 4u;
+        } else {              // the copy finder: out of the windows.  Its kernel refills them every 16 columns (ext_refill) and never finds them
+                              // empty; a caller that does not is served here, with a wait for memory in every 16th column
+            if (SELF_REFILL && E.cnt == 0) { EXT_KEEP_BRANCH(); ext_refill(E, E.q, bases, nmask); }
+            ext_shift(E);
+        }
     }
     E.W0 = (E.W0 >> 1) | ((gc & 1u) << (EXT_W - 1)); E.W1 = (E.W1 >> 1) | (((gc >> 1) & 1u) << (EXT_W - 1)); E.WN = (E.WN >> 1) | ((gc >> 2) << (EXT_W - 1));
     const uint32_t eq = qc < 4u ? (~(E.W0 ^ (0u - (qc & 1u))) & ~(E.W1 ^ (0u - ((qc >> 1) & 1u))) & ~E.WN) : 0u;
@@ -287,7 +384,10 @@ __device__ __forceinline__ void ext_align_dev(const uint8_t *__restrict__ q, int
                                               int64_t jmax, int dlo, int dhi, int *i_out, int *t_out, int *s_out, EXT_LUT_PTR lut) {
     ExtStateT<M> E;
     ext_init(E, q, p0, step, comp, n, bases, nmask, g0, dir, jmax, dlo, dhi);
-    if (n >= 1) while (!ext_step(E, bases, nmask, lut)) { }
+    if (n >= 1) for (int k = 0;; k++) {
+        if ((k & 15) == 0) ext_refill(E, q, bases, nmask);
+        if (ext_step(E, bases, nmask, lut)) break;
+    }
     *i_out = E.best_i; *t_out = E.best_t; *s_out = E.best_s;
 }
 // <<< ext_align_dev
