@@ -97,6 +97,19 @@ class Context:
         Both write the same bytes."""
         self._check(self.lib.hite_fill_config_ctx(self.h, -1 if tiles is None else int(bool(tiles))), "hite_fill_config_ctx")
 
+    def gather_config(self, chunks):
+        """which form of the fine stage's window gather THIS context runs (include/hite_gpu.h hite_gather_config_ctx): True = in chunks of
+        the destination (the default), False = a wavefront per row, None = follow the process default again (HITE_GATHER_CHUNKS=0: per
+        row).  Both write the same window bytes."""
+        self._check(self.lib.hite_gather_config_ctx(self.h, -1 if chunks is None else int(bool(chunks))), "hite_gather_config_ctx")
+
+    def gather_mode(self):
+        """the form of the window gather the next call of this context runs: True = chunks, False = a wavefront per row"""
+        m = self.lib.hite_gather_mode_ctx(self.h)
+        if m < 0:
+            raise HiteError("hite_gather_mode_ctx failed: %d" % m)
+        return bool(m)
+
     def fallback_overlap(self, mode):
         """whether the star alignment of THIS context runs its fall-back alignment beside the layout of the candidates the fall-back does
         not touch (include/hite_gpu.h hite_fallback_overlap_ctx): True / 1 = beside (the default), False / 0 = one after the other,

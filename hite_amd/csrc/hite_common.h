@@ -71,6 +71,7 @@ struct hite_ctx {
     int msa_max_len;                 // its longest window (the tile form's grid)
     int32_t fill_tiles;              // hite_fill_config_ctx: 1 the tile form of the sparse fill / 0 the per-cell form / -1 the process default
     int32_t fallback_overlap;        // hite_fallback_overlap_ctx: 1 the fall-back alignment beside the layout of the other candidates / 0 serial / -1 the process default
+    int32_t gather_chunks;           // hite_gather_config_ctx: 1 the window gather in chunks of the destination / 0 a wavefront per row / -1 the process default
     const int64_t *d_msa_win_off;    // per row of the last star alignment: its window, and where its back pads begin (HITE_IS_ROW_PAD;
     const int32_t *d_msa_win_len;    // layout, fill and the judge's LDS kernels read the rows through these)
     const uint32_t *d_msa_pads;      // per row: pad bytes in front | behind << 16

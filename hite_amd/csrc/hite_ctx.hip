@@ -26,6 +26,7 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
     c->device = device_id;
     c->copy_interval = -1;
     c->fill_tiles = -1;
+    c->gather_chunks = -1;
     c->fallback_overlap = -1;
     // test knobs of hite_msa_subcluster (hite_subcluster.hip), read here so that two contexts of a process may differ
     c->subcluster_chunk = HITE_SUBCLUSTER_CHUNK;

@@ -138,6 +138,161 @@ __device__ __forceinline__ void emit_span(const uint32_t *__restrict__ bases, co
 
 // <<< genome_decode
 
+// >>> gather_chunk (tests/test_host_gather_chunk.py compiles this block for the host, behind genome_decode, and compares it chunk by
+// chunk with plain slicing + pads)
+// What the window gather needs to know about a row (row_meta_kernel writes one per row; the gather reads nothing else about it but
+// where its slot lies).  The row as it is written: `a` pad bytes, the window [g_lo, g_lo + len) read on its strand, `b` pad bytes;
+// under GR_TRUNC the first 500 and the last 500 bytes of that.  A pad byte is the centre's base it faces in lower case -- front pad
+// byte i = centre base i, back pad byte j = centre base c_len - b + j -- or HITE_ROW_PAD where the centre has no such base.
+struct __attribute__((aligned(16))) GatherRow {
+    int64_t g_lo, c_g_lo;      // first base of the window / of the centre's window in the packed genome
+    int32_t len, c_len;        // their lengths (0: no window; else >= 100, window_rule)
+    uint16_t a, b;             // pad bytes in front / behind (pad_lengths)
+    uint32_t flags;
+};
+#define GR_MINUS 1u            // the window is read reverse-complemented
+#define GR_TRUNC 2u            // the first500 + last500 form
+#define GR_CMINUS 4u           // the centre's window is read reverse-complemented
+#define GR_ITEM_CHUNKS 256     // chunks (of 16 bytes) of a row that one wavefront takes at a time
+
+__device__ __forceinline__ int gather_row_len(const GatherRow &R) {
+    if (R.len <= 0) return 0;
+    return (R.flags & GR_TRUNC) ? 1000 : (int)R.a + R.len + (int)R.b;
+}
+// the 16 packed bases that hold positions p .. p + 15 of a window (len >= 16), never leaving the window: the fetch is moved inside
+// and gather_align shifts it back, so that nothing in front of g_lo or behind the window's last base is ever asked for
+__device__ __forceinline__ int gather_clamp(int len, int p) { return p < 0 ? 0 : (p > len - 16 ? len - 16 : p); }
+__device__ __forceinline__ int64_t gather_fetch_pos(int64_t g_lo, int len, bool minus, int p) {
+    if (len < 16) return g_lo;                                         // (no window: nothing of the fetch is used)
+    const int pf = gather_clamp(len, p);
+    return minus ? g_lo + len - 16 - pf : g_lo + pf;
+}
+// what fetch16_codes read at gather_fetch_pos -> base i = position p + i of the window (whatever lies outside it is not defined)
+__device__ __forceinline__ void gather_align(int len, bool minus, int p, uint32_t &codes, uint32_t &nb) {
+    if (minus) revcomp16_codes(codes, nb);
+    int s = p - gather_clamp(len, p);
+    s = s < -15 ? -15 : (s > 15 ? 15 : s);
+    if (s > 0) { codes >>= 2 * s; nb >>= s; }
+    else if (s < 0) { codes <<= -2 * s; nb = (nb << -s) & 0xffffu; }
+}
+__device__ __forceinline__ uint4 gather_ascii16(uint32_t codes, uint32_t nb) {
+    uint4 v;
+    v.x = ascii4(codes & 0xffu, nb & 0xfu);
+    v.y = ascii4((codes >> 8) & 0xffu, (nb >> 4) & 0xfu);
+    v.z = ascii4((codes >> 16) & 0xffu, (nb >> 8) & 0xfu);
+    v.w = ascii4(codes >> 24, (nb >> 12) & 0xfu);
+    return v;
+}
+// bits lo .. hi - 1 of a 16-bit mask (any lo, hi)
+__device__ __forceinline__ uint32_t gather_bits(int lo, int hi) {
+    lo = lo < 0 ? 0 : (lo > 16 ? 16 : lo);
+    hi = hi < 0 ? 0 : (hi > 16 ? 16 : hi);
+    return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+}
+__device__ __forceinline__ uint32_t gather_bytes4(uint32_t m4) {     // bit i -> byte i all ones
+    return (((m4 | (m4 << 7) | (m4 << 14) | (m4 << 21)) & 0x01010101u)) * 0xffu;
+}
+// v where the mask has a bit, else w
+__device__ __forceinline__ uint4 gather_select(uint32_t m16, const uint4 &v, const uint4 &w) {
+    const uint32_t fx = gather_bytes4(m16 & 0xfu), fy = gather_bytes4((m16 >> 4) & 0xfu), fz = gather_bytes4((m16 >> 8) & 0xfu),
+                   fw = gather_bytes4((m16 >> 12) & 0xfu);
+    uint4 o;
+    o.x = (v.x & fx) | (w.x & ~fx); o.y = (v.y & fy) | (w.y & ~fy); o.z = (v.z & fz) | (w.z & ~fz); o.w = (v.w & fw) | (w.w & ~fw);
+    return o;
+}
+// 16 pad bytes that face the centre's positions pc .. pc + 15
+__device__ __forceinline__ uint4 gather_pad16(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, const GatherRow &R,
+                                              int pc) {
+    uint4 pad;
+    pad.x = pad.y = pad.z = pad.w = 0x01010101u * (uint32_t)HITE_ROW_PAD;
+    const uint32_t have = gather_bits(-pc, R.c_len - pc);
+    if (!have) return pad;
+    const bool cm = (R.flags & GR_CMINUS) != 0;
+    uint32_t codes, nb;
+    fetch16_codes(bases, nmask, gather_fetch_pos(R.c_g_lo, R.c_len, cm, pc), codes, nb);
+    gather_align(R.c_len, cm, pc, codes, nb);
+    uint4 v = gather_ascii16(codes, nb);
+    v.x |= 0x20202020u; v.y |= 0x20202020u; v.z |= 0x20202020u; v.w |= 0x20202020u;
+    return gather_select(have, v, pad);
+}
+// bytes i0 .. i1 - 1 of a chunk whose byte i is position P + i of the PADDED window (the rest zero); codes / nb: what fetch16_codes
+// read at gather_fetch_pos(R.g_lo, R.len, minus, P - a)
+__device__ __forceinline__ uint4 gather_seg(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, const GatherRow &R,
+                                            int P, int i0, int i1, uint32_t codes, uint32_t nb) {
+    uint4 out;
+    out.x = out.y = out.z = out.w = 0u;
+    const uint32_t mr = gather_bits(i0, i1);
+    const int a = R.a, e = a + R.len;                                  // the window's bases: padded positions a .. e - 1
+    const uint32_t mw = mr & gather_bits(a - P, e - P), mf = mr & gather_bits(0, a - P), mb = mr & gather_bits(e - P, 16);
+    if (mw) {
+        gather_align(R.len, (R.flags & GR_MINUS) != 0, P - a, codes, nb);
+        out = gather_select(mw, gather_ascii16(codes, nb), out);
+    }
+    if (mf) out = gather_select(mf, gather_pad16(bases, nmask, R, P), out);
+    if (mb) out = gather_select(mb, gather_pad16(bases, nmask, R, P - e + R.c_len - (int)R.b), out);
+    return out;
+}
+// chunk q of a row (bytes 16 q .. 16 q + 15 of its slot) is bytes 0 .. nA - 1 at padded position PA + i and, only in the chunk that
+// holds the seam of the first500 + last500 form (nA < 16), bytes nA .. 15 at padded position PB + i
+__device__ __forceinline__ void gather_chunk_plan(const GatherRow &R, int q, int &PA, int &nA, int &PB) {
+    const int o0 = 16 * q;
+    PA = o0; nA = 16; PB = 0;
+    if (R.flags & GR_TRUNC) {
+        const int shift = (int)R.a + R.len + (int)R.b - 1000;          // output offset o >= 500 is padded position o + shift
+        if (o0 >= 500) PA = o0 + shift;
+        else if (o0 + 16 > 500) { nA = 500 - o0; PB = o0 + shift; }
+    }
+}
+// where the chunk's first 16 bases are fetched (the one load every chunk needs; the kernel issues it for several chunks at once)
+__device__ __forceinline__ int64_t gather_chunk_src(const GatherRow &R, int q) {
+    int PA, nA, PB;
+    gather_chunk_plan(R, q, PA, nA, PB);
+    return gather_fetch_pos(R.g_lo, R.len, (R.flags & GR_MINUS) != 0, PA - (int)R.a);
+}
+// the common case: the chunk lies wholly in window bases ...
+__device__ __forceinline__ bool gather_chunk_plain(const GatherRow &R, int q) {
+    int PA, nA, PB;
+    gather_chunk_plan(R, q, PA, nA, PB);
+    return nA == 16 && PA >= (int)R.a && PA + 16 <= (int)R.a + R.len;
+}
+// ... and is one decode of what fetch16_codes read at gather_chunk_src
+__device__ __forceinline__ uint4 gather_chunk_decode(const GatherRow &R, uint32_t codes, uint32_t nb) {
+    if (R.flags & GR_MINUS) revcomp16_codes(codes, nb);
+    return gather_ascii16(codes, nb);
+}
+// the 16 bytes of any chunk q from what fetch16_codes read at gather_chunk_src: a chunk that touches a pad, the seam or the row's end
+// is put together in registers (a second fetch behind the seam, the centre's for a pad), and the bytes behind the row's length are zero
+__device__ __forceinline__ uint4 gather_chunk_bytes(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, const GatherRow &R,
+                                                    int q, uint32_t codes, uint32_t nb) {
+    if (gather_chunk_plain(R, q)) return gather_chunk_decode(R, codes, nb);
+    int PA, nA, PB;
+    gather_chunk_plan(R, q, PA, nA, PB);
+    const int a = R.a;
+    const bool minus = (R.flags & GR_MINUS) != 0;
+    const int left = gather_row_len(R) - 16 * q;                       // bytes of the row from this chunk on
+    uint4 out = gather_seg(bases, nmask, R, PA, 0, nA < left ? nA : left, codes, nb);
+    if (nA < 16 && left > nA) {
+        fetch16_codes(bases, nmask, gather_fetch_pos(R.g_lo, R.len, minus, PB - a), codes, nb);
+        const uint4 o2 = gather_seg(bases, nmask, R, PB, nA, left < 16 ? left : 16, codes, nb);
+        out.x |= o2.x; out.y |= o2.y; out.z |= o2.z; out.w |= o2.w;
+    }
+    return out;
+}
+// fetch16_codes in two halves, for a kernel that asks for the words of several chunks before it uses the first: the two words of
+// `bases` and the two of `nmask` that hold the 16 bases from packed index g on (bases[g >> 4], the next; nmask[g >> 5], the next)
+// -> their codes and "not ACGT" bits
+__device__ __forceinline__ void gather_words16(uint32_t b0, uint32_t b1, uint32_t m0, uint32_t m1, int64_t g, uint32_t &codes, uint32_t &nb) {
+    codes = (uint32_t)(((uint64_t)b0 | ((uint64_t)b1 << 32)) >> ((int)(g & 15) * 2));
+    nb = (uint32_t)(((uint64_t)m0 | ((uint64_t)m1 << 32)) >> (int)(g & 31)) & 0xffffu;
+}
+__device__ __forceinline__ uint4 gather_chunk(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask, const GatherRow &R, int q) {
+    uint32_t codes, nb;
+    const int64_t g = gather_chunk_src(R, q);
+    gather_words16(bases[g >> 4], bases[(g >> 4) + 1], nmask[g >> 5], nmask[(g >> 5) + 1], g, codes, nb);
+    return gather_chunk_bytes(bases, nmask, R, q, codes, nb);
+}
+// <<< gather_chunk
+
 static __global__ void flank_sizes_kernel(const int64_t *__restrict__ coff, int32_t ncontig, int64_t n,
                                    const int32_t *__restrict__ contig, const int64_t *__restrict__ s1,
                                    const int64_t *__restrict__ e1, int32_t flank, int64_t *__restrict__ out_len,

@@ -191,7 +191,12 @@ __global__ void row_meta_kernel(int n, const int64_t *__restrict__ row_first, co
                                 int32_t *__restrict__ row_pad, uint8_t *__restrict__ row_trunc,
                                 int32_t *__restrict__ maxlen, const uint32_t *__restrict__ clip /* per copy, or NULL */,
                                 const uint8_t *__restrict__ minus,
-                                int32_t *__restrict__ row_cp0 /* per row: the copy of its candidate's centre (clip != NULL) */) {
+                                int32_t *__restrict__ row_cp0 /* per row: the copy of its candidate's centre (clip != NULL) */,
+                                // the chunk form of the gather (desc != NULL): what it needs of a row in one record, and how many
+                                // items (runs of GR_ITEM_CHUNKS chunks of its slot) the row is
+                                GatherRow *__restrict__ desc, int32_t *__restrict__ row_items, const int64_t *__restrict__ coff,
+                                int32_t ncontig, const int32_t *__restrict__ contig, const int64_t *__restrict__ s1,
+                                const int64_t *__restrict__ e1, int32_t flank) {
     int c = blockIdx.x;
     if (c >= n) return;
     if (threadIdx.x == 0) { row_first32[c] = (int32_t)row_first[c]; if (c == n - 1) row_first32[n] = (int32_t)row_first[n]; }
@@ -201,16 +206,32 @@ __global__ void row_meta_kernel(int n, const int64_t *__restrict__ row_first, co
     for (int r = threadIdx.x; r < R; r += blockDim.x) {
         int64_t g = row_first[c] + r;
         int cp = sel[(int64_t)c * MAXROWS + r];
+        const int cp0 = sel[(int64_t)c * MAXROWS];
         // (the rows of the first500 + last500 form are cut from the PADDED window: still 1000 bytes; the centre, row 0, is never padded)
         int pa, pb;
-        pad_lengths(clip, minus, cp, sel[(int64_t)c * MAXROWS], pa, pb);
+        pad_lengths(clip, minus, cp, cp0, pa, pb);
         int L = md == 2 ? 1000 : (int)len[cp] + pa + pb;
         row_copy[g] = cp;
-        if (clip) row_cp0[g] = sel[(int64_t)c * MAXROWS];
+        if (clip) row_cp0[g] = cp0;
         row_len[g] = L;
         row_pad[g] = (L + 15) & ~15;
         row_trunc[g] = md == 2;
         mx = L > mx ? L : mx;
+        if (desc) {
+            GatherRow D;
+            int64_t wl, tl, g_lo;
+            window_rule(coff, ncontig, contig[cp], s1[cp], e1[cp], flank, wl, tl, g_lo);
+            D.g_lo = g_lo; D.len = (int32_t)wl; D.a = (uint16_t)pa; D.b = (uint16_t)pb;
+            D.flags = (minus[cp] ? GR_MINUS : 0u) | (md == 2 ? GR_TRUNC : 0u);
+            D.c_g_lo = 0; D.c_len = 0;
+            if (pa | pb) {
+                window_rule(coff, ncontig, contig[cp0], s1[cp0], e1[cp0], flank, wl, tl, g_lo);
+                D.c_g_lo = g_lo; D.c_len = (int32_t)wl;
+                if (minus[cp0]) D.flags |= GR_CMINUS;
+            }
+            desc[g] = D;
+            row_items[g] = (((L + 15) >> 4) + GR_ITEM_CHUNKS - 1) / GR_ITEM_CHUNKS;
+        }
     }
     // one atomic per wavefront (one per row on a single address was half a millisecond per launch) -- and only from a wavefront
     // whose maximum beats what the word already holds (round 6: a maximum only grows, so a stale read can at worst let a needless
@@ -307,6 +328,153 @@ __global__ void __launch_bounds__(256) row_gather_kernel(const uint32_t *__restr
         emit_span(bases, nmask, g_lo, len, mn, len - 500, 500, dst + 500, lane);
     } else {
         emit_span(bases, nmask, g_lo, len, mn, 0, len, dst, lane);
+    }
+}
+
+// ---- the gather in chunks of the destination (the default; HITE_GATHER_CHUNKS=0 / hite_gather_config_ctx: the kernel above) ----
+// which form a context runs: 1 = chunks, 0 = a wavefront per row, -1 = the process default, taken from the environment once
+static int g_gather_chunks = -1;
+static int gather_chunks_mode(const hite_ctx *ctx) {
+    if (ctx->gather_chunks >= 0) return ctx->gather_chunks;
+    int v = __atomic_load_n(&g_gather_chunks, __ATOMIC_RELAXED);
+    if (v < 0) {
+        const char *e = getenv("HITE_GATHER_CHUNKS");
+        v = (e && !strcmp(e, "0")) ? 0 : 1;
+        __atomic_store_n(&g_gather_chunks, v, __ATOMIC_RELAXED);
+    }
+    return v;
+}
+extern "C" int hite_gather_config_ctx(hite_ctx *ctx, int32_t mode) {
+    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
+    ctx->gather_chunks = mode;
+    return HITE_OK;
+}
+extern "C" int hite_gather_mode_ctx(hite_ctx *ctx) { return ctx ? gather_chunks_mode(ctx) : HITE_EINVAL; }
+// item = (row, run of up to GR_ITEM_CHUNKS chunks of its slot); item_start = the scan of the rows' item counts
+__global__ void gather_items_kernel(int64_t nrows_total, const int64_t *__restrict__ item_start, uint2 *__restrict__ items) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nrows_total) return;
+    const int64_t i0 = item_start[g];
+    const int k = (int)(item_start[g + 1] - i0);
+    for (int j = 0; j < k; j++) items[i0 + j] = make_uint2((unsigned)g, (unsigned)j);
+}
+// A chunk that touches a pad, the seam or the row's end is not put together where the stream runs: its number goes on the wavefront's
+// list in LDS (entry = item of the wavefront << 8 | chunk of the item), and the list is worked off at the end, a chunk per lane
+__device__ __forceinline__ void gather_defer(uint16_t *__restrict__ list, int &n, bool other, unsigned entry, int lane) {
+    const unsigned long long mk = __ballot(other);
+    if (other) list[n + (int)__popcll(mk & ((1ull << lane) - 1ull))] = (uint16_t)entry;
+    n += (int)__popcll(mk);
+}
+__device__ __forceinline__ uint32_t gather_lane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+static_assert(sizeof(GatherRow) == 32 && offsetof(GatherRow, len) == 16 && offsetof(GatherRow, a) == 24 && offsetof(GatherRow, flags) == 28,
+              "row_gather_chunks_kernel reads the descriptor as two 16-byte words");
+#define GR_WAVE_ITEMS 4        // consecutive items a wavefront takes: their look-ups (item, descriptor, slot) run side by side
+// A wavefront takes GR_WAVE_ITEMS consecutive items.  Those of at most 64 chunks (every row of the first500 + last500 form; the last
+// item of a longer row) go TOGETHER, one chunk per lane and item: every lane asks for the genome words of all of them before it
+// decodes the first.  An item of more chunks follows on its own, up to four chunks per lane, again all asked for before the first is
+// used.  One load site each, the address chosen per strand beforehand (gather_chunk_src) and, where a lane has no chunk, that of the
+// item's first chunk, which exists.  Every chunk leaves as ONE 16-byte store inside the row's slot; the bytes between the row's
+// length and the end of its slot are written as zeros.
+__global__ void __launch_bounds__(256) row_gather_chunks_kernel(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ nmask,
+                                                                int64_t n_items, const uint2 *__restrict__ items,
+                                                                const GatherRow *__restrict__ desc, const int64_t *__restrict__ win_off,
+                                                                uint8_t *__restrict__ win) {
+    __shared__ uint16_t s_list[4][GR_WAVE_ITEMS * GR_ITEM_CHUNKS];
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t it0 = ((int64_t)blockIdx.x * 4 + wv) * GR_WAVE_ITEMS;
+    if (it0 >= n_items) return;
+    const int lane = threadIdx.x & 63;
+    uint16_t *list = s_list[wv];
+    GatherRow R[GR_WAVE_ITEMS];
+    uint8_t *dst[GR_WAVE_ITEMS];
+    int q0[GR_WAVE_ITEMS], cnt[GR_WAVE_ITEMS];                            // first chunk of the item in its row, its chunks (0: no such item)
+    // two rounds of look-ups for all the items: lane l reads the record of item l & 3, then its descriptor and slot, and the wavefront
+    // takes them from lanes 0 .. 3 (as scalar loads the compiler spread them over six rounds)
+    const int64_t itl = it0 + (lane & (GR_WAVE_ITEMS - 1));
+    const uint2 recv = items[itl < n_items ? itl : n_items - 1];
+    const uint4 *d4 = reinterpret_cast<const uint4 *>(desc + recv.x);
+    const uint4 lo = d4[0], hi = d4[1];
+    const int64_t offv = win_off[recv.x];
+#pragma unroll
+    for (int j = 0; j < GR_WAVE_ITEMS; j++) {
+        R[j].g_lo = (int64_t)(gather_lane(lo.x, j) | ((uint64_t)gather_lane(lo.y, j) << 32));
+        R[j].c_g_lo = (int64_t)(gather_lane(lo.z, j) | ((uint64_t)gather_lane(lo.w, j) << 32));
+        R[j].len = (int32_t)gather_lane(hi.x, j);
+        R[j].c_len = (int32_t)gather_lane(hi.y, j);
+        const uint32_t ab = gather_lane(hi.z, j);
+        R[j].a = (uint16_t)(ab & 0xffffu); R[j].b = (uint16_t)(ab >> 16);
+        R[j].flags = gather_lane(hi.w, j);
+        dst[j] = win + (int64_t)(gather_lane((uint32_t)offv, j) | ((uint64_t)gather_lane((uint32_t)((uint64_t)offv >> 32), j) << 32));
+        q0[j] = (int)gather_lane(recv.y, j) * GR_ITEM_CHUNKS;
+        const int left = ((gather_row_len(R[j]) + 15) >> 4) - q0[j];
+        cnt[j] = it0 + j >= n_items || left < 0 ? 0 : (left > GR_ITEM_CHUNKS ? GR_ITEM_CHUNKS : left);
+    }
+    int nlist = 0;
+    {   // the items of at most 64 chunks
+        uint32_t b0[GR_WAVE_ITEMS], b1[GR_WAVE_ITEMS], m0[GR_WAVE_ITEMS], m1[GR_WAVE_ITEMS];
+        int64_t gs[GR_WAVE_ITEMS];
+#pragma unroll
+        for (int j = 0; j < GR_WAVE_ITEMS; j++) gs[j] = gather_chunk_src(R[j], q0[j] + (cnt[j] <= 64 && lane < cnt[j] ? lane : 0));
+#pragma unroll
+        for (int j = 0; j < GR_WAVE_ITEMS; j++) {
+            const int64_t w = gs[j] >> 4, mw = gs[j] >> 5;
+            b0[j] = bases[w]; b1[j] = bases[w + 1];
+            m0[j] = nmask[mw]; m1[j] = nmask[mw + 1];
+        }
+#pragma unroll
+        for (int j = 0; j < GR_WAVE_ITEMS; j++) {
+            const int q = q0[j] + lane;
+            const bool live = cnt[j] <= 64 && lane < cnt[j], plain = live && gather_chunk_plain(R[j], q);
+            if (plain) {
+                uint32_t codes, nb;
+                gather_words16(b0[j], b1[j], m0[j], m1[j], gs[j], codes, nb);
+                *reinterpret_cast<uint4 *>(dst[j] + 16 * (int64_t)q) = gather_chunk_decode(R[j], codes, nb);
+            }
+            gather_defer(list, nlist, live && !plain, (unsigned)(j << 8 | lane), lane);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < GR_WAVE_ITEMS; j++) {
+        if (cnt[j] <= 64) continue;                                     // (the same for every lane)
+        uint32_t b0[4], b1[4], m0[4], m1[4];
+        int64_t gs[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) gs[k] = gather_chunk_src(R[j], q0[j] + (lane + 64 * k < cnt[j] ? lane + 64 * k : 0));
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t w = gs[k] >> 4, mw = gs[k] >> 5;
+            b0[k] = bases[w]; b1[k] = bases[w + 1];
+            m0[k] = nmask[mw]; m1[k] = nmask[mw + 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = lane + 64 * k, q = q0[j] + c;
+            const bool live = c < cnt[j], plain = live && gather_chunk_plain(R[j], q);
+            if (plain) {
+                uint32_t codes, nb;
+                gather_words16(b0[k], b1[k], m0[k], m1[k], gs[k], codes, nb);
+                *reinterpret_cast<uint4 *>(dst[j] + 16 * (int64_t)q) = gather_chunk_decode(R[j], codes, nb);
+            }
+            gather_defer(list, nlist, live && !plain, (unsigned)(j << 8 | c), lane);
+        }
+    }
+    // the listed chunks, one per lane: each fetches for itself (its window's words, the second fetch behind the seam, the centre's)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 1
+    for (int base = 0; base < nlist; base += 64) {
+        if (base + lane >= nlist) continue;
+        const unsigned e = list[base + lane];
+        const int j = (int)(e >> 8);
+        GatherRow Rv = R[0];
+        uint8_t *d = dst[0];
+        int qv = q0[0];
+#pragma unroll
+        for (int i = 1; i < GR_WAVE_ITEMS; i++)
+            if (j == i) { Rv = R[i]; d = dst[i]; qv = q0[i]; }
+        qv += (int)(e & 255u);
+        *reinterpret_cast<uint4 *>(d + 16 * (int64_t)qv) = gather_chunk(bases, nmask, Rv, qv);
     }
 }
 
@@ -463,11 +631,26 @@ static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_
     ACHK(arena_alloc(ctx, T, (size_t)total_rows, &p)); row_trunc = (uint8_t *)p;
     int32_t *row_cp0 = nullptr;
     if (d_clip) { ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_cp0 = (int32_t *)p; }
+    const bool chunks = gather_chunks_mode(ctx) != 0;
+    GatherRow *desc = nullptr;
+    int32_t *row_items = nullptr;
+    int64_t *item_start = nullptr;
+    if (chunks) {
+        ACHK(arena_alloc(ctx, T, (size_t)total_rows * sizeof(GatherRow), &p)); desc = (GatherRow *)p;
+        ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_items = (int32_t *)p;
+        ACHK(arena_alloc(ctx, T, (size_t)(total_rows + 1) * 8, &p)); item_start = (int64_t *)p;
+    }
     HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
     hipLaunchKernelGGL(row_meta_kernel, dim3(n), dim3(128), 0, st, n, row_first, nrows, sel, d_mode, d_len, row_first32,
-                       row_copy, row_len, row_pad, row_trunc, (int32_t *)(S->d_scal + 2), d_clip, d_minus, row_cp0);
+                       row_copy, row_len, row_pad, row_trunc, (int32_t *)(S->d_scal + 2), d_clip, d_minus, row_cp0,
+                       desc, row_items, (const int64_t *)ctx->d_contig_off, (int32_t)ctx->n_contigs, d_contig, d_s1, d_e1, (int32_t)flank);
     ACHK(arena_alloc(ctx, T, (size_t)(total_rows + 1) * 8, &p)); win_off = (int64_t *)p;
     ACHK(scan_excl<int32_t>(ctx, T, row_pad, total_rows, win_off, st));
+    if (chunks) {
+        // the items of every row, counted on the device; their total rides on the read-back below
+        ACHK(scan_excl<int32_t>(ctx, T, row_items, total_rows, item_start, st));
+        HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 6, item_start + total_rows, 8, hipMemcpyDeviceToDevice, st));
+    }
     ACHK(arena_alloc(ctx, T, (size_t)n * 8, &p)); ops_cnt = (int64_t *)p;
     ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 8, &p)); ops_base = (int64_t *)p;
     hipLaunchKernelGGL(ops_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, row_first, nrows, row_len, ops_cnt,
@@ -475,7 +658,7 @@ static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_
     ACHK(scan_excl<int64_t>(ctx, T, ops_cnt, n, ops_base, st));
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, win_off + total_rows, 8, hipMemcpyDeviceToDevice, st));
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 1, ops_base + n, 8, hipMemcpyDeviceToDevice, st));
-    ACHK(read_scalars(ctx, S, st, 6));
+    ACHK(read_scalars(ctx, S, st, 7));
     const int64_t win_bytes = S->h_pin[0];
     F.win_bytes = win_bytes; F.ops_elems = S->h_pin[1];
     F.max_len = (int)(((int32_t *)(S->h_pin + 2))[0]);
@@ -483,10 +666,25 @@ static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_
     F.steps = S->h_pin[5];        // anti-diagonal steps
 
     ACHK(arena_alloc(ctx, T, (size_t)win_bytes + 64, &p)); win = (uint8_t *)p;
+    // (both forms under the one name of the stage table: the item list is part of what the chunk form costs)
+    const int64_t n_items = chunks ? S->h_pin[6] : 0;
+    // (row_items says how many items a row is: ceil(row_pad / 4096), none for a row of no bytes; a workgroup takes 4 * GR_WAVE_ITEMS items)
+    const int64_t item_groups = (n_items + 4 * GR_WAVE_ITEMS - 1) / (4 * GR_WAVE_ITEMS);
+    if (chunks && (n_items < 0 || n_items > win_bytes / (16 * GR_ITEM_CHUNKS) + total_rows || item_groups > 0x7fffffff)) return HITE_EINVAL;
     tk = hite_prof_begin(ctx, "row_gather_kernel", st);
-    hipLaunchKernelGGL(row_gather_kernel, dim3((unsigned)((total_rows + 3) / 4)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
-                       ctx->d_contig_off, ctx->n_contigs, total_rows, row_copy, row_trunc, d_contig, d_s1, d_e1, d_minus,
-                       flank, win_off, win, d_clip, row_cp0);
+    if (chunks && n_items == 0) {
+        // (no row has a byte: nothing to gather)
+    } else if (chunks) {
+        uint2 *items;
+        ACHK(arena_alloc(ctx, T, (size_t)n_items * sizeof(uint2), &p)); items = (uint2 *)p;
+        hipLaunchKernelGGL(gather_items_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, item_start, items);
+        hipLaunchKernelGGL(row_gather_chunks_kernel, dim3((unsigned)item_groups), dim3(256), 0, st, (const uint32_t *)ctx->d_bases,
+                           (const uint32_t *)ctx->d_nmask, n_items, items, desc, win_off, win);
+    } else {
+        hipLaunchKernelGGL(row_gather_kernel, dim3((unsigned)((total_rows + 3) / 4)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
+                           ctx->d_contig_off, ctx->n_contigs, total_rows, row_copy, row_trunc, d_contig, d_s1, d_e1, d_minus,
+                           flank, win_off, win, d_clip, row_cp0);
+    }
     hite_prof_end(ctx, tk, st);
     HITE_CHECK(ctx, hipGetLastError());
     F.row_first32 = row_first32; F.row_copy = row_copy; F.row_len = row_len; F.row_pad = row_pad; F.row_cp0 = row_cp0;

@@ -941,6 +941,13 @@ int hite_star_msa_fill_sparse_dev(hite_ctx *ctx, int32_t n, const uint8_t *d_win
  * (and of a tile's output columns) that fit the LDS slot, out[2] = rows a workgroup takes per trip, out[3] = row slices of a
  * candidate (a workgroup takes the rows out[2] * z + wave, stepping by out[2] * out[3]). */
 int hite_fill_config_ctx(hite_ctx *ctx, int32_t mode);
+/* The window gather of the fine stage has two forms that write the same window bytes: in chunks of the destination -- a row
+ * descriptor per row, items of up to 256 chunks of 16 bytes per wavefront, the bytes between a row's length and the end of its slot
+ * zero (the default) -- and a wavefront per row, which leaves those bytes as they were.  mode 1 / 0 selects the chunk / per-row form
+ * for this context, -1 follows the process default again (HITE_GATHER_CHUNKS=0 in the environment: the per-row form). */
+int hite_gather_config_ctx(hite_ctx *ctx, int32_t mode);
+/* the form the next call of this context runs: 1 chunks / 0 per row (its own setting, else the process default) */
+int hite_gather_mode_ctx(hite_ctx *ctx);
 /* The star alignment re-aligns the pairs whose traceback left its slice (the fall-back: a few dozen lone wavefronts).  mode 1: that runs
  * beside the pad fix and the layout of the candidates it does not touch, which are then done once more for the others; mode 0: one after
  * the other; -1 follows the process default again (on, unless HITE_FALLBACK_OVERLAP=0 in the environment).  The same bytes either way. */
