@@ -839,6 +839,88 @@ class Context:
         self._check(self.lib.hite_copy_clips_dev(self._copy_state, C.byref(d), C.byref(n)), "hite_copy_clips_dev")
         return d.value or 0
 
+    # ---- full-length copy support of the intact LTR elements (FiLTR's step 4; include/hite_gpu.h) -----------------------------
+    @staticmethod
+    def _std_arrays(std):
+        std = list(std)
+        return (_arr([t[0] for t in std], np.int32), _arr([t[1] for t in std], np.int64), _arr([t[2] for t in std], np.int64))
+
+    @staticmethod
+    def _support_rows(n, of, oc, os_, oe):
+        of = of.tolist()
+        rows = list(zip(oc[:of[n]].tolist(), os_[:of[n]].tolist(), oe[:of[n]].tolist()))
+        return [rows[of[k]:of[k + 1]] for k in range(n)]
+
+    def ltr_copy_support_records(self, el_len, records, std, contig_len, full_length_coverage=0.985, overlap_threshold=0.95,
+                                 segment_len=100000, cap=None, stats=None):
+        """hite_ltr_copy_support_records: el_len[k] bases of element k, records[k] its copy records (contig, start1, end1, clip) in
+        input order (clip = left | right << 16, as find_copies(clips=True) gives it); std: (contig, start, end) per candidate line in
+        the order of ltr_lines (start = lLTR_start - 1, end = rLTR_end); contig_len per contig -> per element the list of
+        (contig, start1, end1) kept.  cap: room for the output (None: every record); stats: a dict that receives the four counts.
+        A HiteError of code HITE_ECAP carries .n_out, the room the call needs."""
+        n = len(el_len)
+        cf = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in records], out=cf[1:])
+        if len(records) != n or cf[n] >= 2 ** 31:
+            raise ValueError("ltr_copy_support_records: one list of records per element, fewer than 2^31 records in all")
+        flat = [t for r in records for t in r]
+        ct, s1, e1 = _arr([t[0] for t in flat], np.int32), _arr([t[1] for t in flat], np.int64), _arr([t[2] for t in flat], np.int64)
+        cl = _arr([t[3] for t in flat], np.uint32)
+        sc, ss, se = self._std_arrays(std)
+        clen = _arr(contig_len, np.int64)
+        cap = len(flat) if cap is None else int(cap)
+        of = np.zeros(n + 1, dtype=np.int32)
+        oc, os_, oe = np.zeros(cap + 1, dtype=np.int32), np.zeros(cap + 1, dtype=np.int64), np.zeros(cap + 1, dtype=np.int64)
+        nout = C.c_int64(0)
+        st = np.zeros(4, dtype=np.int64)
+        rc = self.lib.hite_ltr_copy_support_records(self.h, C.c_int64(n), _p(_arr(el_len, np.int64)), _p(cf.astype(np.int32)), _p(ct), _p(s1), _p(e1),
+                                                    _p(cl), C.c_int64(len(sc)), _p(sc), _p(ss), _p(se), C.c_int32(len(clen)), _p(clen),
+                                                    C.c_double(full_length_coverage), C.c_double(overlap_threshold), C.c_int64(segment_len),
+                                                    C.c_int64(cap), _p(of), _p(oc), _p(os_), _p(oe), C.byref(nout), _p(st))
+        return self._support_result(rc, "hite_ltr_copy_support_records", n, of, oc, os_, oe, nout, st, stats)
+
+    def _support_result(self, rc, what, n, of, oc, os_, oe, nout, st, stats):
+        if stats is not None:
+            stats.update(zip(("records", "covered", "matched", "kept"), (int(x) for x in st)))
+        if rc != 0:
+            try:
+                self._check(rc, what)
+            except HiteError as e:
+                e.code, e.n_out = rc, nout.value
+                raise
+        return self._support_rows(n, of, oc, os_, oe)
+
+    def ltr_copy_support(self, elements, std, full_length_coverage=0.985, overlap_threshold=0.95, segment_len=100000, stats=None):
+        """hite_ltr_copy_support: the elements (str / bytes) against the packed genome (genome_pack() first) -- the copy finder in
+        aligned-interval mode, then the rules of get_copies_minimap2 and get_intact_ltr_copies on its table where it lies on the
+        device -> per element the list of (contig, start1, end1) kept; std, stats: see ltr_copy_support_records.  More than
+        FIND_COPIES_BATCH elements go in batches that share the index; the order of equally long copies of an element on different
+        contigs follows the contigs' first appearance inside the batch."""
+        if getattr(self, "_copy_state", None) is None:
+            self._copy_state = C.c_void_p(None)
+        eb = [e.encode() if isinstance(e, str) else bytes(e) for e in elements]
+        sc, ss, se = self._std_arrays(std)
+        out, tot = [], np.zeros(4, dtype=np.int64)
+        for k in range(0, len(eb), self.FIND_COPIES_BATCH):
+            part = eb[k:k + self.FIND_COPIES_BATCH]
+            n = len(part)
+            off = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum([len(e) for e in part], out=off[1:])
+            buf = np.frombuffer(b"".join(part) + b"\0" * 16, dtype=np.uint8)
+            cap = 300 * n
+            of = np.zeros(n + 1, dtype=np.int32)
+            oc, os_, oe = np.zeros(cap + 1, dtype=np.int32), np.zeros(cap + 1, dtype=np.int64), np.zeros(cap + 1, dtype=np.int64)
+            nout = C.c_int64(0)
+            st = np.zeros(4, dtype=np.int64)
+            rc = self.lib.hite_ltr_copy_support(self.h, C.byref(self._copy_state), C.c_int32(n), _p(buf), _p(off), C.c_int64(len(sc)), _p(sc), _p(ss),
+                                                _p(se), C.c_double(full_length_coverage), C.c_double(overlap_threshold), C.c_int64(segment_len),
+                                                C.c_int64(cap), _p(of), _p(oc), _p(os_), _p(oe), C.byref(nout), _p(st))
+            tot += st
+            out += self._support_result(rc, "hite_ltr_copy_support", n, of, oc, os_, oe, nout, tot, stats)
+        if stats is not None and not eb:
+            stats.update(dict.fromkeys(("records", "covered", "matched", "kept"), 0))
+        return out
+
     def query_copies(self, qid, sid, qs, qe, ss, se, ident, qlen, slen=None, ns=None, qcov=0.95, scov=0.0, qthr=200, sthr=200, max_copy=100):
         """get_query_copies on an HSP table in file order -> per query list of (subject id, start, end, chain length, '+'/'-')"""
         n = len(qid)

@@ -425,3 +425,92 @@ def ltr_element_decisions(truth, recomb_lines, final_lines, dirty_dicts):
         if not ok:
             wrong.append(t["id"])
     return table, wrong
+
+
+# families of (copies, length of the target-site duplication or None for none) of make_ltr_library_genome's default plan
+LTR_LIBRARY_PLAN = ((1, 5), (1, None), (2, 4), (2, 6), (5, 5), (1, 6))
+
+
+def make_ltr_library_genome(plan=LTR_LIBRARY_PLAN, seed=1, div=0.004, edge=True):
+    """A genome of FAMILIES of whole LTR elements with target-site duplications, for FiLTR's steps 4 to 8 (util.ltr_library; tests and
+    tools/gen_ltr_library_fixture.py): plan = [(copies, tsd_len or None), ...].  A family is two terminals (300 .. 500 bases, TG .. CA,
+    the second 1 .. 4 % apart) around an internal sequence of 1 500 .. 2 500 bases; every copy is the family's element with
+    substitutions at rate div, planted between two copies of a random k-mer of tsd_len bases (None: eight C before it and bases of
+    G / T after it, which share no k-mer), every copy in a slot of 6 000 bases of random sequence, eight slots to a chromosome.  With
+    edge, two more single elements lie at the very start of the first and at the very end of the last chromosome (the windows of the
+    structure search are cut there).  The last copy of a family of five or more has NO candidate line.
+    -> dict(contigs {name: sequence}, scn (the candidate table, by chromosome and start; the identity column takes 100.00, 98.50,
+    95.00, ... in turn), truth [dict(family, copy, chr, line or None, name, tsd)])"""
+    rng = np.random.default_rng(seed)
+    slot, per_chr = 6000, 8
+    units = []
+    for f, (copies, tsd) in enumerate(plan):
+        term = _rand_codes(rng, int(rng.integers(300, 501)))
+        term[:3] = (3, 2, 3)          # TGT .. ACA
+        term[-3:] = (0, 1, 0)
+        right = _diverged_terminal(rng, term, float(rng.uniform(0.01, 0.04)), 0)
+        internal = _rand_codes(rng, int(rng.integers(1500, 2501)))
+        element = np.concatenate([term, internal, right])
+        for c in range(copies):
+            body = element.copy()
+            m = rng.random(len(body)) < div
+            m[:_LTR_CLEAN_END] = False
+            m[len(body) - _LTR_CLEAN_END:] = False
+            body[m] = (body[m] + rng.integers(1, 4, size=int(m.sum())).astype(np.uint8)) & 3
+            units.append(dict(family=f, copy=c, body=body, term=len(term), rterm=len(right), tsd=tsd, line=not (copies >= 5 and c == copies - 1)))
+    order = [int(i) for i in rng.permutation(len(units))]
+    n_chr = (len(units) + per_chr - 1) // per_chr
+    contigs, lines, truth = {}, [], []
+    idents = ("100.00", "98.50", "95.00", "99.20", "90.00")
+    for ci in range(n_chr):
+        chr_name = "chr%d" % (ci + 1)
+        chunk = [units[i] for i in order[ci * per_chr:(ci + 1) * per_chr]]
+        extra = []
+        if edge and ci == 0:
+            extra.append("start")
+        if edge and ci == n_chr - 1:
+            extra.append("end")
+        seq = _rand_codes(rng, slot * len(chunk) + 1000)
+        placed = []
+        for e, u in enumerate(chunk):
+            pos = 700 + e * slot + int(rng.integers(0, 200))
+            body = u["body"]
+            if u["tsd"] is None:
+                seq[pos - 8:pos] = 1
+                seq[pos + len(body):pos + len(body) + 8] = rng.integers(2, 4, size=8).astype(np.uint8)
+            else:
+                k = _rand_codes(rng, u["tsd"])
+                seq[pos - u["tsd"]:pos] = k
+                seq[pos + len(body):pos + len(body) + u["tsd"]] = k
+            seq[pos:pos + len(body)] = body
+            placed.append((u, pos))
+        parts, shift = [seq], 0
+        if "start" in extra:
+            unit, iv = _ltr_element(rng, "clean", 300, 1500)
+            head = unit[iv["left"][0]:iv["right"][1]]
+            parts.insert(0, head)
+            shift = len(head)
+            placed.append((dict(family=-1, copy=0, body=head, term=iv["left"][1] - iv["left"][0], rterm=iv["right"][1] - iv["right"][0], tsd=None,
+                                line=True), -shift))
+        if "end" in extra:
+            unit, iv = _ltr_element(rng, "clean", 300, 1500)
+            tail = unit[iv["left"][0]:iv["right"][1]]
+            placed.append((dict(family=-2, copy=0, body=tail, term=iv["left"][1] - iv["left"][0], rterm=iv["right"][1] - iv["right"][0], tsd=None,
+                                line=True), len(seq)))
+            parts.append(tail)
+        for u, pos in placed:
+            a = pos + shift
+            n = len(u["body"])
+            line = _scn_line((a, a + u["term"]), (a + n - u["rterm"], a + n), len(truth), chr_name)
+            f = line.split(" ")
+            f[9] = idents[len(truth) % len(idents)]
+            line = " ".join(f)
+            truth.append(dict(family=u["family"], copy=u["copy"], chr=chr_name, line=line if u["line"] else None, name="%s-%s-%s" % (chr_name, f[3], f[4]),
+                              tsd=u["tsd"]))
+            if u["line"]:
+                lines.append((ci, a, line))
+        contigs[chr_name] = ASCII[np.concatenate(parts)].tobytes().decode()
+    lines.sort(key=lambda t: (t[0], t[1]))
+    scn = "# planted LTR families: start end len lLTR_start lLTR_end lLTR_len rLTR_start rLTR_end rLTR_len similarity seq_id chr\n" + \
+        "".join(t[2] + "\n" for t in lines)
+    return dict(contigs=contigs, scn=scn, truth=truth)

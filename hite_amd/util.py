@@ -2659,6 +2659,382 @@ def ltr_detect(reference, out_dir, flanking_len=100, max_copy_num=100, ctx=None,
     return confident_scn, table
 
 
+# ---- FiLTR's steps 4 to 8: from the is_LTR table to the LTR library (bin/FiLTR-main/src/LTR_filter.py:702-813) ---------------------
+# Step 4 asks how many full-length copies every confident intact element has.  Where the reference runs minimap2 and filters its SAM
+# records (filter_ltr_by_copy_num_minimap, get_copies_minimap2) and then get_intact_ltr_copies, filter_ltr_by_copy_num makes ONE call
+# of Context.ltr_copy_support ("full-length copy support" in include/hite_gpu.h: the copy finder and the reference's rules on its
+# records, on the device; parity with minimap2 itself is unpinned).  support= replaces it (the signature of Context.ltr_copy_support;
+# the CPU tests pass tests/ltrcopy_twin.support).  Everything around the search is the reference's, restated.
+def _scn_std(ltr_lines, contig_id):
+    """(contig, lLTR_start - 1, rLTR_end) of every candidate line, in the order of ltr_lines"""
+    std = []
+    for candidate_index in ltr_lines:
+        parts = ltr_lines[candidate_index].split(" ")
+        std.append((contig_id[parts[11]], int(parts[3]) - 1, int(parts[7])))
+    return std
+
+
+def get_intact_ltr_copies(ltr_copies, ltr_lines, full_length_threshold, reference):
+    """bin/FiLTR-main/src/Util.py:11022-11147 on its own dicts: ltr_copies {name: [(chr_name, start1, end1, ...)]} -> {name:
+    [(chr_name, start1, end1)]}: the copies that coincide with a candidate line (same segment of 100 000 bases, overlap >=
+    full_length_threshold of both), the shorter of two that overlap by 95 % on one chromosome removed, ascending by length"""
+    ref_names, ref_contigs = reference if isinstance(reference, tuple) else read_fasta(reference)
+    segment_len = 100000
+    n_segments = {n: len(ref_contigs[n]) // segment_len + (len(ref_contigs[n]) % segment_len != 0) for n in ref_names}
+
+    def overlaps(prev, start, end):
+        overlap_len = max(min(prev[1], end) - max(prev[0], start), 0)
+        return overlap_len / abs(prev[1] - prev[0]) >= full_length_threshold and overlap_len / abs(end - start) >= full_length_threshold
+
+    def segment(start, end):
+        a, b = start // segment_len, end // segment_len
+        return a if a == b or not abs(b * segment_len - start) < abs(end - b * segment_len) else b
+
+    chr_segments = {}
+    for candidate_index in ltr_lines:
+        parts = ltr_lines[candidate_index].split(" ")
+        chr_name, start, end = parts[11], int(parts[3]) - 1, int(parts[7])
+        seg = segment(start, end)
+        if seg >= n_segments[chr_name]:
+            raise KeyError(seg)
+        frags = chr_segments.setdefault((chr_name, seg), [])
+        if not any(overlaps(p, start, end) for p in frags):
+            frags.append((start, end))
+    test_fragments = {}
+    for ltr_name in ltr_copies:
+        for copy in ltr_copies[ltr_name]:
+            test_fragments.setdefault(copy[0], []).append((copy[1], copy[2], ltr_name))
+    intact_ltr_copies = {}
+    for chr_name, fragments in test_fragments.items():
+        for start, end, ltr_name in fragments:
+            seg = segment(start, end)
+            if seg >= n_segments[chr_name]:
+                raise KeyError(seg)
+            if any(overlaps(p, start, end) for p in chr_segments.get((chr_name, seg), ())):
+                intact_ltr_copies.setdefault(ltr_name, []).append((chr_name, start, end))
+    for ltr_name, copies in intact_ltr_copies.items():
+        copies.sort(key=lambda x: (x[2] - x[1]))
+        kept = []
+        for i, (chr_i, start_i, end_i) in enumerate(copies):
+            if not any(chr_j == chr_i and min(end_i, end_j) - max(start_i, start_j) + 1 >= 0.95 * (end_i - start_i + 1)
+                       for chr_j, start_j, end_j in copies[i + 1:]):
+                kept.append((chr_i, start_i, end_i))
+        intact_ltr_copies[ltr_name] = kept
+    return intact_ltr_copies
+
+
+def filter_ltr_by_copy_num(output_path, leftLtr2Candidates, ltr_lines, reference, tmp_output_dir, split_ref_dir, threads, full_length_threshold,
+                           debug, ctx=None, support=None):
+    """bin/FiLTR-main/src/Util.py:6119, same arguments: the intact sequences of the candidates whose left terminal output_path marks 1,
+    their full-length copies at coverage 0.985 that coincide with a candidate line (full_length_threshold) -> ({name: [(chr_name,
+    start1, end1)]}, {name: internal sequence}).  One call of Context.ltr_copy_support (support=) for all elements, in batches of
+    Context.FIND_COPIES_BATCH; the genome must be the packed one (set_reference).  Like the reference's, the first dict holds the
+    elements with at least one such copy; its keys are in the order of the elements (the reference's follow the order in which it
+    walks the copies chromosome by chromosome: the same entries, another order of the lines written from them)."""
+    true_ltrs = set()
+    with open(output_path, "r") as f_r:
+        for line in f_r:
+            parts = line.replace("\n", "").split("\t")
+            if int(parts[1]):
+                true_ltrs.add(parts[0])
+    ref_names, ref_contigs = read_fasta(reference)
+    contig_id = {n: k for k, n in enumerate(ref_names)}
+    internal_ltrs, intact_ltrs = {}, {}
+    for name in leftLtr2Candidates:
+        if name not in true_ltrs:
+            continue
+        parts = ltr_lines[leftLtr2Candidates[name]].split(" ")
+        ref_seq = ref_contigs[parts[11]]
+        intact_ltr_seq = ref_seq[int(parts[3]) - 1: int(parts[7])]
+        internal_ltrs[name] = ref_seq[int(parts[4]): int(parts[6]) - 1]
+        if len(intact_ltr_seq) > 0:
+            intact_ltrs[name] = intact_ltr_seq
+    names = list(intact_ltrs)
+    if support is None:
+        support = (ctx or get_ctx()).ltr_copy_support
+    kept = support([intact_ltrs[n] for n in names], _scn_std(ltr_lines, contig_id), 0.985, full_length_threshold) if names else []
+    intact_ltr_copies = {n: [(ref_names[c], s, e) for c, s, e in rows] for n, rows in zip(names, kept) if rows}
+    return intact_ltr_copies, internal_ltrs
+
+
+def search_ltr_structure(ltr_name, left_seq, right_seq):
+    """bin/FiLTR-main/src/Util.py:9803: a target-site duplication of 6, 5 or 4 bases -- the first k-mer of right_seq without N, longest k
+    first, that left_seq holds -> (ltr_name, has_tsd, tsd_seq)"""
+    tsd_lens = [6, 5, 4]
+    exist_tsd = set()
+    for k_num in tsd_lens:
+        for i in range(len(left_seq) - k_num + 1):
+            left_kmer = left_seq[i: i + k_num]
+            if "N" not in left_kmer:
+                exist_tsd.add(left_kmer)
+    for k_num in tsd_lens:
+        for i in range(len(right_seq) - k_num + 1):
+            right_kmer = right_seq[i: i + k_num]
+            if "N" not in right_kmer and right_kmer in exist_tsd:
+                return ltr_name, True, right_kmer
+    return ltr_name, False, ""
+
+
+def is_ltr_has_structure(ltr_name, line, ref_seq):
+    """bin/FiLTR-main/src/Util.py:9956: search_ltr_structure on the 8 bases outside and the 3 bases inside both ends of the element of
+    a candidate line, clamped at the ends of the chromosome"""
+    left_size, internal_size = 8, 3
+    parts = line.split(" ")
+    lLTR_start, rLTR_end = int(parts[3]), int(parts[7])
+    left_seq = ref_seq[max(lLTR_start - 1 - left_size, 0): min(lLTR_start + internal_size - 1, len(ref_seq))]
+    right_seq = ref_seq[max(rLTR_end - internal_size, 0): min(rLTR_end + left_size, len(ref_seq))]
+    return search_ltr_structure(ltr_name, left_seq, right_seq)
+
+
+def estimate_insert_time(identity, miu):
+    """bin/FiLTR-main/src/Util.py:4174: the Jukes-Cantor distance of the two terminals over twice the mutation rate"""
+    d = 1 - identity
+    K = -3 / 4 * math.log(1 - d * 4 / 3)
+    T = K / (2 * miu)
+    return T
+
+
+def filtr_protein_libs():
+    """(LTRPeps.lib, OtherPeps.lib) of FiLTR's databases directory ($HITE_FILTR_DIR/databases): FiLTR's data, not part of this build"""
+    lib_dir = os.path.join(os.environ.get("HITE_FILTR_DIR", ""), "databases")
+    return os.path.join(lib_dir, "LTRPeps.lib"), os.path.join(lib_dir, "OtherPeps.lib")
+
+
+def _intact_protein_names(cons, protein_db, output_table, threads, temp_dir, log, debug, search, ctx):
+    """one half of the protein test of filter_single_copy_ltr (:6022-6042): the sequences of cons with a hit that spans >= 95 % of a
+    protein of protein_db; a missing library is said in the log and gives the empty table blastx gives when it finds nothing"""
+    names = {}
+    if not os.path.exists(protein_db):
+        _scn_log(log, "info", "protein library " + protein_db + " not found (set HITE_FILTR_DIR): the single-copy rule runs with an empty domain table")
+        return names
+    get_domain_info(cons, protein_db, output_table, threads, temp_dir, search=search, ctx=ctx)
+    _protein_names, protein_contigs = read_fasta(protein_db)
+    with open(output_table, "r") as f_r:
+        for i, line in enumerate(f_r):
+            if i < 2:
+                continue
+            parts = line.split("\t")
+            if float(abs(int(parts[5]) - int(parts[4]))) / len(protein_contigs[parts[1]]) >= 0.95:
+                names[parts[0]] = True
+    if not debug:
+        shutil.rmtree(temp_dir, ignore_errors=True)
+        if os.path.exists(output_table):
+            os.remove(output_table)
+    return names
+
+
+def filter_single_copy_ltr(output_path, filtered_output_path, single_copy_internals_file, ltr_copies, internal_ltrs, ltr_protein_db,
+                           other_protein_db, tmp_output_dir, threads, reference, leftLtr2Candidates, ltr_lines, log, debug, search=None, ctx=None):
+    """bin/FiLTR-main/src/Util.py:6005, same arguments: an element of ltr_copies with two or more copies is an LTR; one with at most
+    one copy only when its internal sequence holds an intact LTR protein and no intact other protein and the element has a
+    target-site duplication.  output_path receives name \\t 0 | 1 per element, filtered_output_path the reason of every 0.  search:
+    the mode of get_domain_info."""
+    single_copy_internals = {name: internal_ltrs[name] for name in ltr_copies if len(ltr_copies[name]) <= 1}
+    store_fasta(single_copy_internals, single_copy_internals_file)
+    has_protein = _intact_protein_names(single_copy_internals_file, ltr_protein_db, single_copy_internals_file + ".ltr_domain", threads,
+                                        tmp_output_dir + "/ltr_domain", log, debug, search, ctx)
+    has_other = _intact_protein_names(single_copy_internals_file, other_protein_db, single_copy_internals_file + ".other_domain", threads,
+                                      tmp_output_dir + "/other_domain", log, debug, search, ctx)
+    has_structure = {}
+    _ref_names, ref_contigs = reference if isinstance(reference, tuple) else read_fasta(reference)
+    for ltr_name in single_copy_internals:
+        line = ltr_lines[leftLtr2Candidates[ltr_name]]
+        has_structure[ltr_name] = is_ltr_has_structure(ltr_name, line, ref_contigs[line.split(" ")[11]])[1]
+    no_structure = sum(1 for v in has_structure.values() if not v)
+    _scn_log(log, "info", "Filter the number of no structure single copy LTR: " + str(no_structure) + ", remaining single copy LTR num: " +
+             str(len(single_copy_internals) - no_structure))
+    remain_intact_count = filtered_intact_count = 0
+    with open(output_path, "w") as f_save, open(filtered_output_path, "w") as f_filtered:
+        for name in ltr_copies:
+            if len(ltr_copies[name]) >= 2:
+                cur_is_ltr = 1
+            elif has_other.get(name):
+                cur_is_ltr = 0
+                f_filtered.write(name + "\t" + "has_intact_other_protein" + "\n")
+            elif has_protein.get(name) and has_structure.get(name):
+                cur_is_ltr = 1
+            else:
+                cur_is_ltr = 0
+                filter_reason = [why for why, ok in (("no_intact_protein", has_protein.get(name)), ("no_structure", has_structure.get(name))) if not ok]
+                f_filtered.write(name + "\t" + ("|".join(filter_reason) if filter_reason else "other") + "\n")
+            remain_intact_count += cur_is_ltr
+            filtered_intact_count += 1 - cur_is_ltr
+            f_save.write(name + "\t" + str(cur_is_ltr) + "\n")
+    _scn_log(log, "info", "Filter the number of non-intact LTR: " + str(filtered_intact_count) + ", remaining LTR num: " + str(remain_intact_count))
+    if not debug and os.path.exists(single_copy_internals_file):
+        os.remove(single_copy_internals_file)
+
+
+def get_LTR_seq_from_scn(genome, scn_path, ltr_terminal, ltr_internal, ltr_intact, dirty_dicts, ltr_intact_list, miu, coverage_threshold=0.95):
+    """bin/FiLTR-main/src/Util.py:4071, same arguments: the lines of scn_path without those that the line before covers (runs of
+    neighbours that overlap by coverage_threshold of both), their terminals (<chr>:<start>..<end>-lLTR#LTR, -rLTR#LTR), internal
+    sequences (-int#LTR; not of a dirty element) and whole elements as FASTA -- an element with an empty part or a run of ten N is
+    left out --, and the list in the layout of LTR_retriever's pass list: motif, TSD, internal interval, identity, insertion time"""
+    _ref_names, ref_contigs = read_fasta(genome)
+    with open(scn_path, "r") as f_r:
+        ltr_lines = [line.replace("\n", "") for line in f_r if not line.startswith("#")]
+
+    def frag(line):
+        parts = line.split(" ")
+        return parts[11], int(parts[3]) - 1, int(parts[7])
+
+    deredundant_lines, redundant_index = [], set()
+    for i in range(len(ltr_lines) - 1):          # (like the reference, the last line is never taken)
+        if i in redundant_index:
+            continue
+        chr_name, chr_start, chr_end = frag(ltr_lines[i])
+        for j in range(i + 1, len(ltr_lines)):
+            next_chr_name, next_start, next_end = frag(ltr_lines[j])
+            overlap_len = max(min(next_end, chr_end) - max(next_start, chr_start), 0)
+            if (next_chr_name == chr_name and overlap_len / abs(next_end - next_start) >= coverage_threshold
+                    and overlap_len / abs(chr_end - chr_start) >= coverage_threshold):
+                redundant_index.add(j)
+            else:
+                break
+        deredundant_lines.append(ltr_lines[i])
+    LTR_terminals, LTR_ints, LTR_intacts = {}, {}, {}
+    for line in deredundant_lines:
+        parts = line.split(" ")
+        LTR_start, LTR_end, chr_name = int(parts[0]), int(parts[1]), parts[11]
+        lLTR_start, lLTR_end, rLTR_start, rLTR_end = int(parts[3]), int(parts[4]), int(parts[6]), int(parts[7])
+        ref_seq = ref_contigs[chr_name]
+        lLTR_seq, rLTR_seq = ref_seq[lLTR_start - 1: lLTR_end], ref_seq[rLTR_start - 1: rLTR_end]
+        LTR_int_seq, intact_seq = ref_seq[lLTR_end: rLTR_start - 1], ref_seq[lLTR_start - 1: rLTR_end]
+        if (len(lLTR_seq) > 0 and len(rLTR_seq) > 0 and len(LTR_int_seq) > 0
+                and "NNNNNNNNNN" not in lLTR_seq and "NNNNNNNNNN" not in rLTR_seq and "NNNNNNNNNN" not in LTR_int_seq):
+            intact_name = chr_name + ":" + str(LTR_start) + ".." + str(LTR_end)
+            LTR_terminals[intact_name + "-lLTR" + "#LTR"] = lLTR_seq
+            LTR_terminals[intact_name + "-rLTR" + "#LTR"] = rLTR_seq
+            LTR_intacts[intact_name] = intact_seq
+            if chr_name + "-" + str(lLTR_start) + "-" + str(lLTR_end) not in dirty_dicts:
+                LTR_ints[intact_name + "-int" + "#LTR"] = LTR_int_seq
+    store_fasta(LTR_ints, ltr_internal)
+    store_fasta(LTR_terminals, ltr_terminal)
+    store_fasta(LTR_intacts, ltr_intact)
+    with open(ltr_intact_list, "w") as f_save:
+        for line in deredundant_lines:
+            parts = line.split(" ")
+            chr_name = parts[11]
+            ref_seq = ref_contigs[chr_name]
+            lLTR_start, lLTR_end, rLTR_start, rLTR_end = int(parts[3]), int(parts[4]), int(parts[6]), int(parts[7])
+            identity = float(parts[9]) / 100
+            insertion_time = int(estimate_insert_time(identity, float(miu)))
+            ltr_name, _has_structure, tsd_seq = is_ltr_has_structure(chr_name + ":" + str(int(parts[0])) + ".." + str(int(parts[1])), line, ref_seq)
+            motif = ref_seq[lLTR_start - 1: lLTR_start - 1 + 2] + ref_seq[rLTR_end - 2: rLTR_end]
+            if tsd_seq == "":
+                tsd_seq = "NA"
+            f_save.write(ltr_name + "\t" + "pass" + "\t" + "motif:" + motif + "\t" + "TSD:" + tsd_seq + "\t" + "NA..NA\tNA..NA\t" + "IN:" +
+                         str(lLTR_end) + ".." + str(rLTR_start - 1) + "\t" + str(identity) + "\t.\tNA\tNA" + "\t" + str(insertion_time) + "\n")
+
+
+def assign_label_to_lib(lib, intact_LTR_labels):
+    """module/Util.py:13859, in place: the entries of lib get the names LTR_<i><type>#<label>, <type> the last four characters of the
+    old name (-lLTR and -rLTR both read -LTR: the two terminals of an element become two entries, both with the second's sequence) and <label> that of the element
+    <chr>:<start>..<end>.  An entry shares the index of its partner _LTR / _INT (the names of the LTR_retriever branch); FiLTR's
+    names end in -LTR / -int, so there every entry has an index of its own -- as in the reference."""
+    ltr_names, ltr_contigs = read_fasta(lib)
+    no_label_ltr_names, no_label_ltr_contigs = [], {}
+    for name in ltr_names:
+        seq = ltr_contigs[name]
+        name = name.split("#")[0].replace("-lLTR", "-LTR").replace("-rLTR", "-LTR")
+        no_label_ltr_names.append(name)
+        no_label_ltr_contigs[name] = seq
+    ltr_index = 0
+    stored_names = set()
+    confident_ltr_cut_contigs = {}
+    for name in no_label_ltr_names:
+        if name in stored_names:
+            continue
+        intact_ltr_name, ltr_type = name[:-4], name[-4:]
+        label = intact_LTR_labels[intact_ltr_name]
+        confident_ltr_cut_contigs["LTR_" + str(ltr_index) + ltr_type + "#" + label] = no_label_ltr_contigs[name]
+        other_ltr_type = "_INT" if ltr_type == "_LTR" else "_LTR"
+        other_name = intact_ltr_name + other_ltr_type
+        if other_name in no_label_ltr_contigs:
+            confident_ltr_cut_contigs["LTR_" + str(ltr_index) + other_ltr_type + "#" + label] = no_label_ltr_contigs[other_name]
+            stored_names.add(other_name)
+        ltr_index += 1
+    store_fasta(confident_ltr_cut_contigs, lib)
+
+
+LTR_LIBRARY_FILES = ("intact_LTR.list", "intact_LTR.fa", "confident_ltr.terminal.fa", "confident_ltr.internal.fa", "confident_ltr.fa",
+                     "filtered_single_copy_LTRs.txt")
+
+
+def ltr_library(reference, out_dir, miu=1.3e-8, is_output_lib=1, flanking_len=100, max_copy_num=100, coverage_threshold=0.95, threads=1, debug=0,
+                ctx=None, scan=None, hsps=None, cluster=None, frame_vote=None, support=None, dedup=None, model=None, deep=None, threshold=0.5,
+                domain_search=None, log=None, seconds=None):
+    """FiLTR from the genome to its LTR library, in-tree (bin/FiLTR-main/src/LTR_filter.py:542-813 with is_filter_single and
+    is_deredundant on, its defaults): ltr_detect (steps 1 to 3), then
+      step 4  filter_ltr_by_copy_num + filter_single_copy_ltr -> out_dir/intact_LTR_homo.txt, filtered_single_copy_LTRs.txt;
+      step 5  out_dir/confident_ltr.scn: the lines whose element step 4 kept (the file ltr_detect wrote is replaced);
+      step 6  get_LTR_seq_from_scn -> confident_ltr.terminal.fa, confident_ltr.internal.fa, intact_LTR.fa, intact_LTR.list;
+      steps 7 and 8 (is_output_lib)  deredundant_for_LTR_v5 on the terminals at 0.95 and on the internal sequences at 0.8, their
+              .cons files joined -> confident_ltr.fa.
+    The contamination filters of step 3's chunks (filter_tir, filter_helitron, filter_sine), the tandem-repeat filter of the terminals
+    and clean_LTR_internal.py are not part of this build.  reference is a FASTA path; it is packed on ctx (set_reference) unless
+    support= is given.  scan / hsps / cluster / frame_vote / model / deep / threshold: see ltr_detect; support: see
+    filter_ltr_by_copy_num; dedup: replaces deredundant_for_LTR_v5 (same arguments); domain_search: the mode of get_domain_info;
+    seconds: a dict that receives the wall seconds of every step.  The de-duplication packs the library on the context where the
+    genome was (deredundant_for_LTR_v5): set_reference packs the genome again.  -> {file name: path} of LTR_LIBRARY_FILES"""
+    os.makedirs(out_dir, exist_ok=True)
+    t = [time.perf_counter()]
+    lap = lambda key: (t.append(time.perf_counter()), seconds is not None and seconds.__setitem__(key, t[-1] - t[-2]))  # noqa: E731
+    _conf, table = ltr_detect(reference, out_dir, flanking_len, max_copy_num, ctx=ctx, scan=scan, hsps=hsps, cluster=cluster, frame_vote=frame_vote,
+                              seconds=seconds, model=model, deep=deep, threshold=threshold)
+    t.append(time.perf_counter())
+    final_scn = os.path.join(out_dir, "filter_terminal_align.scn")
+    ref_names, ref_contigs = read_fasta(reference)
+    _terminals, leftLtr2Candidates = left_ltr_terminals(final_scn, ref_contigs, log)
+    _candidates, ltr_lines = read_scn(final_scn, log)
+    with open(os.path.join(out_dir, "remove_recomb.scn")) as f:
+        dirty_dicts = remove_dirty_LTR([line.replace("\n", "") for line in f if line.strip() and not line.startswith("#")], log)
+    msa_flank = os.path.join(out_dir, "msa_flank.txt")
+    with open(msa_flank, "w") as f_save:
+        for name in leftLtr2Candidates:
+            f_save.write(name + "\t" + str(int(bool(table.get(name, (False,))[0]))) + "\n")
+    # step 4
+    if support is None:
+        ctx = ctx or set_reference(reference)
+    ltr_copies, internal_ltrs = filter_ltr_by_copy_num(msa_flank, leftLtr2Candidates, ltr_lines, reference, out_dir, None, threads, coverage_threshold,
+                                                       debug, ctx=ctx, support=support)
+    lap("copy_support")
+    if debug:
+        with open(os.path.join(out_dir, "ltr_copies.json"), "w", encoding="utf-8") as f:
+            json.dump(ltr_copies, f, ensure_ascii=False, indent=4)
+    intact_output_path = os.path.join(out_dir, "intact_LTR_homo.txt")
+    ltr_protein_db, other_protein_db = filtr_protein_libs()
+    filter_single_copy_ltr(intact_output_path, os.path.join(out_dir, "filtered_single_copy_LTRs.txt"), os.path.join(out_dir, "single_copy_internal.fa"),
+                           ltr_copies, internal_ltrs, ltr_protein_db, other_protein_db, out_dir, threads, (ref_names, ref_contigs),
+                           leftLtr2Candidates, ltr_lines, log, debug, search=domain_search, ctx=ctx)
+    lap("single_copy")
+    # step 5
+    true_ltrs = set()
+    with open(intact_output_path, "r") as f_r:
+        for line in f_r:
+            parts = line.replace("\n", "").split("\t")
+            if int(parts[1]):
+                true_ltrs.add(parts[0])
+    confident_scn = os.path.join(out_dir, "confident_ltr.scn")
+    store_scn([ltr_lines[leftLtr2Candidates[name]] for name in leftLtr2Candidates if name in true_ltrs], confident_scn)
+    # step 6
+    paths = {name: os.path.join(out_dir, name) for name in LTR_LIBRARY_FILES}
+    get_LTR_seq_from_scn(reference, confident_scn, paths["confident_ltr.terminal.fa"], paths["confident_ltr.internal.fa"], paths["intact_LTR.fa"],
+                         dirty_dicts, paths["intact_LTR.list"], miu)
+    lap("sequences")
+    # steps 7 and 8
+    if is_output_lib:
+        dedup = dedup or (lambda *a: deredundant_for_LTR_v5(*a, ctx=ctx))
+        dedup(paths["confident_ltr.terminal.fa"], out_dir, threads, "terminal", 0.95, debug)
+        dedup(paths["confident_ltr.internal.fa"], out_dir, threads, "internal", 0.8, debug)
+        with open(paths["confident_ltr.fa"], "w") as out:
+            for part in (paths["confident_ltr.terminal.fa"], paths["confident_ltr.internal.fa"]):
+                with open(part + ".cons") as f:
+                    shutil.copyfileobj(f, out)
+        lap("library")
+    return paths
+
+
 # ---- the annotation of the genome with the library (where HiTE ends with RepeatMasker: annotate_genome.py:17, pan_annotate_genome.py:27)
 # In-tree stage, PARITY UNPINNED against RepeatMasker: what is computed is the "genome annotation" of include/hite_gpu.h
 # (Context.annotate), held to its CPU twin.  annot= replaces the device stage (the signature of Context.annotate; the CPU tests pass the

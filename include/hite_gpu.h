@@ -862,6 +862,47 @@ int hite_find_copies_restricted(hite_ctx *ctx, void **state_io, int32_t n_cand, 
 int hite_copy_clips_dev(void *state, const uint32_t **d_clip, int64_t *n);
 int hite_copy_clips(void *state, int64_t cap, uint32_t *clip);
 
+/* ---- full-length copy support of the confident intact LTR elements --- FiLTR's step 4 (bin/FiLTR-main/src/Util.py:6119
+ * filter_ltr_by_copy_num): `minimap2 -ax asm20 -N 100 -p 0.2` of every element against the genome, get_copies_minimap2 (:6509-6556)
+ * at 0.985, then get_intact_ltr_copies (:11022-11147).  The search is this build's copy finder (unpinned against minimap2); the
+ * rules on its records are the reference's, integer for integer, every floating-point compare in binary64 with the reference's
+ * operations in its order (a division or a multiplication of exactly converted integers, then the compare; a zero denominator,
+ * where the reference raises ZeroDivisionError, answers false).  Twin: tests/ltrcopy_twin.py; rules: hite_amd/csrc/hite_ltrcopy.h.
+ *  The table: element k has el_len[k] bases and the records copy_first[k] .. copy_first[k + 1] (copy_first[0] = 0, at most 300 each)
+ *  -- contig, start1 <= end1 (1-based, inclusive) and clip = the element's bases the alignment left out at its ends,
+ *  left | right << 16 (hite_copy_clips; the soft clips of a record of minimap2; clip NULL: none).  The candidate lines, in the order
+ *  of ltr_lines: std_start = lLTR_start - 1, std_end = rLTR_end on std_contig.
+ *  1. Coverage: aligned = el_len - left - right; a record stays when aligned / el_len >= full_length_coverage and
+ *     aligned / (end1 - start1 + 1) >= full_length_coverage.
+ *  2. Candidate table: in input order a line goes into the bucket (std_contig, map_fragment(std_start, std_end, segment_len))
+ *     (:4837) unless a line stored there before overlaps it (get_overlap_len, :4200: min of the ends - max of the starts, at least
+ *     0) by >= overlap_threshold of |end - start| of either.  A line beyond the segments of its contig is not stored.
+ *  3. Match: a record stays when a stored line of the bucket (contig, map_fragment(start1, end1, segment_len)) -- that bucket alone
+ *     -- passes the same two-sided test with (start1, end1).
+ *  4. Redundancy, per element: the records that stayed, stably ascending by end1 - start1 -- before the sort the reference holds
+ *     them contig by contig, the contigs in the order in which the records that pass rule 1 first name them over the whole call,
+ *     and in input order inside a contig --; record i is dropped when a LATER record j of that order lies on the same contig with
+ *     min(end) - max(start) + 1 >= 0.95 * (end1_i - start1_i + 1) (the literal 0.95).  The others are the output, in that order.
+ * Output: the copies of element k are out_first[k] .. out_first[k + 1] of (out_contig, out_start1, out_end1); *n_out = their number,
+ * set even when HITE_ECAP is returned because it exceeds cap (out_first is all zero then and no copy is written; stats are).  stats (may be NULL) =
+ * {records in, records that pass rule 1, that also pass rule 3, copies kept}.  n_el = 0, n_std = 0 and empty elements are valid.
+ * HITE_EINVAL: a negative count, a missing buffer, descending offsets, an element of more than 300 records, a contig outside
+ * 0 .. n_contig - 1, a negative coordinate of a line, thresholds that are NaN or outside [0, 1], segment_len <= 0.
+ * hite_ltr_copy_support takes the elements as sequences (el, el_off as hite_find_copies takes candidates; n_el < 2^19; *state_io the
+ * index handle, built when NULL), runs hite_find_copies_dev on the packed genome and applies the rules to its table where it lies:
+ * the copy table never comes down.  The finder runs in aligned-interval mode whatever hite_copy_config[_ctx] says; the context's
+ * setting is the same after the call.  Contigs and their lengths are the packed genome's. */
+int hite_ltr_copy_support_records(hite_ctx *ctx, int64_t n_el, const int64_t *el_len, const int32_t *copy_first /* n_el + 1 */,
+                                  const int32_t *contig, const int64_t *start1, const int64_t *end1, const uint32_t *clip, int64_t n_std,
+                                  const int32_t *std_contig, const int64_t *std_start, const int64_t *std_end, int32_t n_contig,
+                                  const int64_t *contig_len, double full_length_coverage, double overlap_threshold, int64_t segment_len,
+                                  int64_t cap, int32_t *out_first /* n_el + 1 */, int32_t *out_contig, int64_t *out_start1, int64_t *out_end1,
+                                  int64_t *n_out, int64_t *stats /* 4 */);
+int hite_ltr_copy_support(hite_ctx *ctx, void **state_io, int32_t n_el, const uint8_t *el, const int64_t *el_off /* n_el + 1 */, int64_t n_std,
+                          const int32_t *std_contig, const int64_t *std_start, const int64_t *std_end, double full_length_coverage,
+                          double overlap_threshold, int64_t segment_len, int64_t cap, int32_t *out_first /* n_el + 1 */, int32_t *out_contig,
+                          int64_t *out_start1, int64_t *out_end1, int64_t *n_out, int64_t *stats /* 4 */);
+
 /* ---- star alignment: this build's GPU-native stage where the reference runs the external
  * `mafft --preservecase --quiet --thread 1` (Util.py:10416; third-party, unpinned, absent -> parity unpinned against
  * mafft itself).  Definition of the stage: every row is aligned to the centre (first row of the candidate) by the
