@@ -116,6 +116,12 @@ class Context:
         None / -1 = follow the process default again (HITE_FALLBACK_OVERLAP=0: one after the other).  Both give the same bytes."""
         self._check(self.lib.hite_fallback_overlap_ctx(self.h, -1 if mode is None or int(mode) < 0 else int(bool(mode))), "hite_fallback_overlap_ctx")
 
+    def wide_tb_runs(self, mode):
+        """which form of the fall-back alignment's traceback THIS context runs (include/hite_gpu.h hite_wide_tb_runs_ctx): True / 1 = by
+        runs of up to 64 path steps per trip (the default), False / 0 = a column per step, None / -1 = follow the process default again
+        (HITE_WIDE_TB_RUNS=0: a column per step).  Both write the same bytes."""
+        self._check(self.lib.hite_wide_tb_runs_ctx(self.h, -1 if mode is None or int(mode) < 0 else int(bool(mode))), "hite_wide_tb_runs_ctx")
+
     def fill_tile_limits(self):
         """(positions of a tile, window-range bytes that fit the LDS slot, rows of a workgroup per trip, row slices) of the tile form"""
         out = (C.c_int32 * 4)()

@@ -1104,6 +1104,10 @@ __device__ __forceinline__ void lane_below_keep3(uint32_t v2, uint32_t v1, uint3
     asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %3 wave_shr:1 row_mask:0xf bank_mask:0xf\n\tv_mov_b32_dpp %1, %4 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
                  "v_mov_b32_dpp %2, %5 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(k2), "+v"(k1), "+v"(k0) : "v"(v2), "v"(v1), "v"(v0));
 }
+// The fall-back runs beside the layout of the other candidates (hite_msa.hip); the stream's priority orders the dispatch of workgroups,
+// not the issue inside a SIMD, so its wavefronts ask for the issue slots themselves: some fifty of them on 1 024 SIMDs.
+// The forward kernel alone: its time is its instruction chain, 2.12 -> 1.90 ms beside the layout.  The tracebacks wait for memory and
+// were SLOWER with it, both forms (0.54 -> 0.59 ms, 1.39 -> 1.55 ms; profiles/r20_fallback_walk.txt): they do not raise it.
 struct WideFwd {
     uint32_t X2, X1, X0, A0, A1, AN, f0, f1, fn;
     uint32_t kz0, kz1, ko0, ko1;       // registers of lane_below_keep: lane 0 holds 0 / 0 / bit 31 / bit 31
@@ -1177,6 +1181,7 @@ __global__ void __launch_bounds__(64) align_wide_fwd_kernel(AlignArgs P, const i
     const int g = list[pi];
     const int c = P.row_cand[g], g0 = P.row_first[c];
     if (g == g0) return;
+    __builtin_amdgcn_s_setprio(3);
     const int m = P.win_len[g0], n = P.win_len[g];
     const uint8_t *b = P.win + P.win_off[g];
     const uint4 *pl = P.planes + P.plane_off[c];
@@ -1319,6 +1324,114 @@ __global__ void __launch_bounds__(64) align_wide_tb_kernel(AlignArgs P, const in
                     }
                 }
             }
+        }
+    }
+    if (fail) { if (lane == 0) P.st[g] = 1; }
+    else out.run(i - 1, i, 0x8000u);
+}
+
+// >>> wide_walk_probe (tests/test_host_wide_walk.py compiles this block for the host and walks random bit matrices with it, 64 "lanes"
+// in a loop, step for step against the column-by-column rule)
+// The same traceback by RUNS (the default; HITE_WIDE_TB_RUNS=0 / hite_wide_tb_runs_ctx: the kernel above).  By the mismatch-1 / gap-3
+// definition a mismatch is a diagonal step too, so the path of a real pair is long runs of diagonal steps cut by a few gaps.  The
+// walk stands at cell (i, j); lane q looks at column j - q, whose band starts at row t (fullt), and gathers three words of it: the
+// diagonal word of row i - q (the cell the path reaches if everything before it was a diagonal step), and the diagonal and the up
+// word of row i (the cell it reaches if everything before it was a left step).  wide_walk_word: which word of the column's nw holds
+// band row kb (clamped: a row outside the band is refused by wide_walk_lane, the gather stays inside the column).
+constexpr uint32_t WALK_DIAG = 1u, WALK_LEFT = 2u;
+__device__ __forceinline__ int wide_walk_word(int kb, int nw) {
+    const int w = kb >> 5;
+    return w < 0 ? 0 : (w >= nw ? nw - 1 : w);
+}
+// WALK_DIAG: the step at (i - q, j - q) is a diagonal one -- the cell is on the matrix, in the band, its diagonal bit set.
+// WALK_LEFT: the step at (i, j - q) is a left one -- on the matrix, in the band, the diagonal bit clear and the stop bit
+// (diagonal | ~up) set at the row itself, so that the general rule finds a run of no up steps and no diagonal behind it.
+// (Whether the column exists is a mask on the flags, not a way round the words: the gathers stay unconditional.)
+__device__ __forceinline__ uint32_t wide_walk_lane(int i, int j, int q, int t, uint32_t dg_diag, uint32_t dg_row, uint32_t up_row, int nw) {
+    const int kd = i - q - t - 1, kr = i - t - 1;
+    const uint32_t fd = (uint32_t)(i - q > 0) & (uint32_t)((unsigned)kd < (unsigned)(32 * nw)) & (dg_diag >> (kd & 31));
+    const uint32_t fl = (uint32_t)(i > 0) & (uint32_t)((unsigned)kr < (unsigned)(32 * nw)) & ~((dg_row | up_row) >> (kr & 31));
+    return ((fd & 1u) * WALK_DIAG | (fl & 1u) * WALK_LEFT) & (0u - (uint32_t)(j - q > 0));
+}
+// length of the run that starts at lane 0: the lanes below the first one whose flag is clear
+__device__ __forceinline__ int wide_walk_run(unsigned long long flags) { return ~flags == 0ull ? 64 : __builtin_ctzll(~flags); }
+// The band positions (fullt) travel in two registers: ta of lane q belongs to column j - q, tb to column j - 64 - q.  When the
+// walk has moved by `moved` (0 .. 64) columns, the new ta of lane q is the value of lane wide_walk_shift_lane of the old ta where
+// wide_walk_shift_from_a holds and of the old tb elsewhere; the new tb is read from memory at wide_walk_col(j - 64, q).
+// wide_walk_col: the column lane q looks at, clamped to the first one (what a lane finds for a column that does not exist is masked
+// away by wide_walk_lane; column 0 is never written).
+__device__ __forceinline__ int wide_walk_col(int j, int q) { return j - q > 0 ? j - q : 1; }
+__device__ __forceinline__ int wide_walk_shift_lane(int q, int moved) { return (q + moved) & 63; }
+__device__ __forceinline__ bool wide_walk_shift_from_a(int q, int moved) { return q + moved < 64; }
+// <<< wide_walk_probe
+
+// A trip of the walk is ONE round trip to memory: the three gathers above and the two full rows of column j (for the general step,
+// should lane 0 need it) leave together.  The band positions come from registers: when the walk has moved by r columns the new ta
+// is the two shifted along the lanes by r (two ds_bpermute), and the new tb is read beside this trip's gathers, so that no trip
+// waits for fullt before it can ask for its words.  No load sits under a branch.
+// Diagonal run: its ops leave through WideOps::run_diag.  Left run: no op.  Anything else at lane 0 -- an up run, a cell outside
+// the band, no stop bit below -- is the general step of the kernel above on the rows already fetched.
+__global__ void __launch_bounds__(64) align_wide_tb_runs_kernel(AlignArgs P, const int32_t *__restrict__ list, int nlist) {
+    constexpr int NW = AL_WIDE_NW, W = 32 * NW;
+    const int pi = blockIdx.x;
+    if (pi >= nlist) return;
+    const int lane = threadIdx.x;
+    const int g = list[pi];
+    const int c = P.row_cand[g], g0 = P.row_first[c];
+    if (g == g0 || P.st[g] != 0) return;
+    const int m = P.win_len[g0], n = P.win_len[g];
+    WideOps out;
+    out.ops = P.ops + P.ops_base[c] + (int64_t)(g - g0) * (m + 1); out.m = m; out.lane = lane; out.acc = 0u;
+    const int64_t full0 = P.full_off[g];
+    const int32_t *ft = P.fullt + full0;                       // columns 1 .. n of this pair (column 0 is never written: clamped away)
+    const uint32_t *fb = P.fullbuf + full0 * (2 * NW);
+    int i = m, j = n;
+    bool fail = false;
+    int ta = ft[wide_walk_col(j, lane)], tb = ft[wide_walk_col(j - 64, lane)];
+    int moved = 0;                                             // columns the last trip moved by: ta and tb are that far behind
+    while (i > 0 && j > 0 && !fail) {
+        i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j);      // (wave-uniform by construction)
+        {
+            const int src = wide_walk_shift_lane(lane, moved);
+            const int xa = __shfl(ta, src, 64), xb = __shfl(tb, src, 64);
+            ta = wide_walk_shift_from_a(lane, moved) ? xa : xb;
+            tb = ft[wide_walk_col(j - 64, lane)];
+        }
+        const int t = ta;
+        const uint32_t *col = fb + (int64_t)wide_walk_col(j, lane) * (2 * NW);
+        const uint32_t dgw = fb[(int64_t)j * (2 * NW) + lane], upw = fb[(int64_t)j * (2 * NW) + NW + lane];
+        const int wd = wide_walk_word(i - lane - t - 1, NW), wr = wide_walk_word(i - t - 1, NW);
+        const uint32_t dg_diag = col[wd], dg_row = col[wr], up_row = col[NW + wr];
+        const uint32_t f = wide_walk_lane(i, j, lane, t, dg_diag, dg_row, up_row, NW);
+        // (the words of the left run are wanted HERE, with the others: left to itself the compiler moves their loads behind the test
+        // of the diagonal run, under the lanes' own branch, and a gap costs a second round trip)
+        asm volatile("" : : "v"(dg_row), "v"(up_row));
+        const unsigned long long bd = __ballot(f & WALK_DIAG), bl = __ballot(f & WALK_LEFT);
+        int r = wide_walk_run(bd);
+        if (r > 0) { out.run_diag(i - 1, r, j - i); i -= r; j -= r; moved = r; continue; }
+        r = wide_walk_run(bl);
+        if (r > 0) { j -= r; moved = r; continue; }
+        // the general step at column j
+        moved = 0;
+        const int kb = i - __builtin_amdgcn_readfirstlane(t) - 1;
+        if ((unsigned)kb >= (unsigned)W) { fail = true; break; }
+        const int wq = kb >> 5;
+        const uint32_t low = 0xffffffffu >> (31 - (kb & 31));
+        const uint32_t sbit = dgw | ~upw;
+        const uint32_t mk = lane > wq ? 0u : (lane == wq ? sbit & low : sbit);
+        const unsigned long long nz = __ballot(mk != 0u);
+        if (nz == 0ull) { fail = true; break; }
+        const int tl = 63 - __clzll(nz);
+        const uint32_t mt = (uint32_t)__builtin_amdgcn_readlane((int)mk, tl), dt = (uint32_t)__builtin_amdgcn_readlane((int)dgw, tl);
+        const int ps = 32 * tl + 31 - __clz(mt);
+        int nup = kb - ps;
+        if (nup > i) nup = i;
+        out.run(i - 1, nup, (uint32_t)j | 0x8000u);
+        i -= nup;
+        if (i > 0) {
+            if ((dt >> (ps & 31)) & 1u) { out.put(i - 1, (uint32_t)(j - 1)); i--; j--; }
+            else j--;
+            moved = 1;
         }
     }
     if (fail) { if (lane == 0) P.st[g] = 1; }
@@ -1987,7 +2100,8 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
             ACHK(aalloc(ctx, A, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
             ACHK(aalloc(ctx, A, (size_t)tcols + 16, &P.fullt));
             hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
-            hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
+            if (hite_wide_tb_runs_mode(ctx)) hipLaunchKernelGGL(align_wide_tb_runs_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
+            else hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
             hite_prof_end(ctx, tk, st);
         } else if (cnt > 0) {
             // ---- the fork.  The fall-back's ~50 wavefronts run on the high-priority stream while the caller works, on `st`, on the
@@ -2011,7 +2125,8 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
             HITE_CHECK(ctx, hipStreamWaitEvent(s2, S->ev_fork, 0));
             const int tl = hite_prof_begin(ctx, "align_fallback", s2);
             hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
-            hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
+            if (hite_wide_tb_runs_mode(ctx)) hipLaunchKernelGGL(align_wide_tb_runs_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
+            else hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
             hite_prof_end(ctx, tl, s2);
             HITE_CHECK(ctx, hipEventRecord(S->ev_join, s2));
             HITE_CHECK(ctx, hipMemsetAsync(pending, 0, (size_t)n_cand * 4, st));

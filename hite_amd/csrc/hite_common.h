@@ -72,6 +72,7 @@ struct hite_ctx {
     int32_t fill_tiles;              // hite_fill_config_ctx: 1 the tile form of the sparse fill / 0 the per-cell form / -1 the process default
     int32_t fallback_overlap;        // hite_fallback_overlap_ctx: 1 the fall-back alignment beside the layout of the other candidates / 0 serial / -1 the process default
     int32_t gather_chunks;           // hite_gather_config_ctx: 1 the window gather in chunks of the destination / 0 a wavefront per row / -1 the process default
+    int32_t wide_tb_runs;            // hite_wide_tb_runs_ctx: 1 the fall-back's traceback by runs of up to 64 steps / 0 a column per step / -1 the process default
     const int64_t *d_msa_win_off;    // per row of the last star alignment: its window, and where its back pads begin (HITE_IS_ROW_PAD;
     const int32_t *d_msa_win_len;    // layout, fill and the judge's LDS kernels read the rows through these)
     const uint32_t *d_msa_pads;      // per row: pad bytes in front | behind << 16
@@ -98,6 +99,7 @@ struct hite_ctx {
 };
 void hite_fmea_release(hite_ctx *ctx);
 int hite_fallback_overlap_mode(const hite_ctx *ctx);   // 1 / 0: the context's setting, or the process default (hite_ctx.hip)
+int hite_wide_tb_runs_mode(const hite_ctx *ctx);       // 1 / 0: the same for the form of the fall-back's traceback (hite_ctx.hip; read by hite_align.hip)
 int hite_aux_streams(hite_ctx *ctx, int k, hipStream_t *st, hipEvent_t *fork_ev, hipEvent_t *join_ev);
 
 // record the time of everything enqueued on `st` between begin and end as stage `name`

@@ -28,6 +28,7 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
     c->fill_tiles = -1;
     c->gather_chunks = -1;
     c->fallback_overlap = -1;
+    c->wide_tb_runs = -1;
     // test knobs of hite_msa_subcluster (hite_subcluster.hip), read here so that two contexts of a process may differ
     c->subcluster_chunk = HITE_SUBCLUSTER_CHUNK;
     if (const char *e = getenv("HITE_SUBCLUSTER_CHUNK_ROWS")) {
@@ -115,6 +116,26 @@ int hite_fallback_overlap_mode(const hite_ctx *ctx) {
 extern "C" int hite_fallback_overlap_ctx(hite_ctx *ctx, int32_t mode) {
     if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
     ctx->fallback_overlap = mode;
+    return HITE_OK;
+}
+
+// which form of the fall-back's traceback runs (hite_align.hip): 1 = by runs of up to 64 path steps per trip (align_wide_tb_runs_kernel),
+// 0 = a column per step (align_wide_tb_kernel), -1 = the process default, taken from the environment once (HITE_WIDE_TB_RUNS=0: a
+// column per step).  Both forms write the same bytes.
+static int g_wide_tb_runs = -1;
+int hite_wide_tb_runs_mode(const hite_ctx *ctx) {
+    if (ctx->wide_tb_runs >= 0) return ctx->wide_tb_runs;
+    int v = __atomic_load_n(&g_wide_tb_runs, __ATOMIC_RELAXED);
+    if (v < 0) {
+        const char *e = getenv("HITE_WIDE_TB_RUNS");
+        v = (e && !strcmp(e, "0")) ? 0 : 1;
+        __atomic_store_n(&g_wide_tb_runs, v, __ATOMIC_RELAXED);
+    }
+    return v;
+}
+extern "C" int hite_wide_tb_runs_ctx(hite_ctx *ctx, int32_t mode) {
+    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
+    ctx->wide_tb_runs = mode;
     return HITE_OK;
 }
 

@@ -993,6 +993,10 @@ int hite_gather_mode_ctx(hite_ctx *ctx);
  * beside the pad fix and the layout of the candidates it does not touch, which are then done once more for the others; mode 0: one after
  * the other; -1 follows the process default again (on, unless HITE_FALLBACK_OVERLAP=0 in the environment).  The same bytes either way. */
 int hite_fallback_overlap_ctx(hite_ctx *ctx, int32_t mode);
+/* The traceback of that fall-back has two forms that write the same bytes: by runs -- up to 64 diagonal or left steps of the path per
+ * trip to memory (the default) -- and a column per step.  mode 1 / 0 selects the run / column form for this context, -1 follows the
+ * process default again (HITE_WIDE_TB_RUNS=0 in the environment: a column per step). */
+int hite_wide_tb_runs_ctx(hite_ctx *ctx, int32_t mode);
 int hite_fill_tile_limits(int32_t out[4]);
 
 /* ---- the fine stage in one call --- body of flank_region_align_v5 from the copy table on ----------
