@@ -1755,7 +1755,8 @@ struct AlignState {
     int lanes_min = -1;            // lane-parallel kernels for pairs of >= this many columns; -1: by the size of the run; -2: never
     float lanes_scale[4] = {1.f, 1.f, 1.f, 1.f};     // measurement aid ($HITE_ALIGN_LANES_SCALE=a,b,c,d): factors on the cost model's lane-parallel work (4-word, 8-word, traceback) and forward chain
     bool sort_attr = false;
-    hipStream_t st2 = nullptr;     // the wider bands run here, beside the traceback of the pairs that are already final; the longest pairs' lane-parallel kernels
+    bool debug = false;            // $HITE_ALIGN_DEBUG: a line per run and per 8-word level on stderr
+    hipStream_t st2 = nullptr;    // the wider bands run here, beside the traceback of the pairs that are already final; the longest pairs' lane-parallel kernels
     hipEvent_t ev = nullptr, ev_fork = nullptr, ev_join = nullptr;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // a run between hite_align_begin and hite_align_finish: what the finish half needs
@@ -1766,6 +1767,27 @@ struct AlignState {
     int32_t *row_dead = nullptr, *cand_flag = nullptr, *info = nullptr;
     hipStream_t st = nullptr;
 };
+
+// The scalar read-backs: d_scal and h_pin hold SLOT_WORDS int64 words each, and a reader copies its words from d_scal to the same
+// words of h_pin and synchronises its stream.  The users on `st` follow one another (each has synchronised `st` before the next
+// writes), so they share words 0..7.  The wider levels of the cap >= 16 route build their lists on the side stream while `st` still
+// runs what was enqueued before them, and the finish half runs on `st` while the side stream may still hold the fall-back: words
+// that the side stream uses are used by nothing on `st`.
+enum AlignSlot {
+    SLOT_PLANE = 0,        // the plane words of the call (align_prep); read after assign_records has synchronised
+    SLOT_ASSIGN = 1,       // assign_records on `st`: block-strips, lane-parallel prefix of the forward pass, of the traceback
+    SLOT_LIST = 0,         // build_list on `st`: count, columns, dead
+    SLOT_STATS = 0,        // the finish half: the seven counters of align_stats_kernel (eight words cleared)
+    SLOT_LIST_SIDE = 8,    // build_list on the side stream: count, columns (it never asks for the dead rows)
+    SLOT_ASSIGN_SIDE = 10, // assign_records on the side stream
+    SLOT_WORDS = 64
+};
+constexpr int SLOT_ASSIGN_WORDS = 3, SLOT_LIST_WORDS = 3, SLOT_STATS_WORDS = 8, SLOT_MAIN_END = 8;
+static_assert(SLOT_PLANE < SLOT_ASSIGN, "the plane words are read after assign_records has written its own");
+static_assert(SLOT_ASSIGN + SLOT_ASSIGN_WORDS <= SLOT_MAIN_END && SLOT_LIST + SLOT_LIST_WORDS <= SLOT_MAIN_END &&
+              SLOT_STATS + SLOT_STATS_WORDS <= SLOT_MAIN_END, "the words of `st`");
+static_assert(SLOT_LIST_SIDE >= SLOT_MAIN_END && SLOT_LIST_SIDE + 2 <= SLOT_ASSIGN_SIDE && SLOT_ASSIGN_SIDE + SLOT_ASSIGN_WORDS <= SLOT_WORDS,
+              "the words of the side stream: apart from those of `st`, from one another, inside the buffers");
 
 // the second stream gets the highest priority: its few long-running waves are the critical path and must not queue behind the
 // traceback's many short workgroups
@@ -1778,7 +1800,7 @@ static hipError_t align_make_stream(hipStream_t *out) {
 static AlignState *align_state(hite_ctx *ctx) {
     if (!ctx->align_state) {
         AlignState *S = new AlignState();
-        if (hipHostMalloc((void **)&S->h_pin, 64 * sizeof(int64_t)) != hipSuccess || hipMalloc((void **)&S->d_scal, 64 * sizeof(int64_t)) != hipSuccess ||
+        if (hipHostMalloc((void **)&S->h_pin, SLOT_WORDS * sizeof(int64_t)) != hipSuccess || hipMalloc((void **)&S->d_scal, SLOT_WORDS * sizeof(int64_t)) != hipSuccess ||
             align_make_stream(&S->st2) != hipSuccess || hipEventCreateWithFlags(&S->ev, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&S->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&S->ev_join, hipEventDisableTiming) != hipSuccess) {
             delete S;
@@ -1792,6 +1814,7 @@ static AlignState *align_state(hite_ctx *ctx) {
         if (l && *l) { const int v = atoi(l); S->lanes_min = v < -2 ? -1 : v; }
         const char *sc = getenv("HITE_ALIGN_LANES_SCALE");
         if (sc && *sc) sscanf(sc, "%f,%f,%f,%f", &S->lanes_scale[0], &S->lanes_scale[1], &S->lanes_scale[2], &S->lanes_scale[3]);
+        S->debug = getenv("HITE_ALIGN_DEBUG") != nullptr;
         ctx->align_state = S;
     }
     return (AlignState *)ctx->align_state;
@@ -1844,61 +1867,154 @@ static int aalloc(hite_ctx *ctx, Arena &A, size_t count, T **out) {
     return rc;
 }
 
-// order-preserving compaction of the rows flagged for `what`; returns the count (host) and the list (device)
-static int build_list(hite_ctx *ctx, AlignState *S, hipStream_t st, int64_t nrows, const int32_t *order, const int32_t *strips,
-                      AlignArgs &P, int what, int level, int cap, int32_t *flag, int32_t *cols, int64_t *pos, int64_t *colpos,
-                      int64_t *scan_tmp, int32_t *list, int64_t *full_off, int64_t *count, int64_t *total_cols, int slot = 0,
-                      int64_t *dead = nullptr) {
+// ---- the arrays of a call: all from the arena, which hite_align_begin resets ----
+// what build_list and assign_records work in, and their words of d_scal / h_pin: a set per stream, so that the side stream
+// builds its lists while `st` works
+struct ListWs {
+    int32_t *flag, *cols;           // cols, colpos: for the fall-back's list alone (the side stream has none)
+    int64_t *pos, *colpos, *scan_tmp;
+    int32_t *bk;
+    int64_t *boff;
+    int slot_list, slot_assign;
+};
+struct AlignWs {
+    int32_t *row_cand, *strips, *order, *pwords;
+    unsigned long long *skeys, *rec;
+    int64_t *plane_off, *full_off;
+    int32_t *list, *list_esc, *list_fin;
+    Sorter srt;
+    ListWs main, side;
+};
+// The order and the sizes of these allocations fix every address of a call relative to the arena's base.
+static int align_ws_alloc(hite_ctx *ctx, Arena &A, int32_t n_cand, int64_t total_rows, hipStream_t st, AlignWs &W, AlignArgs &P) {
+    const size_t rows = (size_t)total_rows;
+    Sorter &srt = W.srt;
+    ListWs &M = W.main, &D = W.side;
+    M.slot_list = SLOT_LIST; M.slot_assign = SLOT_ASSIGN; D.slot_list = SLOT_LIST_SIDE; D.slot_assign = SLOT_ASSIGN_SIDE;
+    ACHK(aalloc(ctx, A, rows, &W.row_cand));
+    ACHK(aalloc(ctx, A, rows, &W.strips));
+    ACHK(aalloc(ctx, A, rows + 1, &W.skeys));
+    ACHK(aalloc(ctx, A, rows + 1, &W.order));
+    srt.ctx = ctx; srt.st = st; srt.cap = total_rows; srt.hist_n = sorter_hist_elems(total_rows);
+    ACHK(aalloc(ctx, A, rows + 1, &srt.k2));
+    ACHK(aalloc(ctx, A, rows + 1, &srt.v2));
+    ACHK(aalloc(ctx, A, (size_t)srt.hist_n, &srt.hist));
+    ACHK(aalloc(ctx, A, (size_t)srt.hist_n + 1, &srt.offs));
+    ACHK(aalloc(ctx, A, (size_t)sorter_tmp_elems(srt.hist_n), &srt.bs));
+    ACHK(aalloc(ctx, A, (size_t)n_cand, &W.pwords));
+    ACHK(aalloc(ctx, A, (size_t)n_cand + 1, &W.plane_off));
+    ACHK(aalloc(ctx, A, rows, &W.rec));
+    ACHK(aalloc(ctx, A, rows / 64 + 2, &M.bk));
+    ACHK(aalloc(ctx, A, rows / 64 + 3, &M.boff));
+    ACHK(aalloc(ctx, A, rows / 64 + 2, &D.bk));
+    ACHK(aalloc(ctx, A, rows / 64 + 3, &D.boff));
+    ACHK(aalloc(ctx, A, rows, &M.flag));
+    ACHK(aalloc(ctx, A, rows, &M.cols));
+    ACHK(aalloc(ctx, A, rows, &W.list));
+    ACHK(aalloc(ctx, A, rows, &W.list_esc));
+    ACHK(aalloc(ctx, A, rows, &W.list_fin));
+    ACHK(aalloc(ctx, A, rows, &D.flag));
+    ACHK(aalloc(ctx, A, rows + 1, &D.pos));
+    ACHK(aalloc(ctx, A, (size_t)scan_tmp_elems(total_rows) + 16, &D.scan_tmp));
+    ACHK(aalloc(ctx, A, rows + 1, &M.pos));
+    ACHK(aalloc(ctx, A, rows + 1, &M.colpos));
+    ACHK(aalloc(ctx, A, rows, &W.full_off));
+    ACHK(aalloc(ctx, A, (size_t)scan_tmp_elems(total_rows > n_cand ? total_rows : n_cand) + 16, &M.scan_tmp));
+    ACHK(aalloc(ctx, A, rows, &P.U));
+    ACHK(aalloc(ctx, A, rows, &P.kst));
+    ACHK(aalloc(ctx, A, rows, &P.st));
+    ACHK(aalloc(ctx, A, rows, &P.lvl));
+    ACHK(aalloc(ctx, A, rows, &P.U4));
+    P.row_cand = W.row_cand; P.full_off = W.full_off; P.plane_off = W.plane_off; P.rec = W.rec;
+    return HITE_OK;
+}
+
+// order-preserving compaction into `list` of the rows flagged for `what` (align_flag_kernel), on `st` with the set L of `st`;
+// returns the count (host).  total_cols (may be NULL; the fall-back's list): the first column record of every listed row goes to
+// full_off, their sum here.  dead (may be NULL; with what == 1): the rows that are dead already and not on the list, counted by
+// the flag kernel; it rides on the read-back.
+static int build_list(hite_ctx *ctx, AlignState *S, hipStream_t st, const AlignWs &W, const ListWs &L, int64_t nrows, AlignArgs &P,
+                      int what, int level, int cap, int32_t *list, int64_t *count, int64_t *total_cols = nullptr, int64_t *dead = nullptr) {
     const unsigned nb = (unsigned)((nrows + 255) / 256);
-    // *dead (with what == 1): the rows that are dead already and not on the list, counted by the flag kernel; it rides on the read-back
-    if (dead) HITE_CHECK(ctx, hipMemsetAsync(S->d_scal + slot + 2, 0, 8, st));
-    hipLaunchKernelGGL(align_flag_kernel, dim3(nb), dim3(256), 0, st, nrows, order, strips, P, what, level, cap, flag, cols,
-                       dead ? (unsigned long long *)(S->d_scal + slot + 2) : nullptr);
-    ACHK(scan_excl_buf<int32_t>(ctx, scan_tmp, flag, nrows, pos, st));
-    if (cols) ACHK(scan_excl_buf<int32_t>(ctx, scan_tmp, cols, nrows, colpos, st));
-    hipLaunchKernelGGL(align_compact_kernel, dim3(nb), dim3(256), 0, st, nrows, order, flag, pos, list, cols ? colpos : nullptr,
-                       cols ? full_off : nullptr, P.st);
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + slot, pos + nrows, 8, hipMemcpyDeviceToDevice, st));
-    if (cols) HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + slot + 1, colpos + nrows, 8, hipMemcpyDeviceToDevice, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + slot, S->d_scal + slot, dead ? 24 : 16, hipMemcpyDeviceToHost, st));
+    int32_t *cols = total_cols ? L.cols : nullptr;
+    int64_t *scal = S->d_scal + L.slot_list, *pin = S->h_pin + L.slot_list;
+    if (dead) HITE_CHECK(ctx, hipMemsetAsync(scal + 2, 0, 8, st));
+    hipLaunchKernelGGL(align_flag_kernel, dim3(nb), dim3(256), 0, st, nrows, W.order, W.strips, P, what, level, cap, L.flag, cols,
+                       dead ? (unsigned long long *)(scal + 2) : nullptr);
+    ACHK(scan_excl_buf<int32_t>(ctx, L.scan_tmp, L.flag, nrows, L.pos, st));
+    if (cols) ACHK(scan_excl_buf<int32_t>(ctx, L.scan_tmp, cols, nrows, L.colpos, st));
+    hipLaunchKernelGGL(align_compact_kernel, dim3(nb), dim3(256), 0, st, nrows, W.order, L.flag, L.pos, list, cols ? L.colpos : nullptr,
+                       cols ? W.full_off : nullptr, P.st);
+    HITE_CHECK(ctx, hipMemcpyAsync(scal, L.pos + nrows, 8, hipMemcpyDeviceToDevice, st));
+    if (cols) HITE_CHECK(ctx, hipMemcpyAsync(scal + 1, L.colpos + nrows, 8, hipMemcpyDeviceToDevice, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(pin, scal, dead ? 24 : 16, hipMemcpyDeviceToHost, st));
     HITE_CHECK(ctx, hipStreamSynchronize(st));
-    *count = S->h_pin[slot];
-    if (total_cols) *total_cols = cols ? S->h_pin[slot + 1] : 0;
-    if (dead) *dead = S->h_pin[slot + 2];
+    *count = pin[0];
+    if (total_cols) *total_cols = pin[1];
+    if (dead) *dead = pin[2];
     return HITE_OK;
 }
 
 // strip records of one forward run over `list`: block sizes, their scan, the region (arena), the addresses
 // *n_long (may be NULL): how many entries at the head of the list -- whole blocks of 64 -- go to the lane-parallel kernels
-static int assign_records(hite_ctx *ctx, AlignState *S, hipStream_t st, const int32_t *list, int64_t cnt, const int32_t *strips, int32_t *bk,
-                          int64_t *boff, int64_t *scan_tmp, unsigned long long *rec, int slot, int words = 4, int64_t *n_long = nullptr, int64_t *n_long_tb = nullptr) {
+static int assign_records(hite_ctx *ctx, AlignState *S, hipStream_t st, const AlignWs &W, const ListWs &L, const int32_t *list, int64_t cnt,
+                          int words = 4, int64_t *n_long = nullptr, int64_t *n_long_tb = nullptr) {
     if (n_long) *n_long = 0;
     if (n_long_tb) *n_long_tb = 0;
     if (cnt <= 0) return HITE_OK;
     const int64_t nb = (cnt + 63) / 64;
-    hipLaunchKernelGGL(align_blockmax_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, list, strips, bk);
-    ACHK(scan_excl_buf<int32_t>(ctx, scan_tmp, bk, nb, boff, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + slot, boff + nb, 8, hipMemcpyDeviceToDevice, st));
+    int64_t *scal = S->d_scal + L.slot_assign, *pin = S->h_pin + L.slot_assign;
+    hipLaunchKernelGGL(align_blockmax_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, list, W.strips, L.bk);
+    ACHK(scan_excl_buf<int32_t>(ctx, L.scan_tmp, L.bk, nb, L.boff, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(scal, L.boff + nb, 8, hipMemcpyDeviceToDevice, st));
     const bool lanes = n_long && S->lanes_min != -2;
     if (lanes) {
         // ns per strip of 16 columns: chains of a lone wavefront, work per block of 64 pairs on the whole machine (see the kernel)
         LaneCost fwd4 = {5440.f, 3200.f, 4.3f, 12.5f}, fwd8 = {7040.f, 3200.f, 13.75f, 25.f}, tb = {6880.f, 530.f, 4.3f, 21.5f};
         fwd4.lane_work *= S->lanes_scale[0]; fwd8.lane_work *= S->lanes_scale[1]; tb.lane_work *= S->lanes_scale[2];
         fwd4.lane_chain *= S->lanes_scale[3]; fwd8.lane_chain *= S->lanes_scale[3];
-        hipLaunchKernelGGL(align_long_blocks_kernel, dim3(1), dim3(1), 0, st, nb, bk, boff,
-                           (int64_t)(S->lanes_min < 0 ? -1 : (S->lanes_min + AL_STRIP - 1) / AL_STRIP), words == 4 ? fwd4 : fwd8, tb, S->d_scal + slot + 1);
+        hipLaunchKernelGGL(align_long_blocks_kernel, dim3(1), dim3(1), 0, st, nb, L.bk, L.boff,
+                           (int64_t)(S->lanes_min < 0 ? -1 : (S->lanes_min + AL_STRIP - 1) / AL_STRIP), words == 4 ? fwd4 : fwd8, tb, scal + 1);
     }
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + slot, S->d_scal + slot, 24, hipMemcpyDeviceToHost, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(pin, scal, lanes ? 8 * SLOT_ASSIGN_WORDS : 8, hipMemcpyDeviceToHost, st));   // (the prefixes: written by the cost kernel alone)
     HITE_CHECK(ctx, hipStreamSynchronize(st));
-    const int64_t block_strips = S->h_pin[slot];
+    const int64_t block_strips = pin[0];
     if (lanes) {
-        const int64_t v = S->h_pin[slot + 1] * 64, vt = S->h_pin[slot + 2] * 64;
+        const int64_t v = pin[1] * 64, vt = pin[2] * 64;
         *n_long = v < cnt ? v : cnt;
         if (n_long_tb) *n_long_tb = vt < cnt ? vt : cnt;
     }
     char *region;
     ACHK(aalloc(ctx, S->arena, (size_t)block_strips * AL_RECB + 256, &region));
-    hipLaunchKernelGGL(align_assign_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, list, boff, region, rec);
+    hipLaunchKernelGGL(align_assign_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, list, L.boff, region, W.rec);
+    return HITE_OK;
+}
+
+// Runs what `enqueue(side stream)` launches on the high-priority stream, beside what the caller enqueues on `st` next: the side
+// stream starts where `st` stands now, and the launches are the profiler's stage `stage``tag`.  `st` goes on alone until
+// align_side_join makes it wait for them (one side run at a time: the next one records the same events).
+template <typename F>
+static int align_side(hite_ctx *ctx, AlignState *S, hipStream_t st, const char *stage, const char *tag, F enqueue) {
+    char name[40];
+    HITE_CHECK(ctx, hipEventRecord(S->ev_fork, st));
+    HITE_CHECK(ctx, hipStreamWaitEvent(S->st2, S->ev_fork, 0));
+    snprintf(name, sizeof name, "%s%s", stage, tag);
+    const int tk = hite_prof_begin(ctx, name, S->st2);
+    enqueue(S->st2);
+    hite_prof_end(ctx, tk, S->st2);
+    HITE_CHECK(ctx, hipEventRecord(S->ev_join, S->st2));
+    return HITE_OK;
+}
+static int align_side_join(hite_ctx *ctx, AlignState *S, hipStream_t st) { HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev_join, 0)); return HITE_OK; }
+
+// the fall-back on `s`: the 64-word forward pass over the `cnt` pairs of `list` (tcols column records), then the traceback in the
+// form the context's switch names
+static int align_fallback(hite_ctx *ctx, AlignState *S, AlignArgs &P, const int32_t *list, int64_t cnt, int64_t tcols, hipStream_t s) {
+    ACHK(aalloc(ctx, S->arena, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
+    ACHK(aalloc(ctx, S->arena, (size_t)tcols + 16, &P.fullt));
+    hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, s, P, list, (int)cnt);
+    if (hite_sw(ctx, HITE_SW_WIDE_TB_RUNS)) hipLaunchKernelGGL(align_wide_tb_runs_kernel, dim3((unsigned)cnt), dim3(64), 0, s, P, list, (int)cnt);
+    else hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, s, P, list, (int)cnt);
     return HITE_OK;
 }
 
@@ -1921,100 +2037,56 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
     Arena &A = S->arena;
     ACHK(arena_reset(ctx, A, true));
     const int cap = S->exact_cap;
+    if (!tag) tag = "";
     AlignArgs P;
     memset(&P, 0, sizeof P);
     P.win = d_win; P.win_off = d_win_off; P.win_len = d_win_len; P.row_first = d_row_first; P.n_cand = n_cand;
     P.ops_base = d_ops_base; P.ops = d_ops;
-    int32_t *row_cand, *strips, *order, *pwords, *flag, *flag2, *cols, *list, *list_esc, *list_fin;
-    unsigned long long *skeys;
-    int64_t *plane_off, *pos, *pos2, *colpos, *scan_tmp, *scan_tmp2, *full_off, *boff, *boff2;
-    int32_t *bk, *bk2;
-    unsigned long long *rec;
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &row_cand));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &strips));
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &skeys));
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &order));
-    Sorter srt;
-    srt.ctx = ctx; srt.st = st; srt.cap = total_rows; srt.hist_n = sorter_hist_elems(total_rows);
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &srt.k2));
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &srt.v2));
-    ACHK(aalloc(ctx, A, (size_t)srt.hist_n, &srt.hist));
-    ACHK(aalloc(ctx, A, (size_t)srt.hist_n + 1, &srt.offs));
-    ACHK(aalloc(ctx, A, (size_t)sorter_tmp_elems(srt.hist_n), &srt.bs));
-    ACHK(aalloc(ctx, A, (size_t)n_cand, &pwords));
-    ACHK(aalloc(ctx, A, (size_t)n_cand + 1, &plane_off));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &rec));
-    ACHK(aalloc(ctx, A, (size_t)total_rows / 64 + 2, &bk));
-    ACHK(aalloc(ctx, A, (size_t)total_rows / 64 + 3, &boff));
-    ACHK(aalloc(ctx, A, (size_t)total_rows / 64 + 2, &bk2));
-    ACHK(aalloc(ctx, A, (size_t)total_rows / 64 + 3, &boff2));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &flag));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &cols));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &list));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &list_esc));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &list_fin));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &flag2));
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &pos2));
-    ACHK(aalloc(ctx, A, (size_t)scan_tmp_elems(total_rows) + 16, &scan_tmp2));
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &pos));
-    ACHK(aalloc(ctx, A, (size_t)total_rows + 1, &colpos));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &full_off));
-    ACHK(aalloc(ctx, A, (size_t)scan_tmp_elems(total_rows > n_cand ? total_rows : n_cand) + 16, &scan_tmp));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &P.U));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &P.kst));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &P.st));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &P.lvl));
-    ACHK(aalloc(ctx, A, (size_t)total_rows, &P.U4));
-    P.row_cand = row_cand; P.full_off = full_off;
+    AlignWs W = {};
+    ACHK(align_ws_alloc(ctx, A, n_cand, total_rows, st, W, P));
+    const ListWs &M = W.main, &D = W.side;
+    const int32_t *order = W.order;
     int tk = hite_prof_begin(ctx, "align_prep", st);
     HITE_CHECK(ctx, hipMemsetAsync(P.st, 0, (size_t)total_rows * 4, st));
     HITE_CHECK(ctx, hipMemsetAsync(P.lvl, 0, (size_t)total_rows * 4, st));
-    hipLaunchKernelGGL(align_rows_kernel, dim3(n_cand), dim3(256), 0, st, n_cand, d_row_first, d_win_len, row_cand, strips, skeys, (unsigned *)order);
+    hipLaunchKernelGGL(align_rows_kernel, dim3(n_cand), dim3(256), 0, st, n_cand, d_row_first, d_win_len, W.row_cand, W.strips, W.skeys, (unsigned *)W.order);
     if (!S->sort_attr) {
         HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rs_scatter_staged_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, RSS_LDS_BYTES));
         S->sort_attr = true;
     }
-    ACHK(sorter_sort(srt, skeys, (unsigned *)order, total_rows, 11));
-    hipLaunchKernelGGL(align_plane_words_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, d_row_first, d_win_len, pwords);
-    ACHK(scan_excl_buf<int32_t>(ctx, scan_tmp, pwords, n_cand, plane_off, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, plane_off + n_cand, 8, hipMemcpyDeviceToDevice, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin, S->d_scal, 8, hipMemcpyDeviceToHost, st));
+    ACHK(sorter_sort(W.srt, W.skeys, (unsigned *)W.order, total_rows, 11));
+    hipLaunchKernelGGL(align_plane_words_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, d_row_first, d_win_len, W.pwords);
+    ACHK(scan_excl_buf<int32_t>(ctx, M.scan_tmp, W.pwords, n_cand, W.plane_off, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + SLOT_PLANE, W.plane_off + n_cand, 8, hipMemcpyDeviceToDevice, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + SLOT_PLANE, S->d_scal + SLOT_PLANE, 8, hipMemcpyDeviceToHost, st));
     int64_t nl4 = 0, nltb = 0;   // the longest pairs (a prefix of `order`): lane-parallel forward pass / traceback
-    ACHK(assign_records(ctx, S, st, order, total_rows, strips, bk, boff, scan_tmp, rec, 1, 4, &nl4, &nltb));     // (synchronises)
-    const int64_t plane_words = S->h_pin[0];
+    ACHK(assign_records(ctx, S, st, W, M, order, total_rows, 4, &nl4, &nltb));     // (synchronises)
+    const int64_t plane_words = S->h_pin[SLOT_PLANE];
     uint4 *planes;
     ACHK(aalloc(ctx, A, (size_t)plane_words + 8, &planes));
-    P.planes = planes; P.plane_off = plane_off; P.rec = rec;
-    hipLaunchKernelGGL(align_planes_kernel, dim3(n_cand), dim3(256), 0, st, n_cand, d_win, d_win_off, d_win_len, d_row_first, plane_off, planes);
+    P.planes = planes;
+    hipLaunchKernelGGL(align_planes_kernel, dim3(n_cand), dim3(256), 0, st, n_cand, d_win, d_win_off, d_win_len, d_row_first, W.plane_off, planes);
     hite_prof_end(ctx, tk, st);
     HITE_CHECK(ctx, hipGetLastError());
     char name[32];
     const int nrows = (int)total_rows;
     // ---- the 4-word band for every pair
-    snprintf(name, sizeof name, "align_fwd4%s", tag ? tag : "");
-    hipStream_t s2 = S->st2;
-    char lname[40];
-    if (getenv("HITE_ALIGN_DEBUG")) fprintf(stderr, "[align%s] rows %d  block-strips %lld  lane-parallel prefix %lld forward, %lld traceback\n", tag ? tag : "", nrows, (long long)S->h_pin[1], (long long)nl4, (long long)nltb);
-    if (nl4 > 0) {               // beside the other pairs, on the high-priority stream: its few wavefronts are the critical path
-        HITE_CHECK(ctx, hipEventRecord(S->ev_fork, st));
-        HITE_CHECK(ctx, hipStreamWaitEvent(s2, S->ev_fork, 0));
-        snprintf(lname, sizeof lname, "align_fwd4_lanes%s", tag ? tag : "");
-        const int tl = hite_prof_begin(ctx, lname, s2);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_lanes_kernel<4>), dim3((unsigned)((nl4 + 15) / 16)), dim3(64), 0, s2, P, order, (int)nl4);
-        hite_prof_end(ctx, tl, s2);
-        HITE_CHECK(ctx, hipEventRecord(S->ev_join, s2));
-    }
+    snprintf(name, sizeof name, "align_fwd4%s", tag);
+    if (S->debug) fprintf(stderr, "[align%s] rows %d  block-strips %lld  lane-parallel prefix %lld forward, %lld traceback\n", tag, nrows, (long long)S->h_pin[SLOT_ASSIGN], (long long)nl4, (long long)nltb);
+    if (nl4 > 0)                 // beside the other pairs, on the high-priority stream: its few wavefronts are the critical path
+        ACHK(align_side(ctx, S, st, "align_fwd4_lanes", tag, [&](hipStream_t s2) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_lanes_kernel<4>), dim3((unsigned)((nl4 + 15) / 16)), dim3(64), 0, s2, P, order, (int)nl4); }));
     if (nrows > nl4) {
         tk = hite_prof_begin(ctx, name, st);
         hipLaunchKernelGGL(align_fwd4_kernel, dim3((unsigned)((nrows - nl4 + 63) / 64)), dim3(64), 0, st, P, order + nl4, (int)(nrows - nl4));
         hite_prof_end(ctx, tk, st);
     }
-    if (nl4 > 0) HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev_join, 0));
+    if (nl4 > 0) ACHK(align_side_join(ctx, S, st));
     // ---- exact mode: wider bands for the pairs without a certificate, on a second stream, beside the traceback of the pairs
     //      whose 4-word run is final (the wider bands have few, long-running waves: alone they leave most SIMDs idle)
-    snprintf(name, sizeof name, "align_tb%s", tag ? tag : "");
+    snprintf(name, sizeof name, "align_tb%s", tag);
     char wname[32];
-    snprintf(wname, sizeof wname, "align_fwd_wide%s", tag ? tag : "");
+    snprintf(wname, sizeof wname, "align_fwd_wide%s", tag);
     int64_t n_esc = 0, n_fin = 0;
     // measured on C3: beside the 8-word level alone the traceback gains nothing (both are issue-bound: 148.8 vs 140.6 ms per step),
     // with the 16-word level (1.5 waves per SIMD, long tail) the overlap saves 10 ms (170 vs 180)
@@ -2023,124 +2095,99 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
         tk = hite_prof_begin(ctx, wname, st);
         for (int level = 8; level <= cap; level *= 2) {
             int64_t cnt = 0;
-            ACHK(build_list(ctx, S, st, total_rows, order, strips, P, 0, level, cap, flag, nullptr, pos, colpos, scan_tmp, list, nullptr, &cnt, nullptr));
+            ACHK(build_list(ctx, S, st, W, M, total_rows, P, 0, level, cap, W.list, &cnt));
             if (cnt == 0) continue;
             int64_t nl8 = 0;
-            ACHK(assign_records(ctx, S, st, list, cnt, strips, bk, boff, scan_tmp, rec, 1, 8, &nl8));
-            if (getenv("HITE_ALIGN_DEBUG")) fprintf(stderr, "[align%s] level %d: pairs %lld  block-strips %lld  lane-parallel prefix %lld\n", tag ? tag : "", level, (long long)cnt, (long long)S->h_pin[1], (long long)nl8);
-            if (nl8 > 0) {
-                HITE_CHECK(ctx, hipEventRecord(S->ev_fork, st));
-                HITE_CHECK(ctx, hipStreamWaitEvent(s2, S->ev_fork, 0));
-                snprintf(lname, sizeof lname, "align_fwd_wide_lanes%s", tag ? tag : "");
-                const int tl = hite_prof_begin(ctx, lname, s2);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_lanes_kernel<8>), dim3((unsigned)((nl8 + 7) / 8)), dim3(64), 0, s2, P, list, (int)nl8);
-                hite_prof_end(ctx, tl, s2);
-                HITE_CHECK(ctx, hipEventRecord(S->ev_join, s2));
-            }
+            ACHK(assign_records(ctx, S, st, W, M, W.list, cnt, 8, &nl8));
+            if (S->debug) fprintf(stderr, "[align%s] level %d: pairs %lld  block-strips %lld  lane-parallel prefix %lld\n", tag, level, (long long)cnt, (long long)S->h_pin[SLOT_ASSIGN], (long long)nl8);
+            if (nl8 > 0)
+                ACHK(align_side(ctx, S, st, "align_fwd_wide_lanes", tag, [&](hipStream_t s2) {
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_lanes_kernel<8>), dim3((unsigned)((nl8 + 7) / 8)), dim3(64), 0, s2, P, W.list, (int)nl8); }));
             if (cnt > nl8)
-                hipLaunchKernelGGL(align_fwd8_pair_kernel, dim3((unsigned)((cnt - nl8 + 31) / 32)), dim3(64), 0, st, P, list + nl8, (int)(cnt - nl8));
-            if (nl8 > 0) HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev_join, 0));
+                hipLaunchKernelGGL(align_fwd8_pair_kernel, dim3((unsigned)((cnt - nl8 + 31) / 32)), dim3(64), 0, st, P, W.list + nl8, (int)(cnt - nl8));
+            if (nl8 > 0) ACHK(align_side_join(ctx, S, st));
         }
         hite_prof_end(ctx, tk, st);
     }
     if (overlap) {
-        ACHK(build_list(ctx, S, st, total_rows, order, strips, P, 2, 0, cap, flag, nullptr, pos, colpos, scan_tmp, list_esc, nullptr, &n_esc, nullptr));
-        if (n_esc > 0)
-            ACHK(build_list(ctx, S, st, total_rows, order, strips, P, 3, 0, cap, flag, nullptr, pos, colpos, scan_tmp, list_fin, nullptr, &n_fin, nullptr));
+        ACHK(build_list(ctx, S, st, W, M, total_rows, P, 2, 0, cap, W.list_esc, &n_esc));
+        if (n_esc > 0) ACHK(build_list(ctx, S, st, W, M, total_rows, P, 3, 0, cap, W.list_fin, &n_fin));
     }
     if (n_esc > 0) {
+        // no fork event here: the side stream's lists are built with host synchronisations, after those of `st` above
+        hipStream_t s2 = S->st2;
         if (n_fin > 0) {
             tk = hite_prof_begin(ctx, name, st);
-            hipLaunchKernelGGL(align_tb_kernel, dim3((unsigned)((n_fin + 63) / 64)), dim3(64), 0, st, P, list_fin, (int)n_fin);
+            hipLaunchKernelGGL(align_tb_kernel, dim3((unsigned)((n_fin + 63) / 64)), dim3(64), 0, st, P, W.list_fin, (int)n_fin);
             hite_prof_end(ctx, tk, st);
         }
         tk = hite_prof_begin(ctx, wname, s2);
         for (int level = 8; level <= cap; level *= 2) {
             int64_t cnt = 0;
-            ACHK(build_list(ctx, S, s2, total_rows, order, strips, P, 0, level, cap, flag2, nullptr, pos2, colpos, scan_tmp2, list, nullptr, &cnt, nullptr, 8));
+            ACHK(build_list(ctx, S, s2, W, D, total_rows, P, 0, level, cap, W.list, &cnt));
             if (cnt == 0) continue;
-            ACHK(assign_records(ctx, S, s2, list, cnt, strips, bk2, boff2, scan_tmp2, rec, 10));
+            ACHK(assign_records(ctx, S, s2, W, D, W.list, cnt));
             const dim3 grid((unsigned)((cnt + 63) / 64));
-            if (level == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<8>), grid, dim3(64), 0, s2, P, list, (int)cnt);
-            else if (level == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<16>), grid, dim3(64), 0, s2, P, list, (int)cnt);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<32>), grid, dim3(64), 0, s2, P, list, (int)cnt);
+            if (level == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<8>), grid, dim3(64), 0, s2, P, W.list, (int)cnt);
+            else if (level == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<16>), grid, dim3(64), 0, s2, P, W.list, (int)cnt);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<32>), grid, dim3(64), 0, s2, P, W.list, (int)cnt);
         }
         hite_prof_end(ctx, tk, s2);
         HITE_CHECK(ctx, hipEventRecord(S->ev, s2));
         HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev, 0));
         tk = hite_prof_begin(ctx, name, st);
-        hipLaunchKernelGGL(align_tb_kernel, dim3((unsigned)((n_esc + 63) / 64)), dim3(64), 0, st, P, list_esc, (int)n_esc);
+        hipLaunchKernelGGL(align_tb_kernel, dim3((unsigned)((n_esc + 63) / 64)), dim3(64), 0, st, P, W.list_esc, (int)n_esc);
         hite_prof_end(ctx, tk, st);
     } else {
         // ---- traceback on the slice of the run kept
-        if (nltb > 0) {
-            HITE_CHECK(ctx, hipEventRecord(S->ev_fork, st));
-            HITE_CHECK(ctx, hipStreamWaitEvent(s2, S->ev_fork, 0));
-            snprintf(lname, sizeof lname, "align_tb_strips%s", tag ? tag : "");
-            const int tl = hite_prof_begin(ctx, lname, s2);
-            hipLaunchKernelGGL(align_tb_strips_kernel, dim3((unsigned)nltb), dim3(64), 0, s2, P, order, (int)nltb);
-            hite_prof_end(ctx, tl, s2);
-            HITE_CHECK(ctx, hipEventRecord(S->ev_join, s2));
-        }
+        if (nltb > 0)
+            ACHK(align_side(ctx, S, st, "align_tb_strips", tag, [&](hipStream_t s2) {
+                hipLaunchKernelGGL(align_tb_strips_kernel, dim3((unsigned)nltb), dim3(64), 0, s2, P, order, (int)nltb); }));
         if (nrows > nltb) {
             tk = hite_prof_begin(ctx, name, st);
             hipLaunchKernelGGL(align_tb_kernel, dim3((unsigned)((nrows - nltb + 63) / 64)), dim3(64), 0, st, P, order + nltb, (int)(nrows - nltb));
             hite_prof_end(ctx, tk, st);
         }
-        if (nltb > 0) HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev_join, 0));
+        if (nltb > 0) ACHK(align_side_join(ctx, S, st));
     }
     HITE_CHECK(ctx, hipGetLastError());
     // ---- fall-back: the pairs whose path left the slice
-    {
-        int64_t cnt = 0, tcols = 0, dead = 0;
-        ACHK(build_list(ctx, S, st, total_rows, order, strips, P, 1, 0, cap, flag, cols, pos, colpos, scan_tmp, list, full_off, &cnt, &tcols, 0,
-                        fork ? &dead : nullptr));
-        if (cnt > 0 && !fork) {
-            tk = hite_prof_begin(ctx, "align_fallback", st);
-            ACHK(aalloc(ctx, A, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
-            ACHK(aalloc(ctx, A, (size_t)tcols + 16, &P.fullt));
-            hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
-            if (hite_wide_tb_runs_mode(ctx)) hipLaunchKernelGGL(align_wide_tb_runs_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
-            else hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, st, P, list, (int)cnt);
-            hite_prof_end(ctx, tk, st);
-        } else if (cnt > 0) {
-            // ---- the fork.  The fall-back's ~50 wavefronts run on the high-priority stream while the caller works, on `st`, on the
-            // candidates that own none of its rows.  From here to hite_align_finish:
-            //   * the fall-back kernels WRITE the ops rows of the pending candidates' listed rows and P.U, P.kst, P.st, P.lvl of those
-            //     rows, and read `list`, full_off, the planes and the windows.  Nothing on `st` may read or write anything of a pending
-            //     candidate: its ops, its layout words, its entries of the caller's per-candidate outputs, the status of its rows
-            //     (align_dead_mark_kernel and the caller's kernels return at once for a candidate whose pending flag is set);
-            //   * row_dead and cand_flag of the rows that are NOT pending are final now and are written here when any is dead (`dead`,
-            //     counted by the flag kernel and read back with the list's length); align_stats_kernel writes the same values again
-            //     in the finish half, and those of the pending candidates for the first time;
-            //   * fullbuf, fullt, the list and the pending arrays live in this arena: nothing resets it before the finish half (only
-            //     the next hite_align_begin does).
-            int32_t *pending, *pend_list, *pend_count;
-            ACHK(aalloc(ctx, A, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
-            ACHK(aalloc(ctx, A, (size_t)tcols + 16, &P.fullt));
-            ACHK(aalloc(ctx, A, (size_t)n_cand, &pending));
-            ACHK(aalloc(ctx, A, (size_t)cnt, &pend_list));
-            ACHK(aalloc(ctx, A, (size_t)1, &pend_count));
-            HITE_CHECK(ctx, hipEventRecord(S->ev_fork, st));
-            HITE_CHECK(ctx, hipStreamWaitEvent(s2, S->ev_fork, 0));
-            const int tl = hite_prof_begin(ctx, "align_fallback", s2);
-            hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
-            if (hite_wide_tb_runs_mode(ctx)) hipLaunchKernelGGL(align_wide_tb_runs_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
-            else hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, s2, P, list, (int)cnt);
-            hite_prof_end(ctx, tl, s2);
-            HITE_CHECK(ctx, hipEventRecord(S->ev_join, s2));
-            HITE_CHECK(ctx, hipMemsetAsync(pending, 0, (size_t)n_cand * 4, st));
-            HITE_CHECK(ctx, hipMemsetAsync(pend_count, 0, 4, st));
-            hipLaunchKernelGGL(align_pending_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (int)cnt, list, row_cand, pending, pend_list, pend_count);
-            if (dead > 0)
-                hipLaunchKernelGGL(align_dead_mark_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, strips, P, pending,
-                                   d_row_dead, d_cand_flag);
-            S->forked = true;
-            fork->cnt = cnt; fork->dead_before = dead; fork->d_pending = pending; fork->d_pend_list = pend_list; fork->d_pend_count = pend_count;
-        }
+    int64_t cnt = 0, tcols = 0, dead = 0;
+    ACHK(build_list(ctx, S, st, W, M, total_rows, P, 1, 0, cap, W.list, &cnt, &tcols, fork ? &dead : nullptr));
+    if (cnt > 0 && !fork) {
+        tk = hite_prof_begin(ctx, "align_fallback", st);
+        ACHK(align_fallback(ctx, S, P, W.list, cnt, tcols, st));
+        hite_prof_end(ctx, tk, st);
+    } else if (cnt > 0) {
+        // ---- the fork.  The fall-back's ~50 wavefronts run on the high-priority stream while the caller works, on `st`, on the
+        // candidates that own none of its rows.  From here to hite_align_finish, which makes `st` wait for them:
+        //   * the fall-back kernels WRITE the ops rows of the pending candidates' listed rows and P.U, P.kst, P.st, P.lvl of those
+        //     rows, and read `list`, full_off, the planes and the windows.  Nothing on `st` may read or write anything of a pending
+        //     candidate: its ops, its layout words, its entries of the caller's per-candidate outputs, the status of its rows
+        //     (align_dead_mark_kernel and the caller's kernels return at once for a candidate whose pending flag is set);
+        //   * row_dead and cand_flag of the rows that are NOT pending are final now and are written here when any is dead (`dead`,
+        //     counted by the flag kernel and read back with the list's length); align_stats_kernel writes the same values again
+        //     in the finish half, and those of the pending candidates for the first time;
+        //   * fullbuf, fullt, the list and the pending arrays live in this arena: nothing resets it before the finish half (only
+        //     the next hite_align_begin does).
+        int32_t *pending, *pend_list, *pend_count;
+        int err = HITE_OK;
+        ACHK(align_side(ctx, S, st, "align_fallback", "", [&](hipStream_t s2) { err = align_fallback(ctx, S, P, W.list, cnt, tcols, s2); }));
+        ACHK(err);
+        ACHK(aalloc(ctx, A, (size_t)n_cand, &pending));
+        ACHK(aalloc(ctx, A, (size_t)cnt, &pend_list));
+        ACHK(aalloc(ctx, A, (size_t)1, &pend_count));
+        HITE_CHECK(ctx, hipMemsetAsync(pending, 0, (size_t)n_cand * 4, st));
+        HITE_CHECK(ctx, hipMemsetAsync(pend_count, 0, 4, st));
+        hipLaunchKernelGGL(align_pending_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (int)cnt, W.list, W.row_cand, pending, pend_list, pend_count);
+        if (dead > 0)
+            hipLaunchKernelGGL(align_dead_mark_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, W.strips, P, pending,
+                               d_row_dead, d_cand_flag);
+        S->forked = true;
+        fork->cnt = cnt; fork->dead_before = dead; fork->d_pending = pending; fork->d_pend_list = pend_list; fork->d_pend_count = pend_count;
     }
     HITE_CHECK(ctx, hipGetLastError());
-    S->P = P; S->total_rows = total_rows; S->strips = strips; S->row_dead = d_row_dead; S->cand_flag = d_cand_flag; S->info = d_info; S->st = st;
+    S->P = P; S->total_rows = total_rows; S->strips = W.strips; S->row_dead = d_row_dead; S->cand_flag = d_cand_flag; S->info = d_info; S->st = st;
     S->open = true;
     return HITE_OK;
 }
@@ -2156,15 +2203,15 @@ int hite_align_finish(hite_ctx *ctx) {
     const int32_t *strips = S->strips;
     int32_t *d_row_dead = S->row_dead, *d_cand_flag = S->cand_flag, *d_info = S->info;
     hipStream_t st = S->st;
-    if (S->forked) HITE_CHECK(ctx, hipStreamWaitEvent(st, S->ev_join, 0));
+    if (S->forked) ACHK(align_side_join(ctx, S, st));
     S->forked = false;
-    HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
+    HITE_CHECK(ctx, hipMemsetAsync(S->d_scal + SLOT_STATS, 0, 8 * SLOT_STATS_WORDS, st));
     hipLaunchKernelGGL(align_stats_kernel, dim3((unsigned)(total_rows + 255 < 1024 * 256 ? (total_rows + 255) / 256 : 1024)), dim3(256), 0, st, total_rows, strips, P, d_row_dead, d_cand_flag,
-                       (unsigned long long *)S->d_scal);
+                       (unsigned long long *)(S->d_scal + SLOT_STATS));
     if (d_info) hipLaunchKernelGGL(align_info_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, P, d_info);
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin, S->d_scal, 56, hipMemcpyDeviceToHost, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + SLOT_STATS, S->d_scal + SLOT_STATS, 56, hipMemcpyDeviceToHost, st));
     HITE_CHECK(ctx, hipStreamSynchronize(st));
-    for (int q = 0; q < 7; q++) S->stats[q] += S->h_pin[q];
+    for (int q = 0; q < 7; q++) S->stats[q] += S->h_pin[SLOT_STATS + q];
     HITE_CHECK(ctx, hipGetLastError());
     return HITE_OK;
 }

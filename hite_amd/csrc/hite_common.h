@@ -6,6 +6,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include "../../include/hite_gpu.h"
+#include "hite_switch.h"
 
 #define HITE_WAVE 64
 #define HITE_BLOCK 256
@@ -69,14 +70,10 @@ struct hite_ctx {
     uint32_t *d_msa_lay;             // layout words of the last sparse star alignment (hite_msa.hip)
     int msa_long;                    // the last star alignment held windows of more than 1 536 bases (the fill's unroll)
     int msa_max_len;                 // its longest window (the tile form's grid)
-    int32_t fill_tiles;              // hite_fill_config_ctx: 1 the tile form of the sparse fill / 0 the per-cell form / -1 the process default
-    int32_t fallback_overlap;        // hite_fallback_overlap_ctx: 1 the fall-back alignment beside the layout of the other candidates / 0 serial / -1 the process default
-    int32_t gather_chunks;           // hite_gather_config_ctx: 1 the window gather in chunks of the destination / 0 a wavefront per row / -1 the process default
-    int32_t wide_tb_runs;            // hite_wide_tb_runs_ctx: 1 the fall-back's traceback by runs of up to 64 steps / 0 a column per step / -1 the process default
+    int32_t sw[HITE_SW_N];           // the tri-state switches (hite_switch.h): 1 / 0 a form, -1 the process default; read with hite_sw
     const int64_t *d_msa_win_off;    // per row of the last star alignment: its window, and where its back pads begin (HITE_IS_ROW_PAD;
     const int32_t *d_msa_win_len;    // layout, fill and the judge's LDS kernels read the rows through these)
     const uint32_t *d_msa_pads;      // per row: pad bytes in front | behind << 16
-    int32_t copy_interval;          // hite_copy_config_ctx: 1 aligned intervals / 0 whole-candidate intervals / -1 the process default
     int32_t *d_contig_rank;         // byte order of "<contig name>:" among the contigs (hite_set_contig_order; NULL: the index)
     // side streams + one fork event and a join event per stream for kernels that run beside each other inside one call (the
     // judge kernels)
@@ -98,8 +95,9 @@ struct hite_ctx {
     int64_t ltrdeep_batch;            // candidates hite_ltr_deep takes at a time ($HITE_LTRDEEP_BATCH; 0: its default)
 };
 void hite_fmea_release(hite_ctx *ctx);
-int hite_fallback_overlap_mode(const hite_ctx *ctx);   // 1 / 0: the context's setting, or the process default (hite_ctx.hip)
-int hite_wide_tb_runs_mode(const hite_ctx *ctx);       // 1 / 0: the same for the form of the fall-back's traceback (hite_ctx.hip; read by hite_align.hip)
+// which form of a switch the context runs (a null context: the process default), and the body of the exported setters
+static inline int hite_sw(const hite_ctx *ctx, HiteSwitch s) { return hite_switch_resolve(ctx ? ctx->sw : nullptr, s); }
+static inline int hite_sw_set(hite_ctx *ctx, HiteSwitch s, int32_t v) { return hite_switch_set(ctx ? ctx->sw : nullptr, s, v) ? HITE_OK : HITE_EINVAL; }
 int hite_aux_streams(hite_ctx *ctx, int k, hipStream_t *st, hipEvent_t *fork_ev, hipEvent_t *join_ev);
 
 // record the time of everything enqueued on `st` between begin and end as stage `name`

@@ -1272,32 +1272,6 @@ static int sorter_from_arena(Sorter &S, hite_ctx *ctx, Arena &A, hipStream_t st,
     return HITE_OK;
 }
 
-// which interval a copy record carries: 1 (default since round 5) = the ALIGNED interval, reference_start + 1 .. reference_end as
-// get_copies_minimap2 reports it (Util.py:8026), the clipped candidate bases beside it; 0 = the interval of the WHOLE candidate
-// (clipped ends extrapolated on the diagonal; rounds 2-4).  Per context (hite_copy_config_ctx); a context that was never
-// configured follows the process default: hite_copy_config, initialised from the environment (HITE_COPY_INTERVAL=aligned | whole).
-static int g_copy_interval = -1;
-static int copy_interval_mode(const hite_ctx *ctx) {
-    if (ctx && ctx->copy_interval >= 0) return ctx->copy_interval;
-    int v = __atomic_load_n(&g_copy_interval, __ATOMIC_RELAXED);
-    if (v < 0) {
-        const char *e = getenv("HITE_COPY_INTERVAL");
-        v = (e && (!strcmp(e, "whole") || !strcmp(e, "0"))) ? 0 : 1;
-        __atomic_store_n(&g_copy_interval, v, __ATOMIC_RELAXED);
-    }
-    return v;
-}
-extern "C" int hite_copy_config(int32_t aligned_interval) {
-    if (aligned_interval < -1 || aligned_interval > 1) return HITE_EINVAL;
-    __atomic_store_n(&g_copy_interval, aligned_interval, __ATOMIC_RELAXED);
-    return HITE_OK;
-}
-extern "C" int hite_copy_config_ctx(hite_ctx *ctx, int32_t aligned_interval) {
-    if (!ctx || aligned_interval < -1 || aligned_interval > 1) return HITE_EINVAL;
-    ctx->copy_interval = aligned_interval;
-    return HITE_OK;
-}
-
 extern "C" void hite_copy_index_release(void *state) {
     CopyState *S = (CopyState *)state;
     if (!S) return;
@@ -1708,10 +1682,10 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
         unsigned long long want_blocks = (chcap + 255ull) / 256ull;
         const unsigned cblocks = (unsigned)(want_blocks < 8192ull ? (want_blocks ? want_blocks : 1ull) : 8192ull);
         hipLaunchKernelGGL(chain_copy_kernel<false>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_tab, x_i, x_t, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, per_cand,
-                           (const int64_t *)nullptr, copy_interval_mode(ctx));
+                           (const int64_t *)nullptr, hite_sw(ctx, HITE_SW_COPY_INTERVAL));
         CCHK(scan_excl_buf<int32_t>(ctx, bs3, per_cand, n_cand, cstart, st));
         hipLaunchKernelGGL(chain_copy_kernel<true>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_tab, x_i, x_t, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, fill,
-                           (const int64_t *)cstart, copy_interval_mode(ctx));
+                           (const int64_t *)cstart, hite_sw(ctx, HITE_SW_COPY_INTERVAL));
     }
     hite_prof_end(ctx, tk_cluster_copy_kernel, st);
     hipLaunchKernelGGL(cap300_kernel, CGRID((int64_t)n_cand), 0, st, n_cand, per_cand, per_cand300);

@@ -24,41 +24,25 @@ extern "C" int hite_ctx_create(int device_id, hite_ctx **out) {
     hite_ctx *c = (hite_ctx *)calloc(1, sizeof(hite_ctx));
     if (!c) return HITE_ENOMEM;
     c->device = device_id;
-    c->copy_interval = -1;
-    c->fill_tiles = -1;
-    c->gather_chunks = -1;
-    c->fallback_overlap = -1;
-    c->wide_tb_runs = -1;
-    // test knobs of hite_msa_subcluster (hite_subcluster.hip), read here so that two contexts of a process may differ
-    c->subcluster_chunk = HITE_SUBCLUSTER_CHUNK;
-    if (const char *e = getenv("HITE_SUBCLUSTER_CHUNK_ROWS")) {
-        const long v = strtol(e, nullptr, 10);
-        if (v >= 1 && v <= HITE_SUBCLUSTER_CHUNK) c->subcluster_chunk = (int32_t)v;
-    }
-    if (const char *e = getenv("HITE_SUBCLUSTER_BATCH_BYTES")) {
-        const long long v = strtoll(e, nullptr, 10);
-        if (v >= 1) c->subcluster_batch_bytes = (int64_t)v;
-    }
-    if (const char *e = getenv("HITE_FRAMECLUSTER_BATCH_BYTES")) {      // test knob of hite_frame_cluster (hite_framecluster.hip)
-        const long long v = strtoll(e, nullptr, 10);
-        if (v >= 1 && v <= ((long long)1 << 30)) c->framecluster_batch_bytes = (int64_t)v;
-    }
-    if (const char *e = getenv("HITE_PAIRHSP_BATCH_PAIRS")) {           // test knob of hite_pair_hsps (hite_pairhsp.hip)
-        const long long v = strtoll(e, nullptr, 10);
-        if (v >= 1 && v <= ((long long)1 << 24)) c->pairhsp_batch_pairs = (int64_t)v;
-    }
-    if (const char *e = getenv("HITE_LTRSCAN_BATCH_BYTES")) {           // test knob of hite_ltr_scan (hite_ltrscan.hip)
-        const long long v = strtoll(e, nullptr, 10);
-        if (v >= 1 && v <= ((long long)1 << 30)) c->ltrscan_batch_bytes = (int64_t)v;
-    }
-    if (const char *e = getenv("HITE_ANNOT_BATCH_BYTES")) {             // knob of hite_annotate (hite_annotate.hip)
-        const long long v = strtoll(e, nullptr, 10);
-        if (v >= 1 && v <= ((long long)1 << 26)) c->annot_batch_bytes = (int64_t)v;
-    }
-    if (const char *e = getenv("HITE_LTRDEEP_BATCH")) {                 // test knob of hite_ltr_deep (hite_ltrdeep.hip)
-        const long long v = strtoll(e, nullptr, 10);
-        if (v >= 1 && v <= 4096) c->ltrdeep_batch = (int64_t)v;
-    }
+    for (int32_t &v : c->sw) v = -1;
+    // batch knobs of the stages, read here so that two contexts of a process may differ (most are test knobs); a value out of range
+    // is ignored
+    int64_t chunk_rows = HITE_SUBCLUSTER_CHUNK;      // (lands in an int32_t)
+    const struct { const char *env; int64_t *dst; long long lo, hi; } knobs[] = {
+        {"HITE_SUBCLUSTER_CHUNK_ROWS", &chunk_rows, 1, HITE_SUBCLUSTER_CHUNK},            // hite_msa_subcluster (hite_subcluster.hip)
+        {"HITE_SUBCLUSTER_BATCH_BYTES", &c->subcluster_batch_bytes, 1, INT64_MAX},
+        {"HITE_FRAMECLUSTER_BATCH_BYTES", &c->framecluster_batch_bytes, 1, 1LL << 30},    // hite_frame_cluster (hite_framecluster.hip)
+        {"HITE_PAIRHSP_BATCH_PAIRS", &c->pairhsp_batch_pairs, 1, 1LL << 24},              // hite_pair_hsps (hite_pairhsp.hip)
+        {"HITE_LTRSCAN_BATCH_BYTES", &c->ltrscan_batch_bytes, 1, 1LL << 30},              // hite_ltr_scan (hite_ltrscan.hip)
+        {"HITE_ANNOT_BATCH_BYTES", &c->annot_batch_bytes, 1, 1LL << 26},                  // hite_annotate (hite_annotate.hip)
+        {"HITE_LTRDEEP_BATCH", &c->ltrdeep_batch, 1, 4096},                               // hite_ltr_deep (hite_ltrdeep.hip)
+    };
+    for (const auto &k : knobs)
+        if (const char *e = getenv(k.env)) {
+            const long long v = strtoll(e, nullptr, 10);
+            if (v >= k.lo && v <= k.hi) *k.dst = (int64_t)v;
+        }
+    c->subcluster_chunk = (int32_t)chunk_rows;
     if (hipSetDevice(device_id) != hipSuccess) { free(c); return HITE_EHIP; }
     *out = c;
     return HITE_OK;
@@ -99,45 +83,14 @@ extern "C" void hite_ctx_destroy(hite_ctx *c) {
 
 extern "C" const char *hite_last_error(hite_ctx *c) { return c ? c->err : "null ctx"; }
 
-// whether the star alignment runs its fall-back alignment beside the layout of the candidates the fall-back does not touch
-// (hite_msa.hip, star_msa_launch): 1 = beside, 0 = one after the other, -1 = the process default, taken from the environment once
-// (HITE_FALLBACK_OVERLAP=0: one after the other).  Both routes give the same bytes.
-static int g_fallback_overlap = -1;
-int hite_fallback_overlap_mode(const hite_ctx *ctx) {
-    if (ctx->fallback_overlap >= 0) return ctx->fallback_overlap;
-    int v = __atomic_load_n(&g_fallback_overlap, __ATOMIC_RELAXED);
-    if (v < 0) {
-        const char *e = getenv("HITE_FALLBACK_OVERLAP");
-        v = (e && !strcmp(e, "0")) ? 0 : 1;
-        __atomic_store_n(&g_fallback_overlap, v, __ATOMIC_RELAXED);
-    }
-    return v;
-}
-extern "C" int hite_fallback_overlap_ctx(hite_ctx *ctx, int32_t mode) {
-    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
-    ctx->fallback_overlap = mode;
-    return HITE_OK;
-}
-
-// which form of the fall-back's traceback runs (hite_align.hip): 1 = by runs of up to 64 path steps per trip (align_wide_tb_runs_kernel),
-// 0 = a column per step (align_wide_tb_kernel), -1 = the process default, taken from the environment once (HITE_WIDE_TB_RUNS=0: a
-// column per step).  Both forms write the same bytes.
-static int g_wide_tb_runs = -1;
-int hite_wide_tb_runs_mode(const hite_ctx *ctx) {
-    if (ctx->wide_tb_runs >= 0) return ctx->wide_tb_runs;
-    int v = __atomic_load_n(&g_wide_tb_runs, __ATOMIC_RELAXED);
-    if (v < 0) {
-        const char *e = getenv("HITE_WIDE_TB_RUNS");
-        v = (e && !strcmp(e, "0")) ? 0 : 1;
-        __atomic_store_n(&g_wide_tb_runs, v, __ATOMIC_RELAXED);
-    }
-    return v;
-}
-extern "C" int hite_wide_tb_runs_ctx(hite_ctx *ctx, int32_t mode) {
-    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
-    ctx->wide_tb_runs = mode;
-    return HITE_OK;
-}
+// the setters of the tri-state switches (hite_switch.h holds the table, the resolve rule and the range check)
+extern "C" int hite_copy_config(int32_t aligned_interval) { return hite_switch_set_default(HITE_SW_COPY_INTERVAL, aligned_interval) ? HITE_OK : HITE_EINVAL; }
+extern "C" int hite_copy_config_ctx(hite_ctx *ctx, int32_t aligned_interval) { return hite_sw_set(ctx, HITE_SW_COPY_INTERVAL, aligned_interval); }
+extern "C" int hite_fill_config_ctx(hite_ctx *ctx, int32_t mode) { return hite_sw_set(ctx, HITE_SW_FILL_TILES, mode); }
+extern "C" int hite_gather_config_ctx(hite_ctx *ctx, int32_t mode) { return hite_sw_set(ctx, HITE_SW_GATHER_CHUNKS, mode); }
+extern "C" int hite_gather_mode_ctx(hite_ctx *ctx) { return ctx ? hite_sw(ctx, HITE_SW_GATHER_CHUNKS) : HITE_EINVAL; }
+extern "C" int hite_fallback_overlap_ctx(hite_ctx *ctx, int32_t mode) { return hite_sw_set(ctx, HITE_SW_FALLBACK_OVERLAP, mode); }
+extern "C" int hite_wide_tb_runs_ctx(hite_ctx *ctx, int32_t mode) { return hite_sw_set(ctx, HITE_SW_WIDE_TB_RUNS, mode); }
 
 // Byte order of the contig NAMES (each followed by ':'): the rows of an alignment are named "<contig>:<start>-<end>(<strand>)" and
 // tools/ready_for_MSA.sh breaks length ties by name (hite_pipeline.hip, select_rows_kernel).  rank[i] = position of contig i in

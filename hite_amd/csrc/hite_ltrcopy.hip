@@ -291,17 +291,17 @@ extern "C" int hite_ltr_copy_support(hite_ctx *ctx, void **state_io, int32_t n_e
         if (!lc_build_buckets(n_std, std_contig, std_start, std_end, ctx->n_contigs, contig_len.data(), overlap_threshold, segment_len, &B))
             return HITE_EINVAL;
         HITE_CHECK(ctx, hipSetDevice(ctx->device));
-        const int32_t mode = ctx->copy_interval;       // the rule reads aligned intervals and their clips, whatever the context is set to
-        ctx->copy_interval = 1;
+        const int32_t mode = ctx->sw[HITE_SW_COPY_INTERVAL];       // the rule reads aligned intervals and their clips, whatever the context is set to
+        ctx->sw[HITE_SW_COPY_INTERVAL] = 1;
         int rc;
         try {
             rc = lc_fused(ctx, state_io, n_el, el, el_off, B, full_length_coverage, overlap_threshold, segment_len, cap, out_first, out_contig,
                           out_start1, out_end1, n_out, stats);
         } catch (...) {
-            ctx->copy_interval = mode;
+            ctx->sw[HITE_SW_COPY_INTERVAL] = mode;
             throw;
         }
-        ctx->copy_interval = mode;
+        ctx->sw[HITE_SW_COPY_INTERVAL] = mode;
         return rc;
     } catch (const std::bad_alloc &) {
         return HITE_ENOMEM;

@@ -667,7 +667,7 @@ static int star_msa_launch(hite_ctx *ctx, int32_t n, const uint8_t *d_win, const
     HiteAlignFork F;
     memset(&F, 0, sizeof F);
     rc = hite_align_begin(ctx, n, d_win, d_win_off, d_win_len, d_row_first, total_rows, d_ops_base, (uint16_t *)opsb, row_dead, cand_flag, d_info,
-                          max_win_len > 1000 ? "_long" : "_short", st, hite_fallback_overlap_mode(ctx) ? &F : nullptr);
+                          max_win_len > 1000 ? "_long" : "_short", st, hite_sw(ctx, HITE_SW_FALLBACK_OVERLAP) ? &F : nullptr);
     if (rc) return rc;
     const bool forked = F.cnt > 0;
     if (!forked) {
@@ -768,24 +768,6 @@ extern "C" int hite_star_msa_sparse_dev(hite_ctx *ctx, int32_t n, const uint8_t 
                            d_cols_out, d_status, d_new_cols, d_last_extra, d_rows_out, nullptr, stream);
 }
 
-// which form of the sparse fill a context runs: 1 = the tile form (the default), 0 = the per-cell form, -1 = the process default,
-// taken from the environment once (HITE_FILL_TILES=0: the per-cell form)
-static int g_fill_tiles = -1;
-static int fill_tiles_mode(const hite_ctx *ctx) {
-    if (ctx->fill_tiles >= 0) return ctx->fill_tiles;
-    int v = __atomic_load_n(&g_fill_tiles, __ATOMIC_RELAXED);
-    if (v < 0) {
-        const char *e = getenv("HITE_FILL_TILES");
-        v = (e && !strcmp(e, "0")) ? 0 : 1;
-        __atomic_store_n(&g_fill_tiles, v, __ATOMIC_RELAXED);
-    }
-    return v;
-}
-extern "C" int hite_fill_config_ctx(hite_ctx *ctx, int32_t mode) {
-    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
-    ctx->fill_tiles = mode;
-    return HITE_OK;
-}
 extern "C" int hite_fill_tile_limits(int32_t out[4]) {
     if (!out) return HITE_EINVAL;
     out[0] = FT_T; out[1] = FT_SLOT; out[2] = FT_ROWS; out[3] = FT_GRID_Z;
@@ -828,7 +810,7 @@ extern "C" int hite_star_msa_fill_sparse_dev(hite_ctx *ctx, int32_t n, const uin
     // walks all rows, layout words once per tile, 16-byte loads and stores, ops two rows and the window range one row ahead:
     // 0.97 + 3.25 ms where the per-cell form above takes 1.68 + 4.96 (profiles/r14_fill_tiles.txt); it is the default.
     // hite_fill_config_ctx / HITE_FILL_TILES=0 select the per-cell form.
-    if (fill_tiles_mode(ctx) && ctx->msa_max_len > 0)
+    if (hite_sw(ctx, HITE_SW_FILL_TILES) && ctx->msa_max_len > 0)
         hipLaunchKernelGGL(star_fill_tile_kernel, dim3(n, ctx->msa_max_len / FT_T + 1, FT_GRID_Z), dim3(64 * FT_ROWS), 0, (hipStream_t)stream, Q);
     else if (ctx->msa_long) hipLaunchKernelGGL(HIP_KERNEL_NAME(star_fill_sparse_kernel<FILL_U_LONG>), dim3(n, 4), dim3(256), 0, (hipStream_t)stream, Q);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(star_fill_sparse_kernel<FILL_U_SHORT>), dim3(n, 4), dim3(256), 0, (hipStream_t)stream, Q);

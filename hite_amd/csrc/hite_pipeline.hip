@@ -332,24 +332,6 @@ __global__ void __launch_bounds__(256) row_gather_kernel(const uint32_t *__restr
 }
 
 // ---- the gather in chunks of the destination (the default; HITE_GATHER_CHUNKS=0 / hite_gather_config_ctx: the kernel above) ----
-// which form a context runs: 1 = chunks, 0 = a wavefront per row, -1 = the process default, taken from the environment once
-static int g_gather_chunks = -1;
-static int gather_chunks_mode(const hite_ctx *ctx) {
-    if (ctx->gather_chunks >= 0) return ctx->gather_chunks;
-    int v = __atomic_load_n(&g_gather_chunks, __ATOMIC_RELAXED);
-    if (v < 0) {
-        const char *e = getenv("HITE_GATHER_CHUNKS");
-        v = (e && !strcmp(e, "0")) ? 0 : 1;
-        __atomic_store_n(&g_gather_chunks, v, __ATOMIC_RELAXED);
-    }
-    return v;
-}
-extern "C" int hite_gather_config_ctx(hite_ctx *ctx, int32_t mode) {
-    if (!ctx || mode < -1 || mode > 1) return HITE_EINVAL;
-    ctx->gather_chunks = mode;
-    return HITE_OK;
-}
-extern "C" int hite_gather_mode_ctx(hite_ctx *ctx) { return ctx ? gather_chunks_mode(ctx) : HITE_EINVAL; }
 // item = (row, run of up to GR_ITEM_CHUNKS chunks of its slot); item_start = the scan of the rows' item counts
 __global__ void gather_items_kernel(int64_t nrows_total, const int64_t *__restrict__ item_start, uint2 *__restrict__ items) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -631,7 +613,7 @@ static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_
     ACHK(arena_alloc(ctx, T, (size_t)total_rows, &p)); row_trunc = (uint8_t *)p;
     int32_t *row_cp0 = nullptr;
     if (d_clip) { ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_cp0 = (int32_t *)p; }
-    const bool chunks = gather_chunks_mode(ctx) != 0;
+    const bool chunks = hite_sw(ctx, HITE_SW_GATHER_CHUNKS) != 0;
     GatherRow *desc = nullptr;
     int32_t *row_items = nullptr;
     int64_t *item_start = nullptr;
