@@ -1857,16 +1857,6 @@ extern "C" int hite_align_stats(hite_ctx *ctx, int64_t *out8, int32_t reset) {
     return HITE_OK;
 }
 
-#define ACHK(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
-
-template <typename T>
-static int aalloc(hite_ctx *ctx, Arena &A, size_t count, T **out) {
-    void *p = nullptr;
-    int rc = arena_alloc(ctx, A, count * sizeof(T), &p);
-    *out = (T *)p;
-    return rc;
-}
-
 // ---- the arrays of a call: all from the arena, which hite_align_begin resets ----
 // what build_list and assign_records work in, and their words of d_scal / h_pin: a set per stream, so that the side stream
 // builds its lists while `st` works
@@ -1891,40 +1881,23 @@ static int align_ws_alloc(hite_ctx *ctx, Arena &A, int32_t n_cand, int64_t total
     Sorter &srt = W.srt;
     ListWs &M = W.main, &D = W.side;
     M.slot_list = SLOT_LIST; M.slot_assign = SLOT_ASSIGN; D.slot_list = SLOT_LIST_SIDE; D.slot_assign = SLOT_ASSIGN_SIDE;
-    ACHK(aalloc(ctx, A, rows, &W.row_cand));
-    ACHK(aalloc(ctx, A, rows, &W.strips));
-    ACHK(aalloc(ctx, A, rows + 1, &W.skeys));
-    ACHK(aalloc(ctx, A, rows + 1, &W.order));
-    srt.ctx = ctx; srt.st = st; srt.cap = total_rows; srt.hist_n = sorter_hist_elems(total_rows);
-    ACHK(aalloc(ctx, A, rows + 1, &srt.k2));
-    ACHK(aalloc(ctx, A, rows + 1, &srt.v2));
-    ACHK(aalloc(ctx, A, (size_t)srt.hist_n, &srt.hist));
-    ACHK(aalloc(ctx, A, (size_t)srt.hist_n + 1, &srt.offs));
-    ACHK(aalloc(ctx, A, (size_t)sorter_tmp_elems(srt.hist_n), &srt.bs));
-    ACHK(aalloc(ctx, A, (size_t)n_cand, &W.pwords));
-    ACHK(aalloc(ctx, A, (size_t)n_cand + 1, &W.plane_off));
-    ACHK(aalloc(ctx, A, rows, &W.rec));
-    ACHK(aalloc(ctx, A, rows / 64 + 2, &M.bk));
-    ACHK(aalloc(ctx, A, rows / 64 + 3, &M.boff));
-    ACHK(aalloc(ctx, A, rows / 64 + 2, &D.bk));
-    ACHK(aalloc(ctx, A, rows / 64 + 3, &D.boff));
-    ACHK(aalloc(ctx, A, rows, &M.flag));
-    ACHK(aalloc(ctx, A, rows, &M.cols));
-    ACHK(aalloc(ctx, A, rows, &W.list));
-    ACHK(aalloc(ctx, A, rows, &W.list_esc));
-    ACHK(aalloc(ctx, A, rows, &W.list_fin));
-    ACHK(aalloc(ctx, A, rows, &D.flag));
-    ACHK(aalloc(ctx, A, rows + 1, &D.pos));
-    ACHK(aalloc(ctx, A, (size_t)scan_tmp_elems(total_rows) + 16, &D.scan_tmp));
-    ACHK(aalloc(ctx, A, rows + 1, &M.pos));
-    ACHK(aalloc(ctx, A, rows + 1, &M.colpos));
-    ACHK(aalloc(ctx, A, rows, &W.full_off));
-    ACHK(aalloc(ctx, A, (size_t)scan_tmp_elems(total_rows > n_cand ? total_rows : n_cand) + 16, &M.scan_tmp));
-    ACHK(aalloc(ctx, A, rows, &P.U));
-    ACHK(aalloc(ctx, A, rows, &P.kst));
-    ACHK(aalloc(ctx, A, rows, &P.st));
-    ACHK(aalloc(ctx, A, rows, &P.lvl));
-    ACHK(aalloc(ctx, A, rows, &P.U4));
+    HITE_TRY(arena_get(ctx, A, rows, &W.row_cand, &W.strips));
+    HITE_TRY(arena_get(ctx, A, rows + 1, &W.skeys, &W.order));
+    HITE_TRY(sorter_from_arena(srt, ctx, A, st, total_rows));
+    HITE_TRY(arena_get(ctx, A, (size_t)n_cand, &W.pwords));
+    HITE_TRY(arena_get(ctx, A, (size_t)n_cand + 1, &W.plane_off));
+    HITE_TRY(arena_get(ctx, A, rows, &W.rec));
+    HITE_TRY(arena_get(ctx, A, rows / 64 + 2, &M.bk));
+    HITE_TRY(arena_get(ctx, A, rows / 64 + 3, &M.boff));
+    HITE_TRY(arena_get(ctx, A, rows / 64 + 2, &D.bk));
+    HITE_TRY(arena_get(ctx, A, rows / 64 + 3, &D.boff));
+    HITE_TRY(arena_get(ctx, A, rows, &M.flag, &M.cols, &W.list, &W.list_esc, &W.list_fin, &D.flag));
+    HITE_TRY(arena_get(ctx, A, rows + 1, &D.pos));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(total_rows) + 16, &D.scan_tmp));
+    HITE_TRY(arena_get(ctx, A, rows + 1, &M.pos, &M.colpos));
+    HITE_TRY(arena_get(ctx, A, rows, &W.full_off));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(total_rows > n_cand ? total_rows : n_cand) + 16, &M.scan_tmp));
+    HITE_TRY(arena_get(ctx, A, rows, &P.U, &P.kst, &P.st, &P.lvl, &P.U4));
     P.row_cand = W.row_cand; P.full_off = W.full_off; P.plane_off = W.plane_off; P.rec = W.rec;
     return HITE_OK;
 }
@@ -1941,8 +1914,8 @@ static int build_list(hite_ctx *ctx, AlignState *S, hipStream_t st, const AlignW
     if (dead) HITE_CHECK(ctx, hipMemsetAsync(scal + 2, 0, 8, st));
     hipLaunchKernelGGL(align_flag_kernel, dim3(nb), dim3(256), 0, st, nrows, W.order, W.strips, P, what, level, cap, L.flag, cols,
                        dead ? (unsigned long long *)(scal + 2) : nullptr);
-    ACHK(scan_excl_buf<int32_t>(ctx, L.scan_tmp, L.flag, nrows, L.pos, st));
-    if (cols) ACHK(scan_excl_buf<int32_t>(ctx, L.scan_tmp, cols, nrows, L.colpos, st));
+    HITE_TRY(scan_excl_buf<int32_t>(ctx, L.scan_tmp, L.flag, nrows, L.pos, st));
+    if (cols) HITE_TRY(scan_excl_buf<int32_t>(ctx, L.scan_tmp, cols, nrows, L.colpos, st));
     hipLaunchKernelGGL(align_compact_kernel, dim3(nb), dim3(256), 0, st, nrows, W.order, L.flag, L.pos, list, cols ? L.colpos : nullptr,
                        cols ? W.full_off : nullptr, P.st);
     HITE_CHECK(ctx, hipMemcpyAsync(scal, L.pos + nrows, 8, hipMemcpyDeviceToDevice, st));
@@ -1965,7 +1938,7 @@ static int assign_records(hite_ctx *ctx, AlignState *S, hipStream_t st, const Al
     const int64_t nb = (cnt + 63) / 64;
     int64_t *scal = S->d_scal + L.slot_assign, *pin = S->h_pin + L.slot_assign;
     hipLaunchKernelGGL(align_blockmax_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, list, W.strips, L.bk);
-    ACHK(scan_excl_buf<int32_t>(ctx, L.scan_tmp, L.bk, nb, L.boff, st));
+    HITE_TRY(scan_excl_buf<int32_t>(ctx, L.scan_tmp, L.bk, nb, L.boff, st));
     HITE_CHECK(ctx, hipMemcpyAsync(scal, L.boff + nb, 8, hipMemcpyDeviceToDevice, st));
     const bool lanes = n_long && S->lanes_min != -2;
     if (lanes) {
@@ -1985,7 +1958,7 @@ static int assign_records(hite_ctx *ctx, AlignState *S, hipStream_t st, const Al
         if (n_long_tb) *n_long_tb = vt < cnt ? vt : cnt;
     }
     char *region;
-    ACHK(aalloc(ctx, S->arena, (size_t)block_strips * AL_RECB + 256, &region));
+    HITE_TRY(arena_get(ctx, S->arena, (size_t)block_strips * AL_RECB + 256, &region));
     hipLaunchKernelGGL(align_assign_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, list, L.boff, region, W.rec);
     return HITE_OK;
 }
@@ -2010,8 +1983,8 @@ static int align_side_join(hite_ctx *ctx, AlignState *S, hipStream_t st) { HITE_
 // the fall-back on `s`: the 64-word forward pass over the `cnt` pairs of `list` (tcols column records), then the traceback in the
 // form the context's switch names
 static int align_fallback(hite_ctx *ctx, AlignState *S, AlignArgs &P, const int32_t *list, int64_t cnt, int64_t tcols, hipStream_t s) {
-    ACHK(aalloc(ctx, S->arena, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
-    ACHK(aalloc(ctx, S->arena, (size_t)tcols + 16, &P.fullt));
+    HITE_TRY(arena_get(ctx, S->arena, (size_t)tcols * 2 * AL_WIDE_NW + 64, &P.fullbuf));
+    HITE_TRY(arena_get(ctx, S->arena, (size_t)tcols + 16, &P.fullt));
     hipLaunchKernelGGL(align_wide_fwd_kernel, dim3((unsigned)cnt), dim3(64), 0, s, P, list, (int)cnt);
     if (hite_sw(ctx, HITE_SW_WIDE_TB_RUNS)) hipLaunchKernelGGL(align_wide_tb_runs_kernel, dim3((unsigned)cnt), dim3(64), 0, s, P, list, (int)cnt);
     else hipLaunchKernelGGL(align_wide_tb_kernel, dim3((unsigned)cnt), dim3(64), 0, s, P, list, (int)cnt);
@@ -2035,7 +2008,7 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
     AlignState *S = align_state(ctx);
     if (!S) return HITE_ENOMEM;
     Arena &A = S->arena;
-    ACHK(arena_reset(ctx, A, true));
+    HITE_TRY(arena_reset(ctx, A, true));
     const int cap = S->exact_cap;
     if (!tag) tag = "";
     AlignArgs P;
@@ -2043,7 +2016,7 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
     P.win = d_win; P.win_off = d_win_off; P.win_len = d_win_len; P.row_first = d_row_first; P.n_cand = n_cand;
     P.ops_base = d_ops_base; P.ops = d_ops;
     AlignWs W = {};
-    ACHK(align_ws_alloc(ctx, A, n_cand, total_rows, st, W, P));
+    HITE_TRY(align_ws_alloc(ctx, A, n_cand, total_rows, st, W, P));
     const ListWs &M = W.main, &D = W.side;
     const int32_t *order = W.order;
     int tk = hite_prof_begin(ctx, "align_prep", st);
@@ -2054,16 +2027,16 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
         HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rs_scatter_staged_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, RSS_LDS_BYTES));
         S->sort_attr = true;
     }
-    ACHK(sorter_sort(W.srt, W.skeys, (unsigned *)W.order, total_rows, 11));
+    HITE_TRY(sorter_sort(W.srt, W.skeys, (unsigned *)W.order, total_rows, 11));
     hipLaunchKernelGGL(align_plane_words_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, d_row_first, d_win_len, W.pwords);
-    ACHK(scan_excl_buf<int32_t>(ctx, M.scan_tmp, W.pwords, n_cand, W.plane_off, st));
+    HITE_TRY(scan_excl_buf<int32_t>(ctx, M.scan_tmp, W.pwords, n_cand, W.plane_off, st));
     HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + SLOT_PLANE, W.plane_off + n_cand, 8, hipMemcpyDeviceToDevice, st));
     HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin + SLOT_PLANE, S->d_scal + SLOT_PLANE, 8, hipMemcpyDeviceToHost, st));
     int64_t nl4 = 0, nltb = 0;   // the longest pairs (a prefix of `order`): lane-parallel forward pass / traceback
-    ACHK(assign_records(ctx, S, st, W, M, order, total_rows, 4, &nl4, &nltb));     // (synchronises)
+    HITE_TRY(assign_records(ctx, S, st, W, M, order, total_rows, 4, &nl4, &nltb));     // (synchronises)
     const int64_t plane_words = S->h_pin[SLOT_PLANE];
     uint4 *planes;
-    ACHK(aalloc(ctx, A, (size_t)plane_words + 8, &planes));
+    HITE_TRY(arena_get(ctx, A, (size_t)plane_words + 8, &planes));
     P.planes = planes;
     hipLaunchKernelGGL(align_planes_kernel, dim3(n_cand), dim3(256), 0, st, n_cand, d_win, d_win_off, d_win_len, d_row_first, W.plane_off, planes);
     hite_prof_end(ctx, tk, st);
@@ -2074,14 +2047,14 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
     snprintf(name, sizeof name, "align_fwd4%s", tag);
     if (S->debug) fprintf(stderr, "[align%s] rows %d  block-strips %lld  lane-parallel prefix %lld forward, %lld traceback\n", tag, nrows, (long long)S->h_pin[SLOT_ASSIGN], (long long)nl4, (long long)nltb);
     if (nl4 > 0)                 // beside the other pairs, on the high-priority stream: its few wavefronts are the critical path
-        ACHK(align_side(ctx, S, st, "align_fwd4_lanes", tag, [&](hipStream_t s2) {
+        HITE_TRY(align_side(ctx, S, st, "align_fwd4_lanes", tag, [&](hipStream_t s2) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_lanes_kernel<4>), dim3((unsigned)((nl4 + 15) / 16)), dim3(64), 0, s2, P, order, (int)nl4); }));
     if (nrows > nl4) {
         tk = hite_prof_begin(ctx, name, st);
         hipLaunchKernelGGL(align_fwd4_kernel, dim3((unsigned)((nrows - nl4 + 63) / 64)), dim3(64), 0, st, P, order + nl4, (int)(nrows - nl4));
         hite_prof_end(ctx, tk, st);
     }
-    if (nl4 > 0) ACHK(align_side_join(ctx, S, st));
+    if (nl4 > 0) HITE_TRY(align_side_join(ctx, S, st));
     // ---- exact mode: wider bands for the pairs without a certificate, on a second stream, beside the traceback of the pairs
     //      whose 4-word run is final (the wider bands have few, long-running waves: alone they leave most SIMDs idle)
     snprintf(name, sizeof name, "align_tb%s", tag);
@@ -2095,23 +2068,23 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
         tk = hite_prof_begin(ctx, wname, st);
         for (int level = 8; level <= cap; level *= 2) {
             int64_t cnt = 0;
-            ACHK(build_list(ctx, S, st, W, M, total_rows, P, 0, level, cap, W.list, &cnt));
+            HITE_TRY(build_list(ctx, S, st, W, M, total_rows, P, 0, level, cap, W.list, &cnt));
             if (cnt == 0) continue;
             int64_t nl8 = 0;
-            ACHK(assign_records(ctx, S, st, W, M, W.list, cnt, 8, &nl8));
+            HITE_TRY(assign_records(ctx, S, st, W, M, W.list, cnt, 8, &nl8));
             if (S->debug) fprintf(stderr, "[align%s] level %d: pairs %lld  block-strips %lld  lane-parallel prefix %lld\n", tag, level, (long long)cnt, (long long)S->h_pin[SLOT_ASSIGN], (long long)nl8);
             if (nl8 > 0)
-                ACHK(align_side(ctx, S, st, "align_fwd_wide_lanes", tag, [&](hipStream_t s2) {
+                HITE_TRY(align_side(ctx, S, st, "align_fwd_wide_lanes", tag, [&](hipStream_t s2) {
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_lanes_kernel<8>), dim3((unsigned)((nl8 + 7) / 8)), dim3(64), 0, s2, P, W.list, (int)nl8); }));
             if (cnt > nl8)
                 hipLaunchKernelGGL(align_fwd8_pair_kernel, dim3((unsigned)((cnt - nl8 + 31) / 32)), dim3(64), 0, st, P, W.list + nl8, (int)(cnt - nl8));
-            if (nl8 > 0) ACHK(align_side_join(ctx, S, st));
+            if (nl8 > 0) HITE_TRY(align_side_join(ctx, S, st));
         }
         hite_prof_end(ctx, tk, st);
     }
     if (overlap) {
-        ACHK(build_list(ctx, S, st, W, M, total_rows, P, 2, 0, cap, W.list_esc, &n_esc));
-        if (n_esc > 0) ACHK(build_list(ctx, S, st, W, M, total_rows, P, 3, 0, cap, W.list_fin, &n_fin));
+        HITE_TRY(build_list(ctx, S, st, W, M, total_rows, P, 2, 0, cap, W.list_esc, &n_esc));
+        if (n_esc > 0) HITE_TRY(build_list(ctx, S, st, W, M, total_rows, P, 3, 0, cap, W.list_fin, &n_fin));
     }
     if (n_esc > 0) {
         // no fork event here: the side stream's lists are built with host synchronisations, after those of `st` above
@@ -2124,9 +2097,9 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
         tk = hite_prof_begin(ctx, wname, s2);
         for (int level = 8; level <= cap; level *= 2) {
             int64_t cnt = 0;
-            ACHK(build_list(ctx, S, s2, W, D, total_rows, P, 0, level, cap, W.list, &cnt));
+            HITE_TRY(build_list(ctx, S, s2, W, D, total_rows, P, 0, level, cap, W.list, &cnt));
             if (cnt == 0) continue;
-            ACHK(assign_records(ctx, S, s2, W, D, W.list, cnt));
+            HITE_TRY(assign_records(ctx, S, s2, W, D, W.list, cnt));
             const dim3 grid((unsigned)((cnt + 63) / 64));
             if (level == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<8>), grid, dim3(64), 0, s2, P, W.list, (int)cnt);
             else if (level == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(align_fwd_kernel<16>), grid, dim3(64), 0, s2, P, W.list, (int)cnt);
@@ -2141,22 +2114,22 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
     } else {
         // ---- traceback on the slice of the run kept
         if (nltb > 0)
-            ACHK(align_side(ctx, S, st, "align_tb_strips", tag, [&](hipStream_t s2) {
+            HITE_TRY(align_side(ctx, S, st, "align_tb_strips", tag, [&](hipStream_t s2) {
                 hipLaunchKernelGGL(align_tb_strips_kernel, dim3((unsigned)nltb), dim3(64), 0, s2, P, order, (int)nltb); }));
         if (nrows > nltb) {
             tk = hite_prof_begin(ctx, name, st);
             hipLaunchKernelGGL(align_tb_kernel, dim3((unsigned)((nrows - nltb + 63) / 64)), dim3(64), 0, st, P, order + nltb, (int)(nrows - nltb));
             hite_prof_end(ctx, tk, st);
         }
-        if (nltb > 0) ACHK(align_side_join(ctx, S, st));
+        if (nltb > 0) HITE_TRY(align_side_join(ctx, S, st));
     }
     HITE_CHECK(ctx, hipGetLastError());
     // ---- fall-back: the pairs whose path left the slice
     int64_t cnt = 0, tcols = 0, dead = 0;
-    ACHK(build_list(ctx, S, st, W, M, total_rows, P, 1, 0, cap, W.list, &cnt, &tcols, fork ? &dead : nullptr));
+    HITE_TRY(build_list(ctx, S, st, W, M, total_rows, P, 1, 0, cap, W.list, &cnt, &tcols, fork ? &dead : nullptr));
     if (cnt > 0 && !fork) {
         tk = hite_prof_begin(ctx, "align_fallback", st);
-        ACHK(align_fallback(ctx, S, P, W.list, cnt, tcols, st));
+        HITE_TRY(align_fallback(ctx, S, P, W.list, cnt, tcols, st));
         hite_prof_end(ctx, tk, st);
     } else if (cnt > 0) {
         // ---- the fork.  The fall-back's ~50 wavefronts run on the high-priority stream while the caller works, on `st`, on the
@@ -2172,11 +2145,11 @@ int hite_align_begin(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const 
         //     the next hite_align_begin does).
         int32_t *pending, *pend_list, *pend_count;
         int err = HITE_OK;
-        ACHK(align_side(ctx, S, st, "align_fallback", "", [&](hipStream_t s2) { err = align_fallback(ctx, S, P, W.list, cnt, tcols, s2); }));
-        ACHK(err);
-        ACHK(aalloc(ctx, A, (size_t)n_cand, &pending));
-        ACHK(aalloc(ctx, A, (size_t)cnt, &pend_list));
-        ACHK(aalloc(ctx, A, (size_t)1, &pend_count));
+        HITE_TRY(align_side(ctx, S, st, "align_fallback", "", [&](hipStream_t s2) { err = align_fallback(ctx, S, P, W.list, cnt, tcols, s2); }));
+        HITE_TRY(err);
+        HITE_TRY(arena_get(ctx, A, (size_t)n_cand, &pending));
+        HITE_TRY(arena_get(ctx, A, (size_t)cnt, &pend_list));
+        HITE_TRY(arena_get(ctx, A, (size_t)1, &pend_count));
         HITE_CHECK(ctx, hipMemsetAsync(pending, 0, (size_t)n_cand * 4, st));
         HITE_CHECK(ctx, hipMemsetAsync(pend_count, 0, 4, st));
         hipLaunchKernelGGL(align_pending_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (int)cnt, W.list, W.row_cand, pending, pend_list, pend_count);
@@ -2203,7 +2176,7 @@ int hite_align_finish(hite_ctx *ctx) {
     const int32_t *strips = S->strips;
     int32_t *d_row_dead = S->row_dead, *d_cand_flag = S->cand_flag, *d_info = S->info;
     hipStream_t st = S->st;
-    if (S->forked) ACHK(align_side_join(ctx, S, st));
+    if (S->forked) HITE_TRY(align_side_join(ctx, S, st));
     S->forked = false;
     HITE_CHECK(ctx, hipMemsetAsync(S->d_scal + SLOT_STATS, 0, 8 * SLOT_STATS_WORDS, st));
     hipLaunchKernelGGL(align_stats_kernel, dim3((unsigned)(total_rows + 255 < 1024 * 256 ? (total_rows + 255) / 256 : 1024)), dim3(256), 0, st, total_rows, strips, P, d_row_dead, d_cand_flag,
@@ -2219,7 +2192,7 @@ int hite_align_finish(hite_ctx *ctx) {
 int hite_align_run(hite_ctx *ctx, int32_t n_cand, const uint8_t *d_win, const int64_t *d_win_off, const int32_t *d_win_len,
                    const int32_t *d_row_first, int64_t total_rows, const int64_t *d_ops_base, uint16_t *d_ops,
                    int32_t *d_row_dead, int32_t *d_cand_flag, int32_t *d_info, const char *tag, hipStream_t st) {
-    ACHK(hite_align_begin(ctx, n_cand, d_win, d_win_off, d_win_len, d_row_first, total_rows, d_ops_base, d_ops, d_row_dead, d_cand_flag, d_info,
+    HITE_TRY(hite_align_begin(ctx, n_cand, d_win, d_win_off, d_win_len, d_row_first, total_rows, d_ops_base, d_ops, d_row_dead, d_cand_flag, d_info,
                           tag, st, nullptr));
     return hite_align_finish(ctx);
 }

@@ -7,6 +7,7 @@
 // ---------------------------------------------------------------------------------------------
 // arenas (grow-only, reset per call; no hipMalloc on the steady-state path)
 // ---------------------------------------------------------------------------------------------
+// >>> host_arena (plain host C++: tests/test_host_arena.py compiles this block against stand-ins of the HIP calls)
 struct Arena {
     std::vector<void *> chunks;
     std::vector<size_t> caps;
@@ -36,6 +37,20 @@ static int arena_alloc(hite_ctx *ctx, Arena &a, size_t bytes, void **out) {
     a.off += bytes;
     return HITE_OK;
 }
+// `count` elements of T (the form every caller but the byte allocator of hite_fmea.hip uses)
+template <class T>
+static int arena_get(hite_ctx *ctx, Arena &a, size_t count, T **out) {
+    void *p = nullptr;
+    const int rc = arena_alloc(ctx, a, count * sizeof(T), &p);
+    *out = (T *)p;
+    return rc;
+}
+// several arrays of `count` elements each, allocated in the order given
+template <class T, class... Ts>
+static int arena_get(hite_ctx *ctx, Arena &a, size_t count, T **out, Ts **...more) {
+    const int rc = arena_get(ctx, a, count, out);
+    return rc ? rc : arena_get(ctx, a, count, more...);
+}
 // soft reset: hand the same memory out again (stream order protects the reuse).
 // hard reset (start of a call): if the arena grew into several chunks, replace them by one chunk of
 // the total capacity, so that the steady state never calls hipMalloc.
@@ -62,4 +77,4 @@ static void arena_free(Arena &a) {
     a.caps.clear();
     a.cur = a.off = 0;
 }
-
+// <<< host_arena

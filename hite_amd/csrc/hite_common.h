@@ -115,6 +115,9 @@ void hite_prof_resolve(hite_ctx *ctx);
         }                                                                                             \
     } while (0)
 
+// pass a non-zero return code of x on to the caller
+#define HITE_TRY(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
+
 int hite_scratch_reserve(hite_ctx *ctx, size_t bytes, void **out);
 int hite_scratch2_reserve(hite_ctx *ctx, size_t bytes, void **out);
 

@@ -23,6 +23,7 @@
 #include "hite_scan.h"
 #include "hite_sort.h"
 #include "hite_arena.h"
+#include <type_traits>
 
 #define CK 15
 #define CW 10
@@ -37,6 +38,22 @@
 #define DIRBITS 26
 #define DBIAS 65536ll
 
+// The words of CopyState::pin.  Every stage leaves the total of its scan in CS_TOTAL; the others a copy call counts on the device, in
+// kernels that hold pointers to them: the call zeroes and reads back its CS_WORDS words together
+enum CopySlot {
+    CS_TOTAL = 0,        // total of the last scan (minimizers, hits, clusters, ...; at the end of a copy call: records before the cap)
+    CS_LONGEST = 1,      // cand_minimizer_kernel: bases of the longest candidate
+    CS_TOTAL_CAPPED = 1, // end of a copy call: records after the cap of C_MAXCOPY per candidate
+    CS_CLUSTERS = 2,     // clusters the per-candidate sort found
+    CS_CHAINS_LONG = 4,  // chains with a long end to extend; the sorts' epilogue and chain_list_kernel index the words from here on
+    CS_CHAINS_SHORT = 5, // the other chains
+    CS_TASK_QUEUE = 6,   // tasks the lanes of chain_extend_kernel have taken
+    CS_EXT_COLS = 7,     // columns of the end extension (chain_extend_kernel: the word behind its queue)
+    CS_WORDS = 8
+};
+static_assert(CS_CHAINS_LONG + 3 == CS_EXT_COLS && CS_EXT_COLS < CS_WORDS, "the chain counters: four consecutive words of the read-back");
+static_assert(CS_WORDS <= SCAL_WORDS, "the read-back fits the allocation");
+
 struct CopyState {
     unsigned *idx_hs = nullptr, *idx_pos = nullptr, *dir = nullptr;
     unsigned *idx_t = nullptr;   // rank of every index entry among the minimizers in position order (stage 3.1 walks the seeds in that order)
@@ -47,8 +64,7 @@ struct CopyState {
     Arena build;      // temporaries of the index build
     Arena arena;      // temporaries of one call
     Arena out;        // copy table handed to the caller (valid until the next call)
-    int64_t *h_pin = nullptr;
-    int64_t *d_scal = nullptr;
+    ScalPin pin;      // the scalars of a call: words CopySlot (below)
     const uint32_t *out_clip = nullptr;   // per copy record of the last call (in `out`): candidate bases clipped left | right << 16 (hite_copy_clips_dev)
     int64_t out_n = 0;
     // the minimizer tiles of the last index build (still in the build arena): valid for THIS genome state (hite_ctx::genome_epoch) up to
@@ -1257,20 +1273,26 @@ __global__ void fill_u64_kernel(int64_t n, unsigned long long *__restrict__ p, u
 // host side
 // ---------------------------------------------------------------------------------------------
 #define CGRID(n) dim3((unsigned)((((n) > 0 ? (n) : 1) + 255) / 256)), dim3(256)
-#define CCHK(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
-static int sorter_from_arena(Sorter &S, hite_ctx *ctx, Arena &A, hipStream_t st, int64_t n, bool with_vals = true) {
-    S.ctx = ctx; S.st = st; S.cap = n;
-    S.hist_n = sorter_hist_elems(n);
-    void *p;
-    CCHK(arena_alloc(ctx, A, (size_t)(n + 1) * 8, &p)); S.k2 = (unsigned long long *)p;
-    S.v2 = nullptr;
-    if (with_vals) { CCHK(arena_alloc(ctx, A, (size_t)(n + 1) * 4, &p)); S.v2 = (unsigned *)p; }
-    CCHK(arena_alloc(ctx, A, (size_t)S.hist_n * sizeof(rs_cnt_t), &p)); S.hist = (rs_cnt_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(S.hist_n + 1) * sizeof(rs_off_t), &p)); S.offs = (rs_off_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)sorter_tmp_elems(S.hist_n) * 8, &p)); S.bs = (int64_t *)p;
-    return HITE_OK;
-}
+// The switches of this file (tests and measurements), each with its own rule; read once per process: a test starts a fresh one
+static bool knob_not0(const char *v) { return !(v && *v == '0'); }                     // off only on a leading '0'
+static bool knob_is1(const char *v) { return v && *v == '1'; }                         // on only on a leading '1'
+static bool knob_nonzero(const char *v) { return v && *v && atoi(v) != 0; }            // on when atoi != 0
+static bool knob_unless0(const char *v) { return !(v && *v && atoi(v) == 0); }         // off only when set and atoi == 0
+static int knob_int(const char *v, int dflt) { return v && *v ? atoi(v) : dflt; }      // atoi, with a default
+struct CopyKnobs {
+    bool keep_minimizers = knob_not0(getenv("HITE_KEEP_MINIMIZERS"));    // an index build keeps the tiles of the last one on this genome state
+    bool hits_wide = knob_nonzero(getenv("HITE_HITS_WIDE"));             // the 12-byte hits whatever the sizes
+    bool hit_hist = knob_nonzero(getenv("HITE_HIT_HIST"));               // the first call prints its hits per candidate, by class, to stderr
+    bool hit_segsort = knob_unless0(getenv("HITE_HIT_SEGSORT"));         // the per-candidate sort (off: the global sort and the cluster kernels)
+    int ext_blocks = knob_int(getenv("HITE_EXT_BLOCKS"), 0);             // at most this many blocks of chain_extend_kernel (0: no limit)
+    bool seed_count2 = knob_not0(getenv("HITE_SEED_COUNT2"));            // seed_count2_kernel (off: the run arrays and the thread-per-entry kernel)
+    int seed_place = knob_int(getenv("HITE_SEED_PLACE"), -1);            // the grouped placement of the seed records: 0 never, 1 always, -1 by size
+    int seed_place_lds = knob_int(getenv("HITE_SEED_PLACE_LDS"), 65536); // bytes of LDS seed_place_kernel asks for (it uses none)
+    bool seed_place_cnt = knob_is1(getenv("HITE_SEED_PLACE_CNT"));       // seed_place_kernel scatters the counts beside the records
+    bool seed_pack = knob_not0(getenv("HITE_SEED_PACK"));                // the packed anchors where they fit (off: always the unpacked ones)
+};
+static const CopyKnobs &copy_knobs() { static const CopyKnobs k; return k; }
 
 extern "C" void hite_copy_index_release(void *state) {
     CopyState *S = (CopyState *)state;
@@ -1282,27 +1304,75 @@ extern "C" void hite_copy_index_release(void *state) {
     arena_free(S->build);
     arena_free(S->arena);
     arena_free(S->out);
-    if (S->h_pin) (void)hipHostFree(S->h_pin);
-    if (S->d_scal) (void)hipFree(S->d_scal);
+    S->pin.release();
     delete S;
 }
 
-static int read_back(hite_ctx *ctx, CopyState *S, hipStream_t st, int count) {
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin, S->d_scal, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
-    HITE_CHECK(ctx, hipStreamSynchronize(st));
-    return HITE_OK;
-}
-
-// builds the minimizer index of the packed genome; *state_io receives the index handle
 static int copy_state_get(hite_ctx *ctx, void **state_io, CopyState **out) {
     CopyState *S = (CopyState *)*state_io;
     if (!S) {
-        S = new CopyState();
-        *state_io = S;
-        HITE_CHECK(ctx, hipHostMalloc((void **)&S->h_pin, 64 * sizeof(int64_t)));
-        HITE_CHECK(ctx, hipMalloc((void **)&S->d_scal, 64 * sizeof(int64_t)));
+        *state_io = S = new CopyState();
+        HITE_CHECK(ctx, S->pin.alloc());
     }
     *out = S;
+    return HITE_OK;
+}
+
+// The arrays of one index build, all from the build arena.  Every build on a handle allocates the same things in the same order, so the
+// tiles of the last build are where the new ones go -- unless the arena was rebuilt, which the pointers and the chunk count tell
+struct IndexWs {
+    int64_t G, ntiles; unsigned long long cap;
+    unsigned long long *keys, *stage; unsigned *vals; int32_t *tile_cnt; int64_t *tile_first, *tbs;
+    int32_t *tile_cnt_r = nullptr; unsigned long long *wmask = nullptr;       // restricted build from kept tiles: the filtered counts
+};
+
+// Kept tiles, the decision: the tiles always hold EVERY minimizer (a restricted build filters them afterwards).  Kept from the last build
+// on this genome state, only the tiles a mask has touched since are done again -- window starts [a - K - W - 2, b + 2] of a masked [a, b):
+// a window reads the k-mers of W starts, a k-mer K bases, and a window's record depends on the window before it.  *all: every tile
+// (nothing is kept); otherwise the *nl tiles of *d_list (uploaded here; 0: none)
+static int kept_tiles_dirty(hite_ctx *ctx, CopyState *S, hipStream_t st, const IndexWs &W, bool one_chunk, bool *all, int32_t **d_list,
+                            int64_t *nl) {
+    const bool kept = one_chunk && S->kept_stage == W.stage && S->kept_cnt == W.tile_cnt && S->kept_ctx == ctx && S->kept_G == W.G &&
+                      S->kept_epoch == ctx->genome_epoch && S->kept_log <= ctx->mask_log_n;
+    S->kept_epoch = -1;                       // (void until this build's kernels are queued)
+    *all = !kept; *d_list = nullptr; *nl = 0;
+    if (!kept || S->kept_log >= ctx->mask_log_n) return HITE_OK;
+    std::vector<unsigned char> dirty((size_t)W.ntiles, 0);
+    for (int64_t k = S->kept_log; k < ctx->mask_log_n; k++) {
+        int64_t lo = ctx->mask_log[2 * k] - CK - CW - 2, hi = ctx->mask_log[2 * k + 1] + 2;
+        lo = lo < 0 ? 0 : lo; hi = hi > W.G - 1 ? W.G - 1 : hi;
+        for (int64_t t = lo / GM_TILE; t <= hi / GM_TILE && t < W.ntiles; t++) dirty[(size_t)t] = 1;
+    }
+    std::vector<int32_t> list;
+    for (int64_t t = 0; t < W.ntiles; t++) if (dirty[(size_t)t]) list.push_back((int32_t)t);
+    if (list.empty()) return HITE_OK;
+    HITE_TRY(arena_get(ctx, S->build, list.size(), d_list));
+    HITE_CHECK(ctx, hipMemcpyAsync(*d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
+    HITE_CHECK(ctx, hipStreamSynchronize(st));          // (the list is a local)
+    *nl = (int64_t)list.size();
+    return HITE_OK;
+}
+
+// the minimizer pass over the genome's tiles (all of them, or the ones kept_tiles_dirty names)
+static int index_tile_pass(hite_ctx *ctx, CopyState *S, hipStream_t st, const IndexWs &W, HSet hset, bool one_chunk) {
+    const int64_t blocks = W.ntiles < 1 ? 1 : W.ntiles < 256 * 64 ? W.ntiles : 256 * 64;
+    if (!copy_knobs().keep_minimizers) S->kept_epoch = -1;
+    if (!copy_knobs().keep_minimizers && hset.tab) {
+        hipLaunchKernelGGL(genome_minimizer_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off,
+                           ctx->n_contigs, W.G, W.ntiles, W.stage, W.tile_cnt, hset, (const int32_t *)nullptr);
+        return HITE_OK;
+    }
+    // every minimizer of the tiles: of all of them, or of the listed ones (kept tiles: possibly none)
+    bool all = true; int32_t *d_list = nullptr; int64_t nl = 0;
+    if (copy_knobs().keep_minimizers) HITE_TRY(kept_tiles_dirty(ctx, S, st, W, one_chunk, &all, &d_list, &nl));
+    const int64_t nt = all ? W.ntiles : nl;         // (all: `blocks` of them also for no tile at all -- a grid of 0 is no launch)
+    if (all || nl > 0)
+        hipLaunchKernelGGL(genome_minimizer_kernel<false>, dim3((unsigned)(all || blocks < nl ? blocks : nl)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
+                           ctx->d_contig_off, ctx->n_contigs, W.G, nt, W.stage, W.tile_cnt, HSet{nullptr, nullptr, 0, 0}, (const int32_t *)d_list);
+    if (copy_knobs().keep_minimizers) {
+        S->kept_stage = W.stage; S->kept_cnt = W.tile_cnt; S->kept_ctx = ctx; S->kept_G = W.G;
+        S->kept_epoch = ctx->genome_epoch; S->kept_log = ctx->mask_log_n;
+    }
     return HITE_OK;
 }
 
@@ -1313,125 +1383,70 @@ static int index_build_impl(hite_ctx *ctx, void **state_io, hipStream_t st, HSet
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     // rebuilding on an existing handle (next genome / chunk) keeps its arenas: their growth is the expensive part of a cold call
     CopyState *S;
-    CCHK(copy_state_get(ctx, state_io, &S));
-    S->M = 0;
-    S->restricted = hset.tab != nullptr;
-    const int64_t G = ctx->n_bases;
-    const unsigned long long cap = (unsigned long long)(G * 0.32) + 4096;
-    if ((int64_t)cap > S->idx_cap) {      // the index arrays: grow-only, shared by every genome packed behind this handle
+    HITE_TRY(copy_state_get(ctx, state_io, &S));
+    S->M = 0; S->restricted = hset.tab != nullptr;
+    IndexWs W;
+    W.G = ctx->n_bases; W.cap = (unsigned long long)(W.G * 0.32) + 4096; W.ntiles = (W.G + GM_TILE - 1) / GM_TILE;
+    if ((int64_t)W.cap > S->idx_cap) {      // the index arrays: grow-only, shared by every genome packed behind this handle
         if (S->idx_hs) (void)hipFree(S->idx_hs);
         if (S->idx_pos) (void)hipFree(S->idx_pos);
         if (S->idx_t) (void)hipFree(S->idx_t);
         S->idx_hs = S->idx_pos = S->idx_t = nullptr; S->idx_cap = 0;
-        HITE_CHECK(ctx, hipMalloc((void **)&S->idx_hs, (size_t)(cap + 16) * 4));
-        HITE_CHECK(ctx, hipMalloc((void **)&S->idx_pos, (size_t)(cap + 16) * 4));
-        HITE_CHECK(ctx, hipMalloc((void **)&S->idx_t, (size_t)(cap + 16) * 4));
-        S->idx_cap = (int64_t)cap;
+        HITE_CHECK(ctx, hipMalloc((void **)&S->idx_hs, (size_t)(W.cap + 16) * 4));
+        HITE_CHECK(ctx, hipMalloc((void **)&S->idx_pos, (size_t)(W.cap + 16) * 4));
+        HITE_CHECK(ctx, hipMalloc((void **)&S->idx_t, (size_t)(W.cap + 16) * 4));
+        S->idx_cap = (int64_t)W.cap;
     }
     if (!S->dir) HITE_CHECK(ctx, hipMalloc((void **)&S->dir, (size_t)((1 << DIRBITS) + 2) * 4));
     const bool one_chunk = S->build.chunks.size() == 1;       // (more: the reset below rebuilds the arena, and what it held is gone)
-    CCHK(arena_reset(ctx, S->build, true));
+    HITE_TRY(arena_reset(ctx, S->build, true));
     Arena &B = S->build;
-    void *p;
-    const int64_t ntiles = (G + GM_TILE - 1) / GM_TILE;
-    unsigned long long *keys, *stage;
-    unsigned *vals;
-    int32_t *tile_cnt; int64_t *tile_first, *tbs;
-    // (kept tiles: every build on a handle allocates the same things in the same order, so the tiles of the last build are where the
-    // new ones go -- unless the arena was rebuilt, which the pointers below and the chunk count tell)
-    static const bool keep_on = [] { const char *v = getenv("HITE_KEEP_MINIMIZERS"); return !(v && *v == '0'); }();
-    CCHK(arena_alloc(ctx, B, (size_t)cap * 8, &p)); keys = (unsigned long long *)p;
-    CCHK(arena_alloc(ctx, B, (size_t)cap * 4, &p)); vals = (unsigned *)p;
-    CCHK(arena_alloc(ctx, B, (size_t)(ntiles + 1) * 4, &p)); tile_cnt = (int32_t *)p;
-    CCHK(arena_alloc(ctx, B, (size_t)(ntiles + 2) * 8, &p)); tile_first = (int64_t *)p;
-    CCHK(arena_alloc(ctx, B, (size_t)scan_tmp_elems(ntiles + 1) * 8, &p)); tbs = (int64_t *)p;
-    CCHK(arena_alloc(ctx, B, (size_t)(ntiles > 0 ? ntiles : 1) * GM_TILE * 8, &p)); stage = (unsigned long long *)p;
-    int32_t *tile_cnt_r = nullptr;       // restricted build from kept tiles: the filtered counts
-    unsigned long long *wmask = nullptr;
-    if (keep_on && hset.tab) {
-        CCHK(arena_alloc(ctx, B, (size_t)(ntiles + 1) * 4, &p)); tile_cnt_r = (int32_t *)p;
-        CCHK(arena_alloc(ctx, B, (size_t)(ntiles + 1) * (GM_TILE / 64) * 8, &p)); wmask = (unsigned long long *)p;
+    HITE_TRY(arena_get(ctx, B, (size_t)W.cap, &W.keys, &W.vals));
+    HITE_TRY(arena_get(ctx, B, (size_t)(W.ntiles + 1), &W.tile_cnt));
+    HITE_TRY(arena_get(ctx, B, (size_t)(W.ntiles + 2), &W.tile_first));
+    HITE_TRY(arena_get(ctx, B, (size_t)scan_tmp_elems(W.ntiles + 1), &W.tbs));
+    HITE_TRY(arena_get(ctx, B, (size_t)(W.ntiles > 0 ? W.ntiles : 1) * GM_TILE, &W.stage));
+    if (copy_knobs().keep_minimizers && hset.tab) {
+        HITE_TRY(arena_get(ctx, B, (size_t)(W.ntiles + 1), &W.tile_cnt_r));
+        HITE_TRY(arena_get(ctx, B, (size_t)(W.ntiles + 1) * (GM_TILE / 64), &W.wmask));
     }
-    int64_t blocks = ntiles < 256 * 64 ? ntiles : 256 * 64;
-    if (blocks < 1) blocks = 1;
     int tk_gm = hite_prof_begin(ctx, "index_minimizers", st);
-    const HSet none{nullptr, nullptr, 0, 0};
-    if (!keep_on) {
-        S->kept_epoch = -1;
-        if (hset.tab)
-            hipLaunchKernelGGL(genome_minimizer_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off,
-                               ctx->n_contigs, G, ntiles, stage, tile_cnt, hset, (const int32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(genome_minimizer_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off,
-                               ctx->n_contigs, G, ntiles, stage, tile_cnt, none, (const int32_t *)nullptr);
-    } else {
-        // the tiles always hold EVERY minimizer (a restricted build filters them below).  Kept from the last build on this genome state:
-        // only the tiles a mask has touched since are done again -- window starts [a - K - W - 2, b + 2] of a masked [a, b): a window
-        // reads the k-mers of W starts and a k-mer K bases, and a window's record also depends on the window before it
-        const bool kept = one_chunk && S->kept_stage == stage && S->kept_cnt == tile_cnt && S->kept_ctx == ctx && S->kept_G == G &&
-                          S->kept_epoch == ctx->genome_epoch && S->kept_log <= ctx->mask_log_n;
-        S->kept_epoch = -1;                       // (void until this build's kernels are queued)
-        if (!kept)
-            hipLaunchKernelGGL(genome_minimizer_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off,
-                               ctx->n_contigs, G, ntiles, stage, tile_cnt, none, (const int32_t *)nullptr);
-        else if (S->kept_log < ctx->mask_log_n) {
-            std::vector<unsigned char> dirty((size_t)ntiles, 0);
-            for (int64_t k = S->kept_log; k < ctx->mask_log_n; k++) {
-                int64_t lo = ctx->mask_log[2 * k] - CK - CW - 2, hi = ctx->mask_log[2 * k + 1] + 2;
-                if (lo < 0) lo = 0;
-                if (hi > G - 1) hi = G - 1;
-                for (int64_t t = lo / GM_TILE; t <= hi / GM_TILE && t < ntiles; t++) dirty[(size_t)t] = 1;
-            }
-            std::vector<int32_t> list;
-            for (int64_t t = 0; t < ntiles; t++) if (dirty[(size_t)t]) list.push_back((int32_t)t);
-            if (!list.empty()) {
-                int32_t *d_list;
-                CCHK(arena_alloc(ctx, B, list.size() * 4, &p)); d_list = (int32_t *)p;
-                HITE_CHECK(ctx, hipMemcpyAsync(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
-                HITE_CHECK(ctx, hipStreamSynchronize(st));          // (the list is a local)
-                const int64_t nl = (int64_t)list.size();
-                hipLaunchKernelGGL(genome_minimizer_kernel<false>, dim3((unsigned)(nl < blocks ? nl : blocks)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
-                                   ctx->d_contig_off, ctx->n_contigs, G, nl, stage, tile_cnt, none, (const int32_t *)d_list);
-            }
-        }
-        S->kept_stage = stage; S->kept_cnt = tile_cnt; S->kept_ctx = ctx; S->kept_G = G;
-        S->kept_epoch = ctx->genome_epoch; S->kept_log = ctx->mask_log_n;
-    }
+    HITE_TRY(index_tile_pass(ctx, S, st, W, hset, one_chunk));
     int64_t M = 0;
-    if (ntiles > 0) {
-        if (tile_cnt_r) {
-            hipLaunchKernelGGL(genome_minimizer_filter_kernel<false>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, ntiles, stage, tile_cnt, hset,
-                               tile_cnt_r, (const int64_t *)nullptr, (unsigned long long *)nullptr, (unsigned *)nullptr, cap, wmask);
-            CCHK(scan_excl_buf<int32_t>(ctx, tbs, tile_cnt_r, ntiles, tile_first, st));
-            HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, tile_first + ntiles, 8, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(genome_minimizer_filter_kernel<true>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, ntiles, stage, tile_cnt, hset,
-                               (int32_t *)nullptr, tile_first, keys, vals, cap, wmask);
-        } else {
-            CCHK(scan_excl_buf<int32_t>(ctx, tbs, tile_cnt, ntiles, tile_first, st));
-            HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, tile_first + ntiles, 8, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(genome_minimizer_pack_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, ntiles, stage, tile_first, keys, vals, cap);
-        }
+    if (W.ntiles > 0) {
+        // tiles -> keys / vals in position order (a restricted build from kept tiles filters on the way).  (The scan is called by name: it
+        // is the file's first, and where a template is first named decides where its kernels stand in the code object, see r22.)
+        const dim3 grid((unsigned)((W.ntiles + 3) / 4));
+        if (W.tile_cnt_r)
+            hipLaunchKernelGGL(genome_minimizer_filter_kernel<false>, grid, dim3(256), 0, st, W.ntiles, W.stage, W.tile_cnt, hset,
+                               W.tile_cnt_r, (const int64_t *)nullptr, (unsigned long long *)nullptr, (unsigned *)nullptr, W.cap, W.wmask);
+        HITE_TRY(scan_excl_buf<int32_t>(ctx, W.tbs, W.tile_cnt_r ? W.tile_cnt_r : W.tile_cnt, W.ntiles, W.tile_first, st));
+        HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + CS_TOTAL, W.tile_first + W.ntiles, 8, hipMemcpyDeviceToDevice, st));
+        if (W.tile_cnt_r)
+            hipLaunchKernelGGL(genome_minimizer_filter_kernel<true>, grid, dim3(256), 0, st, W.ntiles, W.stage, W.tile_cnt, hset,
+                               (int32_t *)nullptr, W.tile_first, W.keys, W.vals, W.cap, W.wmask);
+        else hipLaunchKernelGGL(genome_minimizer_pack_kernel, grid, dim3(256), 0, st, W.ntiles, W.stage, W.tile_first, W.keys, W.vals, W.cap);
         hite_prof_end(ctx, tk_gm, st);
         HITE_CHECK(ctx, hipGetLastError());
-        CCHK(read_back(ctx, S, st, 1));
-        M = S->h_pin[0];
+        HITE_TRY(S->pin.read_back(ctx, st, 1));
+        M = S->pin.h[CS_TOTAL];
     } else hite_prof_end(ctx, tk_gm, st);
-    if ((unsigned long long)M > cap) return HITE_ECAP;
+    if ((unsigned long long)M > W.cap) return HITE_ECAP;
     S->M = M;
     // stable sort on the hash (the key's upper word): equal hashes stay in position order
     int tk_is = hite_prof_begin(ctx, "index_sort", st);
     if (M > 1) {
         Sorter so;
-        CCHK(sorter_from_arena(so, ctx, B, st, M));
-        CCHK(sorter_sort_bits_swap(so, &keys, &vals, M, 32, 64));
+        HITE_TRY(sorter_from_arena(so, ctx, B, st, M));
+        HITE_TRY(sorter_sort_bits_swap(so, &W.keys, &W.vals, M, 32, 64));
     }
     hite_prof_end(ctx, tk_is, st);
     int tk_dir = hite_prof_begin(ctx, "index_directory", st);
-    S->idx_key = keys;
+    S->idx_key = W.keys;
     hipLaunchKernelGGL(fill_u32_kernel, CGRID((int64_t)(1 << DIRBITS) + 2), 0, st, (int64_t)(1 << DIRBITS) + 2, S->dir, (unsigned)M);
     if (M > 0) {
-        hipLaunchKernelGGL(split_index_kernel, CGRID(M), 0, st, M, keys, S->idx_hs, S->idx_pos);
-        HITE_CHECK(ctx, hipMemcpyAsync(S->idx_t, vals, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(split_index_kernel, CGRID(M), 0, st, M, W.keys, S->idx_hs, S->idx_pos);
+        HITE_CHECK(ctx, hipMemcpyAsync(S->idx_t, W.vals, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(index_directory_kernel, CGRID(M), 0, st, M, S->idx_hs, S->dir);
     }
     hite_prof_end(ctx, tk_dir, st);
@@ -1448,273 +1463,251 @@ extern "C" int hite_copy_index_build(hite_ctx *ctx, void **state_io, void *strea
     return index_build_impl(ctx, state_io, (hipStream_t)stream, HSet{nullptr, nullptr, 0, 0});
 }
 
-// candidates (device) -> copy table (device arrays owned by the index state's arena; valid until the next call)
-static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const uint8_t *d_cand, const int64_t *d_cand_off,
-                            int64_t cand_bytes, int32_t **d_copy_first, int64_t *n_copies, int32_t **d_contig,
-                            int64_t **d_start1, int64_t **d_end1, uint8_t **d_minus, int32_t **d_anchors, void *stream,
-                            bool restricted_ok /* the index was restricted to THESE candidates by the caller */) {
-    CopyState *S = (CopyState *)state;
-    if (!ctx || !S || !ctx->d_bases || n_cand < 0 || n_cand >= (1 << 19) || !n_copies) return HITE_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    if (S->restricted && !restricted_ok) {     // an index restricted to another candidate set answers nothing else: the full one
-        void *sp = S;
-        CCHK(index_build_impl(ctx, &sp, st, HSet{nullptr, nullptr, 0, 0}));
-    }
-    CCHK(arena_reset(ctx, S->arena, true));
-    CCHK(arena_reset(ctx, S->out, true));
-    Arena &A = S->arena;
-    void *p;
-    int32_t *ofirst32;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(n_cand + 2) * 4, &p)); ofirst32 = (int32_t *)p;
-    *d_copy_first = ofirst32; *n_copies = 0;
-    S->out_clip = nullptr; S->out_n = 0;
-    HITE_CHECK(ctx, hipMemsetAsync(ofirst32, 0, (size_t)(n_cand + 2) * 4, st));
-    *d_contig = nullptr; *d_start1 = nullptr; *d_end1 = nullptr; *d_minus = nullptr; *d_anchors = nullptr;
-    if (n_cand == 0 || cand_bytes <= 0 || S->M == 0) return HITE_OK;
-    // candidate minimizers
-    unsigned long long qcap = (unsigned long long)(cand_bytes * 0.32) + 4096 + (unsigned long long)n_cand;
-    unsigned *q_c, *q_pos, *q_hs, *occ_lo, *hval, *cval;
-    int32_t *occ_n, *per_cand, *per_cand300;
-    int64_t *hit_off, *bs, *cstart, *ofirst;
-    unsigned long long *hkey, *ckey;
-    CCHK(arena_alloc(ctx, A, qcap * 4, &p)); q_c = (unsigned *)p;
-    CCHK(arena_alloc(ctx, A, qcap * 4, &p)); q_pos = (unsigned *)p;
-    CCHK(arena_alloc(ctx, A, qcap * 4, &p)); q_hs = (unsigned *)p;
-    HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
-    int64_t nq, max_cand_len = 0;
-    int64_t *q_first = nullptr;          // first minimizer of every candidate (n_cand + 1): the hits of a candidate are one contiguous range
-    {
-        int32_t *q_cnt; int64_t *qbs; unsigned *r_pos, *r_hs;
-        CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 1) * 4, &p)); q_cnt = (int32_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 2) * 8, &p)); q_first = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(n_cand) * 8, &p)); qbs = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(cand_bytes + 64) * 4, &p)); r_pos = (unsigned *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(cand_bytes + 64) * 4, &p)); r_hs = (unsigned *)p;
-        int wblocks = n_cand < 65536 ? n_cand : 65536;
-        int tk_cm = hite_prof_begin(ctx, "cand_minimizer_kernel", st);
-        hipLaunchKernelGGL(cand_minimizer_kernel, dim3(wblocks), dim3(256), 0, st, n_cand, d_cand, d_cand_off, r_pos, r_hs, q_cnt,
-                           (unsigned long long *)(S->d_scal + 1));
-        CCHK(scan_excl_buf<int32_t>(ctx, qbs, q_cnt, n_cand, q_first, st));
-        HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, q_first + n_cand, 8, hipMemcpyDeviceToDevice, st));
-        CCHK(read_back(ctx, S, st, 2));
-        nq = S->h_pin[0];
-        max_cand_len = S->h_pin[1];
-        if ((unsigned long long)nq > qcap) return HITE_ECAP;
-        S->last[0] = nq; S->last[1] = S->last[2] = S->last[3] = S->last[4] = S->last[5] = S->last[6] = 0;
-        hipLaunchKernelGGL(cand_minimizer_pack_kernel, dim3((n_cand + 3) / 4 < 8192 ? (n_cand + 3) / 4 : 8192), dim3(256), 0, st, n_cand,
-                           d_cand_off, r_pos, r_hs, q_first, q_c, q_pos, q_hs);
-        hite_prof_end(ctx, tk_cm, st);
-    }
-    if (nq == 0) return HITE_OK;
-    CCHK(arena_alloc(ctx, A, (size_t)nq * 4, &p)); occ_lo = (unsigned *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)nq * 4, &p)); occ_n = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(nq + 1) * 8, &p)); hit_off = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(nq) * 8, &p)); bs = (int64_t *)p;
+// What a copy call keeps from stage to stage: the call, the sizes read back, the arrays that outlive a stage (in the call's arena)
+struct CopyWs {
+    int32_t n_cand; const uint8_t *d_cand; const int64_t *d_cand_off; int64_t cand_bytes; hipStream_t st;
+    int32_t *ofirst32;              // (in S->out) first record of every candidate, n_cand + 1
+    // candidate minimizers: every candidate's in its own region of r_pos / r_hs, and their counts; then packed: candidate, position and
+    // hash of each, the first of every candidate (n_cand + 1: a candidate's hits are one range), their number, the longest candidate
+    unsigned *r_pos, *r_hs, *q_c, *q_pos, *q_hs; int32_t *q_cnt; int64_t *q_first, nq, max_cand_len;
+    // hits: first hit of every minimizer, the hits, their format, the sorter sized for them
+    int64_t *hit_off, nh; unsigned long long *hkey; unsigned *hval; HitFmt F; int cbits, dbits; Sorter so;
+    // chains: fused = packed hits, the per-candidate sort writes the chain table itself; the table (its length stays on the device), its
+    // counters in S->pin.d (CS_CLUSTERS; CS_CHAINS_LONG and the three words behind it), the extension's clips per chain and end
+    bool fused; unsigned long long chcap; ChainRec *chain_tab; unsigned long long *d_ncl, *d_nchain; int32_t *x_i, *x_t;
+    // clusters of the globally sorted hits (!fused): their count (fused: -1, it arrives with the final read-back), first hit, extreme anchors
+    int64_t ncl; unsigned *c_first; unsigned long long *c_lo, *c_hi;
+};
+
+// First part of the candidate-minimizer stage, shared with the restricted index (whose hash set is made of r_hs): the minimizers in the
+// candidates' regions, their counts, the scan; nq and the longest candidate are read back.  The caller has zeroed the words of S->pin.d
+static int cand_minimizers_count(hite_ctx *ctx, CopyState *S, CopyWs &W, int words /* of the read-back */) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int32_t n_cand = W.n_cand;
+    int64_t *qbs;
+    HITE_TRY(arena_get(ctx, A, (size_t)(n_cand + 1), &W.q_cnt));
+    HITE_TRY(arena_get(ctx, A, (size_t)(n_cand + 2), &W.q_first));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(n_cand), &qbs));
+    HITE_TRY(arena_get(ctx, A, (size_t)(W.cand_bytes + 64), &W.r_pos, &W.r_hs));
+    hipLaunchKernelGGL(cand_minimizer_kernel, dim3(n_cand < 65536 ? n_cand : 65536), dim3(256), 0, st, n_cand, W.d_cand, W.d_cand_off, W.r_pos,
+                       W.r_hs, W.q_cnt, (unsigned long long *)(S->pin.d + CS_LONGEST));
+    HITE_TRY(S->pin.scan_total(ctx, st, qbs, W.q_cnt, n_cand, W.q_first, CS_TOTAL));
+    HITE_TRY(S->pin.read_back(ctx, st, words));
+    W.nq = S->pin.h[CS_TOTAL]; W.max_cand_len = S->pin.h[CS_LONGEST];
+    return HITE_OK;
+}
+
+// stage 1, candidate minimizers: W.nq of them (0: nothing to look up)
+static int copy_minimizers(hite_ctx *ctx, CopyState *S, CopyWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int32_t n_cand = W.n_cand;
+    const unsigned long long qcap = (unsigned long long)(W.cand_bytes * 0.32) + 4096 + (unsigned long long)n_cand;
+    HITE_TRY(arena_get(ctx, A, qcap, &W.q_c, &W.q_pos, &W.q_hs));
+    HITE_CHECK(ctx, hipMemsetAsync(S->pin.d, 0, CS_WORDS * sizeof(int64_t), st));
+    int tk_cm = hite_prof_begin(ctx, "cand_minimizer_kernel", st);
+    HITE_TRY(cand_minimizers_count(ctx, S, W, CS_LONGEST + 1));
+    if ((unsigned long long)W.nq > qcap) return HITE_ECAP;
+    S->last[0] = W.nq; S->last[1] = S->last[2] = S->last[3] = S->last[4] = S->last[5] = S->last[6] = 0;
+    hipLaunchKernelGGL(cand_minimizer_pack_kernel, dim3((n_cand + 3) / 4 < 8192 ? (n_cand + 3) / 4 : 8192), dim3(256), 0, st, n_cand,
+                       W.d_cand_off, W.r_pos, W.r_hs, W.q_first, W.q_c, W.q_pos, W.q_hs);
+    hite_prof_end(ctx, tk_cm, st);
+    return HITE_OK;
+}
+
+// stage 2, occurrences and hits: W.nh hits (0: none, and nothing else is set up), their format, the sorter and the chain table
+static int copy_hits(hite_ctx *ctx, CopyState *S, CopyWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int32_t n_cand = W.n_cand; const int64_t nq = W.nq;
+    unsigned *occ_lo; int32_t *occ_n; int64_t *bs;
+    HITE_TRY(arena_get(ctx, A, (size_t)nq, &occ_lo, &occ_n));
+    HITE_TRY(arena_get(ctx, A, (size_t)(nq + 1), &W.hit_off));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(nq), &bs));
     int tk_occ_kernel = hite_prof_begin(ctx, "occ_kernel", st);
-    hipLaunchKernelGGL(occ_kernel, CGRID(nq), 0, st, nq, q_hs, S->idx_hs, S->dir, occ_lo, occ_n);
+    hipLaunchKernelGGL(occ_kernel, CGRID(nq), 0, st, nq, W.q_hs, S->idx_hs, S->dir, occ_lo, occ_n);
     hite_prof_end(ctx, tk_occ_kernel, st);
-    CCHK(scan_excl_buf<int32_t>(ctx, bs, occ_n, nq, hit_off, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, hit_off + nq, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(read_back(ctx, S, st, 1));
-    const int64_t nh = S->h_pin[0];
+    HITE_TRY(S->pin.scan_total(ctx, st, bs, occ_n, nq, W.hit_off, CS_TOTAL));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    const int64_t nh = W.nh = S->pin.h[CS_TOTAL];
     S->last[1] = nh;
     if (nh == 0) return HITE_OK;
     if (nh >= 0xffffffffll) return HITE_ECAP;
     int cbits = 1; while ((1ll << cbits) < n_cand) cbits++;
     int dbits = 1; while ((1ll << dbits) < ctx->n_bases + DBIAS + 1) dbits++;
     if (dbits > 33) dbits = 33;
-    int qbits = 1; while ((1ll << qbits) < max_cand_len) qbits++;
-    HitFmt F;
+    int qbits = 1; while ((1ll << qbits) < W.max_cand_len) qbits++;
+    W.cbits = cbits; W.dbits = dbits; HitFmt &F = W.F;
     F.qbits = qbits + dbits + 1 + cbits <= 64 ? qbits : 0; F.dbits = dbits; F.hval = nullptr;
-    {   // HITE_HITS_WIDE=1 (tests): the 12-byte form whatever the sizes
-        static const bool wide_only = [] { const char *e = getenv("HITE_HITS_WIDE"); return e && *e && atoi(e) != 0; }();
-        if (wide_only) F.qbits = 0;
-    }
-    CCHK(arena_alloc(ctx, A, (size_t)(nh + 1) * 8, &p)); hkey = (unsigned long long *)p;
-    hval = nullptr;
-    if (!F.qbits) { CCHK(arena_alloc(ctx, A, (size_t)(nh + 1) * 4, &p)); hval = (unsigned *)p; F.hval = hval; }
+    if (copy_knobs().hits_wide) F.qbits = 0;
+    HITE_TRY(arena_get(ctx, A, (size_t)(nh + 1), &W.hkey));
+    W.hval = nullptr;
+    if (!F.qbits) { HITE_TRY(arena_get(ctx, A, (size_t)(nh + 1), &W.hval)); F.hval = W.hval; }
     int tk_hit_kernel = hite_prof_begin(ctx, "hit_kernel", st);
-    hipLaunchKernelGGL(hit_kernel, CGRID(nq), 0, st, nq, q_c, q_pos, q_hs, d_cand_off, S->idx_hs, S->idx_pos, occ_lo, occ_n, hit_off, hkey, hval, F);
+    hipLaunchKernelGGL(hit_kernel, CGRID(nq), 0, st, nq, W.q_c, W.q_pos, W.q_hs, W.d_cand_off, S->idx_hs, S->idx_pos, occ_lo, occ_n, W.hit_off, W.hkey,
+                       W.hval, F);
     hite_prof_end(ctx, tk_hit_kernel, st);
-    {
-        static const bool hist = [] { const char *e = getenv("HITE_HIT_HIST"); return e && *e && atoi(e) != 0; }();
-        static bool printed = false;
-        if (hist && !printed) {
-            printed = true;
-            unsigned long long *d_h, h_h[11];
-            CCHK(arena_alloc(ctx, A, 11 * 8, &p)); d_h = (unsigned long long *)p;
-            HITE_CHECK(ctx, hipMemsetAsync(d_h, 0, 11 * 8, st));
-            hipLaunchKernelGGL(hit_hist_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, q_first, hit_off, d_h);
-            HITE_CHECK(ctx, hipMemcpyAsync(h_h, d_h, 11 * 8, hipMemcpyDeviceToHost, st));
-            HITE_CHECK(ctx, hipStreamSynchronize(st));
-            fprintf(stderr, "hit_hist: candidates %d hits %lld max %llu | classes <=1024 <=2048 <=4096 <=8192 above: candidates %llu %llu %llu %llu %llu hits %llu %llu %llu %llu %llu\n",
-                    n_cand, (long long)nh, h_h[10], h_h[0], h_h[1], h_h[2], h_h[3], h_h[4], h_h[5], h_h[6], h_h[7], h_h[8], h_h[9]);
-        }
+    static bool printed = false;
+    if (copy_knobs().hit_hist && !printed) {
+        unsigned long long *d_h, h_h[11]; printed = true;
+        HITE_TRY(arena_get(ctx, A, 11, &d_h));
+        HITE_CHECK(ctx, hipMemsetAsync(d_h, 0, 11 * 8, st));
+        hipLaunchKernelGGL(hit_hist_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, W.q_first, W.hit_off, d_h);
+        HITE_CHECK(ctx, hipMemcpyAsync(h_h, d_h, 11 * 8, hipMemcpyDeviceToHost, st));
+        HITE_CHECK(ctx, hipStreamSynchronize(st));
+        fprintf(stderr, "hit_hist: candidates %d hits %lld max %llu | classes <=1024 <=2048 <=4096 <=8192 above: candidates %llu %llu %llu %llu %llu hits %llu %llu %llu %llu %llu\n",
+                n_cand, (long long)nh, h_h[10], h_h[0], h_h[1], h_h[2], h_h[3], h_h[4], h_h[5], h_h[6], h_h[7], h_h[8], h_h[9]);
     }
-    Sorter so;
-    CCHK(sorter_from_arena(so, ctx, A, st, nh));
+    HITE_TRY(sorter_from_arena(W.so, ctx, A, st, nh));
     // chains -> end extension -> copies.  The chain table is sized for the worst case (every chain needs >= 3 hits); its length
     // stays on the device (the kernels behind it run grid-stride loops up to the count they read there)
-    const unsigned long long chcap = (unsigned long long)(nh / C_MINANCH) + 1;
-    ChainRec *chain_tab;
-    CCHK(arena_alloc(ctx, A, (size_t)chcap * sizeof(ChainRec), &p)); chain_tab = (ChainRec *)p;
-    unsigned long long *d_ncl = (unsigned long long *)(S->d_scal + 2);        // clusters, counted on the device by the per-candidate sort
-    unsigned long long *d_nchain = (unsigned long long *)(S->d_scal + 4);     // [0] long chains, [1] short chains, [2] task queue
-    static const bool seg_sort = [] { const char *e = getenv("HITE_HIT_SEGSORT"); return !(e && *e && atoi(e) == 0); }();
-    const bool fused = F.qbits && seg_sort;      // packed hits: the per-candidate sort writes the chain table itself
+    W.chcap = (unsigned long long)(nh / C_MINANCH) + 1;
+    HITE_TRY(arena_get(ctx, A, (size_t)W.chcap, &W.chain_tab));
+    W.d_ncl = (unsigned long long *)(S->pin.d + CS_CLUSTERS); W.d_nchain = (unsigned long long *)(S->pin.d + CS_CHAINS_LONG);
+    W.fused = F.qbits && copy_knobs().hit_segsort; W.ncl = -1;
+    return HITE_OK;
+}
+
+// stage 3 (the default path), the per-candidate sort in LDS with the chains as its epilogue: classify, then one launch per class.  No
+// cluster array, no sorted hits written back, and no read-back of the cluster count: it arrives with the copy counts
+static int copy_segsort_chains(hite_ctx *ctx, CopyState *S, CopyWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int32_t n_cand = W.n_cand;
     int tk_sh = hite_prof_begin(ctx, "radix_sort_hits", st);
-    if (fused) {
-        // per-candidate sort in LDS (above) with the chains as its epilogue: classify, then one launch per class.  No flag, cluster
-        // id or cluster array, no sorted hits written back, and no read-back of the cluster count: it arrives with the copy counts
-        unsigned *hs_counts; int32_t *hs_lists;
-        CCHK(arena_alloc(ctx, A, 16, &p)); hs_counts = (unsigned *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)HS_NCLS * n_cand * 4 + 16, &p)); hs_lists = (int32_t *)p;
-        HITE_CHECK(ctx, hipMemsetAsync(hs_counts, 0, 16, st));
-        HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
-        hipLaunchKernelGGL(hit_sort_classify_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, q_first, hit_off, hs_counts, hs_lists, d_ncl);
-        static unsigned long long attr_done = 0ull;      // bit = device id: the attribute belongs to the device the kernel runs on
-        const unsigned long long dev_bit = 1ull << (ctx->device & 63);
-        if (!(attr_done & dev_bit)) {
-            HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&hit_segsort_kernel<HS_MEDIUM, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HS_MEDIUM * 8));
-            attr_done |= dev_bit;
-        }
-        const int sbits = dbits + 1;
-        const int gsm = n_cand < 8192 ? n_cand : 8192, gmd = n_cand < 2048 ? n_cand : 2048, glg = n_cand < 1024 ? n_cand : 1024;
-        // the few large ranges (long chains, 32 KB of LDS each) run on a side stream beside the small ones; the medium class
-        // takes a CU's whole LDS and follows on the main stream
-        hipStream_t sside[HITE_AUX_STREAMS];
-        hipEvent_t ev_fork, ev_join[HITE_AUX_STREAMS];
-        CCHK(hite_aux_streams(ctx, 1, sside, &ev_fork, ev_join));
-        HITE_CHECK(ctx, hipEventRecord(ev_fork, st));
-        HITE_CHECK(ctx, hipStreamWaitEvent(sside[0], ev_fork, 0));
-#define HS_CHAIN_ARGS d_cand_off, ctx->d_contig_off, ctx->n_contigs, chain_tab, chcap, d_nchain, d_ncl
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<0, 512>), dim3(glg), dim3(512), 0, sside[0], hs_counts + 3, hs_lists + (size_t)3 * n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_SMALL, 256>), dim3(gsm), dim3(256), 2 * HS_SMALL * 8, st, hs_counts, hs_lists, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MID, 256>), dim3(gmd), dim3(256), 2 * HS_MID * 8, st, hs_counts + 1, hs_lists + (size_t)n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MEDIUM, 512>), dim3(gmd), dim3(512), 2 * HS_MEDIUM * 8, st, hs_counts + 2, hs_lists + (size_t)2 * n_cand, q_first, hit_off, hkey, so.k2, F.qbits, sbits, HS_CHAIN_ARGS);
+    unsigned *hs_counts; int32_t *hs_lists;
+    HITE_TRY(arena_get(ctx, A, 4, &hs_counts));
+    HITE_TRY(arena_get(ctx, A, (size_t)HS_NCLS * n_cand + 4, &hs_lists));
+    HITE_CHECK(ctx, hipMemsetAsync(hs_counts, 0, 16, st));
+    HITE_CHECK(ctx, hipMemsetAsync(S->pin.d, 0, CS_WORDS * sizeof(int64_t), st));
+    hipLaunchKernelGGL(hit_sort_classify_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, W.q_first, W.hit_off, hs_counts, hs_lists, W.d_ncl);
+    static unsigned long long attr_done = 0ull;      // bit = device id: the attribute belongs to the device the kernel runs on
+    const unsigned long long dev_bit = 1ull << (ctx->device & 63);
+    if (!(attr_done & dev_bit)) {
+        HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&hit_segsort_kernel<HS_MEDIUM, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HS_MEDIUM * 8));
+        attr_done |= dev_bit;
+    }
+    const int sbits = W.dbits + 1;
+    const int gsm = n_cand < 8192 ? n_cand : 8192, gmd = n_cand < 2048 ? n_cand : 2048, glg = n_cand < 1024 ? n_cand : 1024;
+    // the few large ranges (long chains, 32 KB of LDS each) run on a side stream beside the small ones; the medium class
+    // takes a CU's whole LDS and follows on the main stream
+    hipStream_t sside[HITE_AUX_STREAMS]; hipEvent_t ev_fork, ev_join[HITE_AUX_STREAMS];
+    HITE_TRY(hite_aux_streams(ctx, 1, sside, &ev_fork, ev_join));
+    HITE_CHECK(ctx, hipEventRecord(ev_fork, st));
+    HITE_CHECK(ctx, hipStreamWaitEvent(sside[0], ev_fork, 0));
+#define HS_CHAIN_ARGS W.q_first, W.hit_off, W.hkey, W.so.k2, W.F.qbits, sbits, W.d_cand_off, ctx->d_contig_off, ctx->n_contigs, W.chain_tab, W.chcap, W.d_nchain, W.d_ncl
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<0, 512>), dim3(glg), dim3(512), 0, sside[0], hs_counts + 3, hs_lists + (size_t)3 * n_cand, HS_CHAIN_ARGS);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_SMALL, 256>), dim3(gsm), dim3(256), 2 * HS_SMALL * 8, st, hs_counts, hs_lists, HS_CHAIN_ARGS);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MID, 256>), dim3(gmd), dim3(256), 2 * HS_MID * 8, st, hs_counts + 1, hs_lists + (size_t)n_cand, HS_CHAIN_ARGS);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hit_segsort_kernel<HS_MEDIUM, 512>), dim3(gmd), dim3(512), 2 * HS_MEDIUM * 8, st, hs_counts + 2, hs_lists + (size_t)2 * n_cand, HS_CHAIN_ARGS);
 #undef HS_CHAIN_ARGS
-        HITE_CHECK(ctx, hipEventRecord(ev_join[0], sside[0]));
-        HITE_CHECK(ctx, hipStreamWaitEvent(st, ev_join[0], 0));
-        HITE_CHECK(ctx, hipGetLastError());
-    } else if (F.qbits) {
+    HITE_CHECK(ctx, hipEventRecord(ev_join[0], sside[0]));
+    HITE_CHECK(ctx, hipStreamWaitEvent(st, ev_join[0], 0));
+    HITE_CHECK(ctx, hipGetLastError());
+    hite_prof_end(ctx, tk_sh, st);
+    return arena_get(ctx, A, (size_t)W.chcap * 2, &W.x_i, &W.x_t);          // (the end extension's clips, as behind the global sort)
+}
+
+// stage 4 (12-byte hits, HITE_HIT_SEGSORT=0), the global sort and the clusters of the sorted hits: flags, ids, first hit and extreme
+// anchors of every cluster, for chain_list_kernel to make the same chain table of.  The default path has none of these arrays
+static int copy_global_clusters(hite_ctx *ctx, CopyState *S, CopyWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; HitFmt &F = W.F; const int64_t nh = W.nh;
+    int tk_sh = hite_prof_begin(ctx, "radix_sort_hits", st);
+    if (F.qbits) {
         // the key has a hole: the diagonal (gpos - qo + DBIAS < n_bases + DBIAS) rarely needs its 33 bits.  Two runs of stable
         // passes -- the diagonal's bits, then strand + candidate -- take 3 + 2 passes at 1 Gbp / 2^17 candidates where the
         // 51-bit key as a whole takes 6; the sorted pair of buffers is taken over instead of copied back
-        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, F.qbits, F.qbits + dbits));
-        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, F.qbits + dbits, F.qbits + dbits + 1 + cbits));
+        HITE_TRY(sorter_sort_bits_swap(W.so, &W.hkey, &W.hval, nh, F.qbits, F.qbits + W.dbits));
+        HITE_TRY(sorter_sort_bits_swap(W.so, &W.hkey, &W.hval, nh, F.qbits + W.dbits, F.qbits + W.dbits + 1 + W.cbits));
     } else {
-        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, 0, dbits));
-        CCHK(sorter_sort_bits_swap(so, &hkey, &hval, nh, 33, 34 + cbits));
-        F.hval = hval;
+        HITE_TRY(sorter_sort_bits_swap(W.so, &W.hkey, &W.hval, nh, 0, W.dbits));
+        HITE_TRY(sorter_sort_bits_swap(W.so, &W.hkey, &W.hval, nh, 33, 34 + W.cbits));
+        F.hval = W.hval;
     }
     hite_prof_end(ctx, tk_sh, st);
-    int32_t *x_i, *x_t;
-    CCHK(arena_alloc(ctx, A, (size_t)chcap * 8, &p)); x_i = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)chcap * 8, &p)); x_t = (int32_t *)p;
-    int64_t ncl = -1;                            // fused: known with the final read-back
-    int tk_ext;
-    if (!fused) {
-        // clusters of the globally sorted hits (12-byte hits, HITE_HIT_SEGSORT=0): flags, ids, extreme anchors, then the same chain
-        // table.  The default path has none of these arrays
-        int32_t *flag; int64_t *cid, *bs2; unsigned *c_first; unsigned long long *c_lo, *c_hi;
-        CCHK(arena_alloc(ctx, A, (size_t)(nh + 1) * 4, &p)); flag = (int32_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(nh + 2) * 8, &p)); cid = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(nh) * 8, &p)); bs2 = (int64_t *)p;
-        int tk_cluster_flag_kernel = hite_prof_begin(ctx, "cluster_flag_kernel", st);
-        hipLaunchKernelGGL(cluster_flag_kernel, CGRID(nh), 0, st, nh, hkey, F, ctx->d_contig_off, ctx->n_contigs, flag);
-        hite_prof_end(ctx, tk_cluster_flag_kernel, st);
-        CCHK(scan_excl_buf<int32_t>(ctx, bs2, flag, nh, cid, st));
-        HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, cid + nh, 8, hipMemcpyDeviceToDevice, st));
-        CCHK(read_back(ctx, S, st, 1));
-        ncl = S->h_pin[0];
-        CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 8, &p)); c_lo = (unsigned long long *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 8, &p)); c_hi = (unsigned long long *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(ncl + 2) * 4, &p)); c_first = (unsigned *)p;
-        hipLaunchKernelGGL(cluster_first_kernel, CGRID(nh), 0, st, nh, flag, cid, c_first, ncl);
-        int tk_cluster_acc_kernel = hite_prof_begin(ctx, "cluster_acc_kernel", st);
-        hipLaunchKernelGGL(cluster_acc_init_kernel, CGRID(ncl), 0, st, ncl, c_lo, c_hi);
-        hipLaunchKernelGGL(cluster_acc_kernel, CGRID(nh), 0, st, nh, hkey, F, flag, cid, c_lo, c_hi);
-        hite_prof_end(ctx, tk_cluster_acc_kernel, st);
-        HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
-        tk_ext = hite_prof_begin(ctx, "chain_extend_kernel", st);
-        int64_t lblocks = (ncl + 256 * CL_ITEMS - 1) / (256 * CL_ITEMS);
-        if (lblocks > 16384) lblocks = 16384;
-        if (lblocks < 1) lblocks = 1;
-        hipLaunchKernelGGL(chain_list_kernel, dim3((unsigned)lblocks), dim3(256), 0, st, ncl, hkey, F, c_first, c_lo, c_hi, d_cand_off, chain_tab, chcap, d_nchain);
-    } else tk_ext = hite_prof_begin(ctx, "chain_extend_kernel", st);
-    {
-        // persistent lanes: every lane takes (chain, end) tasks from the queue until it is empty
-        unsigned long long want_blocks = (2ull * chcap + 255ull) / 256ull;
-        unsigned eblocks = (unsigned)(want_blocks < 2048ull ? (want_blocks ? want_blocks : 1ull) : 2048ull);
-        // HITE_EXT_BLOCKS=<n> (tests): at most n blocks, so that lanes take several tasks each also in a small batch
-        static const int ext_blocks = [] { const char *e = getenv("HITE_EXT_BLOCKS"); return e && *e ? atoi(e) : 0; }();
-        if (ext_blocks >= 1 && (unsigned)ext_blocks < eblocks) eblocks = (unsigned)ext_blocks;
-        hipLaunchKernelGGL(chain_extend_kernel, dim3(eblocks), dim3(256), 0, st, d_nchain, chain_tab, d_cand,
-                           d_cand_off, ctx->d_bases, ctx->d_nmask, ctx->d_contig_off, ctx->n_contigs, chcap, d_nchain + 2, x_i, x_t);
+    int32_t *flag; int64_t *cid, *bs2;
+    HITE_TRY(arena_get(ctx, A, (size_t)W.chcap * 2, &W.x_i, &W.x_t));
+    HITE_TRY(arena_get(ctx, A, (size_t)(nh + 1), &flag));
+    HITE_TRY(arena_get(ctx, A, (size_t)(nh + 2), &cid));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(nh), &bs2));
+    int tk_cluster_flag_kernel = hite_prof_begin(ctx, "cluster_flag_kernel", st);
+    hipLaunchKernelGGL(cluster_flag_kernel, CGRID(nh), 0, st, nh, W.hkey, F, ctx->d_contig_off, ctx->n_contigs, flag);
+    hite_prof_end(ctx, tk_cluster_flag_kernel, st);
+    HITE_TRY(S->pin.scan_total(ctx, st, bs2, flag, nh, cid, CS_TOTAL));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    const int64_t ncl = W.ncl = S->pin.h[CS_TOTAL];
+    HITE_TRY(arena_get(ctx, A, (size_t)(ncl + 1), &W.c_lo, &W.c_hi));
+    HITE_TRY(arena_get(ctx, A, (size_t)(ncl + 2), &W.c_first));
+    hipLaunchKernelGGL(cluster_first_kernel, CGRID(nh), 0, st, nh, flag, cid, W.c_first, ncl);
+    int tk_cluster_acc_kernel = hite_prof_begin(ctx, "cluster_acc_kernel", st);
+    hipLaunchKernelGGL(cluster_acc_init_kernel, CGRID(ncl), 0, st, ncl, W.c_lo, W.c_hi);
+    hipLaunchKernelGGL(cluster_acc_kernel, CGRID(nh), 0, st, nh, W.hkey, F, flag, cid, W.c_lo, W.c_hi);
+    hite_prof_end(ctx, tk_cluster_acc_kernel, st);
+    HITE_CHECK(ctx, hipMemsetAsync(S->pin.d, 0, CS_WORDS * sizeof(int64_t), st));
+    return HITE_OK;
+}
+
+// stage 5, end extension (behind the global sort: the chain table first): persistent lanes take (chain, end) tasks until the queue is empty
+static int copy_extend(hite_ctx *ctx, CopyState *S, CopyWs &W) {
+    hipStream_t st = W.st;
+    int tk_ext = hite_prof_begin(ctx, "chain_extend_kernel", st);
+    if (!W.fused) {
+        int64_t lblocks = (W.ncl + 256 * CL_ITEMS - 1) / (256 * CL_ITEMS);
+        lblocks = lblocks > 16384 ? 16384 : lblocks < 1 ? 1 : lblocks;
+        hipLaunchKernelGGL(chain_list_kernel, dim3((unsigned)lblocks), dim3(256), 0, st, W.ncl, W.hkey, W.F, W.c_first, W.c_lo, W.c_hi, W.d_cand_off,
+                           W.chain_tab, W.chcap, W.d_nchain);
     }
+    unsigned long long want_blocks = (2ull * W.chcap + 255ull) / 256ull;
+    unsigned eblocks = (unsigned)(want_blocks < 2048ull ? (want_blocks ? want_blocks : 1ull) : 2048ull);
+    // HITE_EXT_BLOCKS=<n> (tests): at most n blocks, so that lanes take several tasks each also in a small batch
+    const int ext_blocks = copy_knobs().ext_blocks;
+    if (ext_blocks >= 1 && (unsigned)ext_blocks < eblocks) eblocks = (unsigned)ext_blocks;
+    hipLaunchKernelGGL(chain_extend_kernel, dim3(eblocks), dim3(256), 0, st, W.d_nchain, W.chain_tab, W.d_cand, W.d_cand_off, ctx->d_bases,
+                       ctx->d_nmask, ctx->d_contig_off, ctx->n_contigs, W.chcap, (unsigned long long *)(S->pin.d + CS_TASK_QUEUE), W.x_i, W.x_t);
     hite_prof_end(ctx, tk_ext, st);
-    int32_t *r_contig, *r_anch;
-    int64_t *r_s1, *r_e1;
-    uint8_t *r_minus;
-    uint32_t *r_clip;
-    // (records: at most one per chain)
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 8, &p)); ckey = (unsigned long long *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 4, &p)); cval = (unsigned *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 4, &p)); r_contig = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 8, &p)); r_s1 = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 8, &p)); r_e1 = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 16), &p)); r_minus = (uint8_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 4, &p)); r_anch = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(chcap + 1) * 4, &p)); r_clip = (uint32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 1) * 4, &p)); per_cand = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 1) * 4, &p)); per_cand300 = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 2) * 8, &p)); cstart = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 2) * 8, &p)); ofirst = (int64_t *)p;
-    int32_t *fill;
-    CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 1) * 4, &p)); fill = (int32_t *)p;
+    return HITE_OK;
+}
+
+// stage 6, records (at most one per chain) and the capped table: coverage filter and boundary extrapolation in two passes over the
+// chains (count per candidate, scan, fill), the sort by (candidate | anchors desc | start), the first C_MAXCOPY of every candidate
+static int copy_records(hite_ctx *ctx, CopyState *S, CopyWs &W, int64_t *n_copies, int32_t **d_contig, int64_t **d_start1, int64_t **d_end1,
+                        uint8_t **d_minus, int32_t **d_anchors) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int32_t n_cand = W.n_cand; const unsigned long long chcap = W.chcap;
+    unsigned long long *ckey; unsigned *cval; uint8_t *r_minus; uint32_t *r_clip;
+    int32_t *r_contig, *r_anch, *per_cand, *per_cand300, *fill; int64_t *r_s1, *r_e1, *cstart, *ofirst, *bs3;
+    HITE_TRY(arena_get(ctx, A, (size_t)(chcap + 1), &ckey, &cval, &r_contig, &r_s1, &r_e1));
+    HITE_TRY(arena_get(ctx, A, (size_t)(chcap + 16), &r_minus));
+    HITE_TRY(arena_get(ctx, A, (size_t)(chcap + 1), &r_anch, &r_clip));
+    HITE_TRY(arena_get(ctx, A, (size_t)(n_cand + 1), &per_cand, &per_cand300));
+    HITE_TRY(arena_get(ctx, A, (size_t)(n_cand + 2), &cstart, &ofirst));
+    HITE_TRY(arena_get(ctx, A, (size_t)(n_cand + 1), &fill));
     HITE_CHECK(ctx, hipMemsetAsync(per_cand, 0, (size_t)(n_cand + 1) * 4, st));
     HITE_CHECK(ctx, hipMemsetAsync(fill, 0, (size_t)(n_cand + 1) * 4, st));
-    int64_t *bs3;
-    CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(n_cand) * 8, &p)); bs3 = (int64_t *)p;
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(n_cand), &bs3));
     int tk_cluster_copy_kernel = hite_prof_begin(ctx, "chain_copy_kernel", st);
-    {
-        unsigned long long want_blocks = (chcap + 255ull) / 256ull;
-        const unsigned cblocks = (unsigned)(want_blocks < 8192ull ? (want_blocks ? want_blocks : 1ull) : 8192ull);
-        hipLaunchKernelGGL(chain_copy_kernel<false>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_tab, x_i, x_t, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, per_cand,
-                           (const int64_t *)nullptr, hite_sw(ctx, HITE_SW_COPY_INTERVAL));
-        CCHK(scan_excl_buf<int32_t>(ctx, bs3, per_cand, n_cand, cstart, st));
-        hipLaunchKernelGGL(chain_copy_kernel<true>, dim3(cblocks), dim3(256), 0, st, d_nchain, chcap, chain_tab, x_i, x_t, d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, fill,
-                           (const int64_t *)cstart, hite_sw(ctx, HITE_SW_COPY_INTERVAL));
-    }
+    const unsigned long long want_blocks = (chcap + 255ull) / 256ull;
+    const unsigned cblocks = (unsigned)(want_blocks < 8192ull ? (want_blocks ? want_blocks : 1ull) : 8192ull);
+    auto copy_pass = [&](auto write, int32_t *counter, const int64_t *first) {
+        hipLaunchKernelGGL(chain_copy_kernel<decltype(write)::value>, dim3(cblocks), dim3(256), 0, st, W.d_nchain, chcap, W.chain_tab, W.x_i, W.x_t,
+                           W.d_cand_off, ctx->d_contig_off, ctx->n_contigs, ckey, cval, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip, counter, first,
+                           hite_sw(ctx, HITE_SW_COPY_INTERVAL));
+    };
+    copy_pass(std::false_type{}, per_cand, nullptr);
+    HITE_TRY(scan_excl_buf<int32_t>(ctx, bs3, per_cand, n_cand, cstart, st));
+    copy_pass(std::true_type{}, fill, cstart);
     hite_prof_end(ctx, tk_cluster_copy_kernel, st);
     hipLaunchKernelGGL(cap300_kernel, CGRID((int64_t)n_cand), 0, st, n_cand, per_cand, per_cand300);
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, cstart + n_cand, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(scan_excl_buf<int32_t>(ctx, bs3, per_cand300, n_cand, ofirst, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 1, ofirst + n_cand, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(read_back(ctx, S, st, 8));
-    const int64_t ncp = S->h_pin[0], nout = S->h_pin[1];
-    S->last[2] = fused ? S->h_pin[2] : ncl;
-    S->last[4] = S->h_pin[4]; S->last[5] = S->h_pin[5]; S->last[6] = S->h_pin[7];
-    *n_copies = nout;
-    S->last[3] = ncp;
-    hipLaunchKernelGGL(i64_to_i32_kernel, CGRID((int64_t)n_cand + 1), 0, st, (int64_t)n_cand + 1, ofirst, ofirst32);
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + CS_TOTAL, cstart + n_cand, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.scan_total(ctx, st, bs3, per_cand300, n_cand, ofirst, CS_TOTAL_CAPPED));
+    HITE_TRY(S->pin.read_back(ctx, st, CS_WORDS));
+    const int64_t *h = S->pin.h, ncp = h[CS_TOTAL], nout = h[CS_TOTAL_CAPPED];
+    S->last[2] = W.fused ? h[CS_CLUSTERS] : W.ncl;
+    S->last[4] = h[CS_CHAINS_LONG]; S->last[5] = h[CS_CHAINS_SHORT]; S->last[6] = h[CS_EXT_COLS];
+    *n_copies = nout; S->last[3] = ncp;
+    hipLaunchKernelGGL(i64_to_i32_kernel, CGRID((int64_t)n_cand + 1), 0, st, (int64_t)n_cand + 1, ofirst, W.ofirst32);
     if (ncp == 0) return HITE_OK;
     Sorter so2;
-    CCHK(sorter_from_arena(so2, ctx, A, st, ncp));
+    HITE_TRY(sorter_from_arena(so2, ctx, A, st, ncp));
     int tk_sc = hite_prof_begin(ctx, "radix_sort_copies", st);
-    CCHK(sorter_sort(so2, ckey, cval, ncp, 64));
+    HITE_TRY(sorter_sort(so2, ckey, cval, ncp, 64));
     hite_prof_end(ctx, tk_sc, st);
-    int32_t *o_contig, *o_anch;
-    int64_t *o_s1, *o_e1;
-    uint8_t *o_minus;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(nout + 1) * 4, &p)); o_contig = (int32_t *)p;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(nout + 1) * 8, &p)); o_s1 = (int64_t *)p;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(nout + 1) * 8, &p)); o_e1 = (int64_t *)p;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(nout + 16), &p)); o_minus = (uint8_t *)p;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(nout + 1) * 4, &p)); o_anch = (int32_t *)p;
-    uint32_t *o_clip;
-    CCHK(arena_alloc(ctx, S->out, (size_t)(nout + 1) * 4, &p)); o_clip = (uint32_t *)p;
+    int32_t *o_contig, *o_anch; int64_t *o_s1, *o_e1; uint8_t *o_minus; uint32_t *o_clip;
+    HITE_TRY(arena_get(ctx, S->out, (size_t)(nout + 1), &o_contig, &o_s1, &o_e1));
+    HITE_TRY(arena_get(ctx, S->out, (size_t)(nout + 16), &o_minus));
+    HITE_TRY(arena_get(ctx, S->out, (size_t)(nout + 1), &o_anch, &o_clip));
     hipLaunchKernelGGL(emit_copies_kernel, CGRID(ncp), 0, st, ncp, ckey, cval, cstart, ofirst, r_contig, r_s1, r_e1, r_minus, r_anch, r_clip,
                        o_contig, o_s1, o_e1, o_minus, o_anch, o_clip);
     S->out_clip = o_clip; S->out_n = nout;
@@ -1722,11 +1715,39 @@ static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const ui
     *d_contig = o_contig; *d_start1 = o_s1; *d_end1 = o_e1; *d_minus = o_minus; *d_anchors = o_anch;
     // if the temporaries grew into several chunks during this call, merge them NOW (they are dead; the copy table lives in
     // S->out): the next call then starts on one chunk and performs no hipMalloc
-    CCHK(arena_reset(ctx, S->arena, true));
-    return HITE_OK;
+    return arena_reset(ctx, S->arena, true);
 }
 
-// host-buffer wrapper: builds the index if *state_io is NULL, uploads the candidates, downloads the table
+// candidates (device) -> copy table (device arrays owned by the index state's arena; valid until the next call)
+static int find_copies_impl(hite_ctx *ctx, void *state, int32_t n_cand, const uint8_t *d_cand, const int64_t *d_cand_off,
+                            int64_t cand_bytes, int32_t **d_copy_first, int64_t *n_copies, int32_t **d_contig,
+                            int64_t **d_start1, int64_t **d_end1, uint8_t **d_minus, int32_t **d_anchors, void *stream,
+                            bool restricted_ok /* the index was restricted to THESE candidates by the caller */) {
+    CopyState *S = (CopyState *)state;
+    if (!ctx || !S || !ctx->d_bases || n_cand < 0 || n_cand >= (1 << 19) || !n_copies) return HITE_EINVAL;
+    CopyWs W{n_cand, d_cand, d_cand_off, cand_bytes, (hipStream_t)stream};
+    HITE_CHECK(ctx, hipSetDevice(ctx->device));
+    if (S->restricted && !restricted_ok) {     // an index restricted to another candidate set answers nothing else: the full one
+        void *sp = S;
+        HITE_TRY(index_build_impl(ctx, &sp, W.st, HSet{nullptr, nullptr, 0, 0}));
+    }
+    HITE_TRY(arena_reset(ctx, S->arena, true));
+    HITE_TRY(arena_reset(ctx, S->out, true));
+    HITE_TRY(arena_get(ctx, S->out, (size_t)(n_cand + 2), &W.ofirst32));
+    *d_copy_first = W.ofirst32; *n_copies = 0; S->out_clip = nullptr; S->out_n = 0;
+    HITE_CHECK(ctx, hipMemsetAsync(W.ofirst32, 0, (size_t)(n_cand + 2) * 4, W.st));
+    *d_contig = nullptr; *d_start1 = nullptr; *d_end1 = nullptr; *d_minus = nullptr; *d_anchors = nullptr;
+    if (n_cand == 0 || cand_bytes <= 0 || S->M == 0) return HITE_OK;
+    HITE_TRY(copy_minimizers(ctx, S, W));
+    if (W.nq == 0) return HITE_OK;
+    HITE_TRY(copy_hits(ctx, S, W));
+    if (W.nh == 0) return HITE_OK;
+    if (W.fused) HITE_TRY(copy_segsort_chains(ctx, S, W));
+    else HITE_TRY(copy_global_clusters(ctx, S, W));
+    HITE_TRY(copy_extend(ctx, S, W));
+    return copy_records(ctx, S, W, n_copies, d_contig, d_start1, d_end1, d_minus, d_anchors);      // (returns early on no copy at all)
+}
+
 extern "C" int hite_find_copies_dev(hite_ctx *ctx, void *state, int32_t n_cand, const uint8_t *d_cand, const int64_t *d_cand_off,
                                     int64_t cand_bytes, int32_t **d_copy_first, int64_t *n_copies, int32_t **d_contig,
                                     int64_t **d_start1, int64_t **d_end1, uint8_t **d_minus, int32_t **d_anchors, void *stream) {
@@ -1748,86 +1769,62 @@ extern "C" int hite_find_copies_restricted_dev(hite_ctx *ctx, void **state_io, i
     hipStream_t st = (hipStream_t)stream;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
     CopyState *S;
-    CCHK(copy_state_get(ctx, state_io, &S));
-    CCHK(arena_reset(ctx, S->arena, true));
+    HITE_TRY(copy_state_get(ctx, state_io, &S));
+    HITE_TRY(arena_reset(ctx, S->arena, true));
     Arena &A = S->arena;
-    void *p;
     unsigned *tab = nullptr, *bits = nullptr; unsigned mask = 1023, bmask = 65535;
-    const int64_t cb = cand_bytes > 0 ? cand_bytes : 0;
+    const bool any = n_cand > 0 && cand_bytes > 0; CopyWs W{n_cand, d_cand, d_cand_off, cand_bytes, st};
     int tk = hite_prof_begin(ctx, "restricted_set", st);
-    if (n_cand > 0 && cb > 0) {
-        int32_t *q_cnt; unsigned *r_pos, *r_hs; int64_t *q_first, *qbs;
-        CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 1) * 4, &p)); q_cnt = (int32_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(n_cand + 2) * 8, &p)); q_first = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(n_cand) * 8, &p)); qbs = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(cb + 64) * 4, &p)); r_pos = (unsigned *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(cb + 64) * 4, &p)); r_hs = (unsigned *)p;
-        HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
-        hipLaunchKernelGGL(cand_minimizer_kernel, dim3(n_cand < 65536 ? n_cand : 65536), dim3(256), 0, st, n_cand, d_cand, d_cand_off, r_pos,
-                           r_hs, q_cnt, (unsigned long long *)(S->d_scal + 1));
-        CCHK(scan_excl_buf<int32_t>(ctx, qbs, q_cnt, n_cand, q_first, st));
-        HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, q_first + n_cand, 8, hipMemcpyDeviceToDevice, st));
-        CCHK(read_back(ctx, S, st, 1));
-        const int64_t nq = S->h_pin[0];
-        while ((int64_t)mask + 1 < 4 * nq && mask < 0x7fffffffu) mask = mask * 2 + 1;     // load <= 1/4
-        if ((int64_t)mask + 1 < 2 * nq) return HITE_ECAP;
-        while ((int64_t)bmask + 1 < 16 * nq && bmask < 0x00ffffffu) bmask = bmask * 2 + 1;     // <= 2 MiB
-        CCHK(arena_alloc(ctx, A, ((size_t)mask + 1) * 4, &p)); tab = (unsigned *)p;
-        CCHK(arena_alloc(ctx, A, ((size_t)bmask + 1) / 8, &p)); bits = (unsigned *)p;
-        HITE_CHECK(ctx, hipMemsetAsync(tab, 0xff, ((size_t)mask + 1) * 4, st));
-        HITE_CHECK(ctx, hipMemsetAsync(bits, 0, ((size_t)bmask + 1) / 8, st));
+    if (any) {
+        HITE_CHECK(ctx, hipMemsetAsync(S->pin.d, 0, CS_WORDS * sizeof(int64_t), st));
+        HITE_TRY(cand_minimizers_count(ctx, S, W, CS_TOTAL + 1));
+        while ((int64_t)mask + 1 < 4 * W.nq && mask < 0x7fffffffu) mask = mask * 2 + 1;     // load <= 1/4
+        if ((int64_t)mask + 1 < 2 * W.nq) return HITE_ECAP;
+        while ((int64_t)bmask + 1 < 16 * W.nq && bmask < 0x00ffffffu) bmask = bmask * 2 + 1;     // <= 2 MiB
+    }
+    HITE_TRY(arena_get(ctx, A, (size_t)mask + 1, &tab));
+    HITE_TRY(arena_get(ctx, A, ((size_t)bmask + 1) / 32, &bits));
+    HITE_CHECK(ctx, hipMemsetAsync(tab, 0xff, ((size_t)mask + 1) * 4, st));
+    HITE_CHECK(ctx, hipMemsetAsync(bits, 0, ((size_t)bmask + 1) / 8, st));
+    if (any) {
         hipLaunchKernelGGL(hset_insert_kernel, dim3((n_cand + 3) / 4 < 8192 ? (n_cand + 3) / 4 : 8192), dim3(256), 0, st, n_cand, d_cand_off,
-                           r_hs, q_cnt, tab, mask, bits, bmask);
+                           W.r_hs, W.q_cnt, tab, mask, bits, bmask);
         HITE_CHECK(ctx, hipGetLastError());
-    } else {
-        CCHK(arena_alloc(ctx, A, ((size_t)mask + 1) * 4, &p)); tab = (unsigned *)p;
-        CCHK(arena_alloc(ctx, A, ((size_t)bmask + 1) / 8, &p)); bits = (unsigned *)p;
-        HITE_CHECK(ctx, hipMemsetAsync(tab, 0xff, ((size_t)mask + 1) * 4, st));
-        HITE_CHECK(ctx, hipMemsetAsync(bits, 0, ((size_t)bmask + 1) / 8, st));
     }
     hite_prof_end(ctx, tk, st);
-    CCHK(index_build_impl(ctx, state_io, st, HSet{tab, bits, mask, bmask}));     // (its own arena; ends with a stream synchronise: `tab` is free to go)
+    HITE_TRY(index_build_impl(ctx, state_io, st, HSet{tab, bits, mask, bmask}));     // (its own arena; ends with a stream synchronise: `tab` is free to go)
     return find_copies_impl(ctx, *state_io, n_cand, d_cand, d_cand_off, cand_bytes, d_copy_first, n_copies, d_contig, d_start1, d_end1,
                             d_minus, d_anchors, stream, true);
 }
 
+// host-buffer wrapper: builds the index if *state_io is NULL, uploads the candidates, downloads the table
 static int find_copies_host(hite_ctx *ctx, void **state_io, int32_t n_cand, const uint8_t *cand, const int64_t *cand_off,
                             int64_t cap, int32_t *copy_first, int32_t *contig, int64_t *start1, int64_t *end1, uint8_t *minus,
                             int32_t *anchors, int64_t *n_out, bool restricted) {
     if (!ctx || !state_io || !cand || !cand_off || !copy_first || !n_out) return HITE_EINVAL;
     HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    if (!*state_io && !restricted) CCHK(hite_copy_index_build(ctx, state_io, nullptr));
+    if (!*state_io && !restricted) HITE_TRY(hite_copy_index_build(ctx, state_io, nullptr));
     int64_t bytes = cand_off[n_cand];
     DevBuf b_off, b_cand;           // (freed b_cand, b_off)
     HITE_CHECK(ctx, b_cand.alloc((size_t)bytes + 64));
     HITE_CHECK(ctx, b_off.alloc((size_t)(n_cand + 1) * 8));
-    uint8_t *dc = b_cand.as<uint8_t>();
-    int64_t *dco = b_off.as<int64_t>();
+    uint8_t *dc = b_cand.as<uint8_t>(); int64_t *dco = b_off.as<int64_t>();
     HITE_CHECK(ctx, hipMemcpy(dc, cand, (size_t)bytes, hipMemcpyHostToDevice));
     HITE_CHECK(ctx, hipMemcpy(dco, cand_off, (size_t)(n_cand + 1) * 8, hipMemcpyHostToDevice));
-    int32_t *dcf, *dct, *dan;
-    int64_t *ds1, *de1;
-    uint8_t *dmn;
-    int64_t n = 0;
+    int32_t *dcf, *dct, *dan; int64_t *ds1, *de1, n = 0; uint8_t *dmn;
     int rc = restricted ? hite_find_copies_restricted_dev(ctx, state_io, n_cand, dc, dco, bytes, &dcf, &n, &dct, &ds1, &de1, &dmn, &dan, nullptr)
                         : hite_find_copies_dev(ctx, *state_io, n_cand, dc, dco, bytes, &dcf, &n, &dct, &ds1, &de1, &dmn, &dan, nullptr);
-    if (rc == HITE_OK) {
-        *n_out = n;
-        if (hipDeviceSynchronize() != hipSuccess) rc = HITE_EHIP;
-        else if (n > cap) rc = HITE_ECAP;
-        else {
-            hipError_t e = hipMemcpy(copy_first, dcf, (size_t)(n_cand + 1) * 4, hipMemcpyDeviceToHost);
-            if (n > 0) {
-                if (e == hipSuccess) e = hipMemcpy(contig, dct, (size_t)n * 4, hipMemcpyDeviceToHost);
-                if (e == hipSuccess) e = hipMemcpy(start1, ds1, (size_t)n * 8, hipMemcpyDeviceToHost);
-                if (e == hipSuccess) e = hipMemcpy(end1, de1, (size_t)n * 8, hipMemcpyDeviceToHost);
-                if (e == hipSuccess) e = hipMemcpy(minus, dmn, (size_t)n, hipMemcpyDeviceToHost);
-                if (e == hipSuccess && anchors) e = hipMemcpy(anchors, dan, (size_t)n * 4, hipMemcpyDeviceToHost);
-            }
-            if (e != hipSuccess) rc = HITE_EHIP;
-        }
-    }
-    return rc;
+    if (rc != HITE_OK) return rc;
+    *n_out = n;
+    if (hipDeviceSynchronize() != hipSuccess) return HITE_EHIP;
+    if (n > cap) return HITE_ECAP;
+    const size_t un = n > 0 ? (size_t)n : 0;         // (no record: only the table of first records comes down)
+    const struct { void *dst; const void *src; size_t bytes; } down[6] = {
+        {copy_first, dcf, (size_t)(n_cand + 1) * 4}, {contig, dct, un * 4}, {start1, ds1, un * 8},
+        {end1, de1, un * 8},                         {minus, dmn, un},      {anchors, dan, anchors ? un * 4 : 0}};
+    for (const auto &d : down)
+        if (d.bytes && hipMemcpy(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost) != hipSuccess) return HITE_EHIP;
+    return HITE_OK;
 }
 
 // sizes of the last hite_find_copies[_dev] call on this index: {candidate minimizers, index hits, diagonal clusters, copies before the cap}
@@ -2387,9 +2384,233 @@ extern "C" int hite_seed_segments(hite_ctx *ctx, int64_t seg_len, int32_t cap, i
     return (seg_chrom && n > cap) ? HITE_ECAP : HITE_OK;
 }
 
+// launches that differ only in the packed / unpacked anchor form: f(std::true_type or std::false_type), a kernel<decltype(pk)::value>
+template <class Fn>
+static void by_pk(bool packed, Fn &&f) { if (packed) f(std::true_type{}); else f(std::false_type{}); }
+
+// What a seeding call keeps from stage to stage (device arrays in the call's arena)
+struct SeedWs {
+    hipStream_t st; int64_t M, G, seg_len; SeedShard shard;
+    bool packed;                                // anchors of 8 bytes (the query position inside the key) instead of 12
+    int32_t *seg_base;                          // first segment id of every contig
+    int32_t *cnt; int64_t *aoff; uint2 *srec;   // per seed, in position order: partners, first anchor, record (index entry, place in its run)
+    int64_t na, ncl, np;                        // anchors, clusters, pieces
+    unsigned long long *akey; unsigned *aval;   // anchors: strand | diagonal (packed: | query position); the query positions (unpacked)
+    unsigned *c_first;                          // first anchor of every cluster (+ sentinel)
+    int32_t *pcnt; int64_t *pfirst;             // pieces of every cluster, and their scan
+    unsigned *plist; unsigned long long *pn;    // the clusters that can be an HSP (each holds >= SEED_MINANCH anchors), and how many
+    int32_t *f_qseg, *f_sseg; int64_t *f_q[4];  // the sorted table
+};
+
+// runs of equal hs >> 1 in the index; per seed -- in position order, the rank the index build left in idx_t -- its partner count and
+// its record; the scan of the counts, whose total (the anchors) is read back
+static int seed_runs_counts(hite_ctx *ctx, CopyState *S, SeedWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int64_t M = W.M, G = W.G;
+    const CopyKnobs &K = copy_knobs();
+    int tk_rc = hite_prof_begin(ctx, "seed_runs_count", st);
+    // HITE_SEED_COUNT2=0: the run arrays (flags, scan, first-of-run) and the thread-per-entry kernel of round 5
+    const bool count2 = K.seed_count2;
+    int32_t *rflag = nullptr; int64_t *rid = nullptr, *bs; unsigned *run_first = nullptr;
+    if (!count2) {
+        HITE_TRY(arena_get(ctx, A, (size_t)(M + 1), &rflag));
+        HITE_TRY(arena_get(ctx, A, (size_t)(M + 2), &rid, &run_first));
+    }
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(M), &bs));
+    HITE_TRY(arena_get(ctx, A, (size_t)(M + 1), &W.cnt));
+    HITE_TRY(arena_get(ctx, A, (size_t)(M + 2), &W.aoff));
+    HITE_TRY(arena_get(ctx, A, (size_t)(M + 1), &W.srec));
+    const dim3 c2grid((unsigned)((M + SC_TILE - 1) / SC_TILE));
+    if (!count2) {
+        hipLaunchKernelGGL(seed_runflag_kernel, CGRID(M), 0, st, M, S->idx_hs, rflag);
+        HITE_TRY(scan_excl_buf<int32_t>(ctx, bs, rflag, M, rid, st));
+        hipLaunchKernelGGL(seed_runfirst_kernel, CGRID(M), 0, st, M, rflag, rid, run_first);
+    }
+    // HITE_SEED_PLACE=0 / 1 (tests): never / always through the grouped form
+    if (K.seed_place == 1 || (K.seed_place != 0 && M >= RS_WIDE_MIN)) {
+        unsigned long long *pk; unsigned *pv;
+        HITE_TRY(arena_get(ctx, A, (size_t)(M + 1), &pk, &pv));
+        Sorter sp;
+        HITE_TRY(sorter_from_arena(sp, ctx, A, st, M));
+        if (count2) hipLaunchKernelGGL(seed_count2_kernel<true>, c2grid, dim3(256), 0, st, M, G, S->idx_hs, S->idx_key, S->idx_t, W.shard, W.srec, pk, pv);
+        else hipLaunchKernelGGL(seed_count_kernel<true>, CGRID(M), 0, st, M, G, rflag, rid, run_first, S->idx_key, S->idx_t, W.shard, W.srec, pk, pv);
+        int mb = 1;
+        while (mb < 32 && (1ll << mb) < M) mb++;                  // ranks < 2^mb
+        const int shift = mb > 10 ? mb - 10 : 0;
+        HITE_TRY(sorter_sort_bits_swap(sp, &pk, &pv, M, shift, shift + (M >= RS_WIDE_MIN ? 10 : 8)));       // ONE pass
+        const int nb = (int)((M + 256 * SPL_ITEMS - 1) / (256 * SPL_ITEMS));
+        // what keeps the window inside an L2 (4 MB): two workgroups per compute unit -- 64 KB of LDS asked for, none used --, i.e. 131 k
+        // records of a chiplet in flight, half a group; and the counts NOT scattered beside the records (a second window): seed_cnt_kernel
+        // reads them back in order.  1 Gbp, 182 M seeds, seed_runs_count: direct scatter 10.7 ms; grouped 9.1; without the counts 7.8;
+        // with the LDS cap 7.1.
+        hipLaunchKernelGGL(seed_place_kernel, dim3((unsigned)nb), dim3(256), (size_t)K.seed_place_lds, st, M, nb, pk, pv, W.srec,
+                           K.seed_place_cnt ? W.cnt : (int32_t *)nullptr);
+        if (!K.seed_place_cnt) hipLaunchKernelGGL(seed_cnt_kernel, CGRID(M), 0, st, M, W.srec, W.cnt);
+    } else {
+        if (count2) hipLaunchKernelGGL(seed_count2_kernel<false>, c2grid, dim3(256), 0, st, M, G, S->idx_hs, S->idx_key, S->idx_t, W.shard, W.srec,
+                                       (unsigned long long *)nullptr, (unsigned *)nullptr);
+        else hipLaunchKernelGGL(seed_count_kernel<false>, CGRID(M), 0, st, M, G, rflag, rid, run_first, S->idx_key, S->idx_t, W.shard, W.srec,
+                                (unsigned long long *)nullptr, (unsigned *)nullptr);
+        hipLaunchKernelGGL(seed_cnt_kernel, CGRID(M), 0, st, M, W.srec, W.cnt);
+    }
+    HITE_TRY(scan_excl_buf<int32_t>(ctx, bs, W.cnt, M, W.aoff, st));
+    hite_prof_end(ctx, tk_rc, st);
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + CS_TOTAL, W.aoff + M, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    W.na = S->pin.h[CS_TOTAL];
+    return HITE_OK;
+}
+
+// the anchors, and their stable sort on (strand, diagonal >> 6)
+static int seed_anchors_sorted(hite_ctx *ctx, CopyState *S, SeedWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int64_t M = W.M, G = W.G, na = W.na;
+    W.aval = nullptr;
+    HITE_TRY(arena_get(ctx, A, (size_t)(na + 1), &W.akey));
+    if (!W.packed) HITE_TRY(arena_get(ctx, A, (size_t)(na + 1), &W.aval));
+    int tk = hite_prof_begin(ctx, "seed_anchor", st);
+    const dim3 cgrid((unsigned)((M + 255) / 256));
+    if (W.shard.sharded) by_pk(W.packed, [&](auto pk) {
+        hipLaunchKernelGGL(seed_anchor_kernel<decltype(pk)::value>, CGRID(M), 0, st, M, G, W.srec, S->idx_key, W.cnt, W.aoff, W.shard, W.akey, W.aval);
+    });
+    else by_pk(W.packed, [&](auto pk) {
+        hipLaunchKernelGGL(seed_anchor_coop_kernel<decltype(pk)::value>, cgrid, dim3(256), 0, st, M, G, W.srec, S->idx_key, W.aoff, W.akey, W.aval);
+    });
+    hite_prof_end(ctx, tk, st);
+    // after an odd number of passes the sorted records sit in the sorter's buffers (no copy back: akey / aval are re-pointed)
+    tk = hite_prof_begin(ctx, "seed_anchor_sort", st);
+    Sorter so;
+    HITE_TRY(sorter_from_arena(so, ctx, A, st, na, !W.packed));
+    if (W.packed) { unsigned *nov = nullptr; HITE_TRY(sorter_sort_bits_swap(so, &W.akey, &nov, na, 36, 62)); }
+    else HITE_TRY(sorter_sort_bits_swap(so, &W.akey, &W.aval, na, 6, 35));
+    hite_prof_end(ctx, tk, st);
+    return HITE_OK;
+}
+
+// clusters: starts per tile of 2048 anchors -> scan -> the index of every cluster's first anchor (+ sentinel)
+static int seed_clusters(hite_ctx *ctx, CopyState *S, SeedWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int64_t na = W.na;
+    int tk_cl = hite_prof_begin(ctx, "seed_clusters", st);
+    const int64_t ntile = (na + SF_TILE - 1) / SF_TILE;
+    int32_t *tcnt; int64_t *tfirst, *bs2; uint8_t *sbits;
+    HITE_TRY(arena_get(ctx, A, (size_t)(ntile + 1), &tcnt));
+    HITE_TRY(arena_get(ctx, A, (size_t)(ntile + 2), &tfirst));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(ntile), &bs2));
+    HITE_TRY(arena_get(ctx, A, (size_t)ntile * 256, &sbits));
+    by_pk(W.packed, [&](auto pk) {
+        hipLaunchKernelGGL(seed_clusters_kernel<decltype(pk)::value>, dim3((unsigned)ntile), dim3(256), 0, st, na, W.G, W.akey, W.aval, ctx->d_contig_off,
+                           ctx->n_contigs, tcnt, sbits);
+    });
+    HITE_TRY(S->pin.scan_total(ctx, st, bs2, tcnt, ntile, tfirst, CS_TOTAL));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    W.ncl = S->pin.h[CS_TOTAL];
+    HITE_TRY(arena_get(ctx, A, (size_t)(W.ncl + 2), &W.c_first));
+    hipLaunchKernelGGL(seed_cluster_emit_kernel, dim3((unsigned)ntile), dim3(256), 0, st, na, sbits, (const int64_t *)tfirst, W.c_first);
+    hite_prof_end(ctx, tk_cl, st);
+    return HITE_OK;
+}
+
+// one pass of seed_piece_kernel over the clusters of plist (its length stays on the device): counting into pcnt, or emitting at pfirst
+template <bool EMIT>
+static void seed_piece_pass(hite_ctx *ctx, const SeedWs &W, const int64_t *pfirst, unsigned long long *okey, unsigned *oval, int32_t *t_qseg,
+                            int32_t *t_sseg, int64_t *const *t_q) {
+    by_pk(W.packed, [&](auto pk) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(seed_piece_kernel<EMIT, decltype(pk)::value>), dim3(8192), dim3(256), 0, W.st, W.ncl, W.G, W.seg_len, W.akey,
+                           W.aval, W.c_first, ctx->d_contig_off, ctx->n_contigs, W.seg_base, W.pcnt, pfirst, okey, oval, t_qseg, t_sseg, t_q[0], t_q[1],
+                           t_q[2], t_q[3], W.plist, W.pn);
+    });
+}
+
+// pieces: select, count, scan; the total is read back
+static int seed_pieces(hite_ctx *ctx, CopyState *S, SeedWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int64_t ncl = W.ncl;
+    int tk_pc = hite_prof_begin(ctx, "seed_pieces", st);
+    int64_t *bs3;
+    HITE_TRY(arena_get(ctx, A, (size_t)(ncl + 1), &W.pcnt));
+    HITE_TRY(arena_get(ctx, A, (size_t)(ncl + 2), &W.pfirst));
+    HITE_TRY(arena_get(ctx, A, (size_t)scan_tmp_elems(ncl), &bs3));
+    HITE_TRY(arena_get(ctx, A, (size_t)(W.na / SEED_MINANCH + 64), &W.plist));
+    HITE_TRY(arena_get(ctx, A, 2, &W.pn));
+    HITE_CHECK(ctx, hipMemsetAsync(W.pn, 0, 16, st));
+    by_pk(W.packed, [&](auto pk) {
+        hipLaunchKernelGGL(seed_piece_select_kernel<decltype(pk)::value>, dim3((unsigned)((ncl + 256 * SPS_ITEMS - 1) / (256 * SPS_ITEMS))), dim3(256), 0, st,
+                           ncl, W.akey, W.aval, W.c_first, W.pcnt, W.plist, W.pn);
+    });
+    int64_t *const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    seed_piece_pass<false>(ctx, W, nullptr, nullptr, nullptr, nullptr, nullptr, none);
+    HITE_TRY(scan_excl_buf<int32_t>(ctx, bs3, W.pcnt, ncl, W.pfirst, st));
+    hite_prof_end(ctx, tk_pc, st);
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + CS_TOTAL, W.pfirst + ncl, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    W.np = S->pin.h[CS_TOTAL];
+    return HITE_OK;
+}
+
+// the pieces' records, their stable sort by (query segment, subject segment), the sorted table
+static int seed_emit_sorted(hite_ctx *ctx, CopyState *S, SeedWs &W) {
+    Arena &A = S->arena; hipStream_t st = W.st; const int64_t np = W.np;
+    unsigned long long *okey; unsigned *oval; int32_t *t_qseg, *t_sseg; int64_t *t_q[4];
+    HITE_TRY(arena_get(ctx, A, (size_t)(np + 1), &okey, &oval, &t_qseg, &t_sseg, &W.f_qseg, &W.f_sseg));
+    for (int i = 0; i < 4; i++) {
+        HITE_TRY(arena_get(ctx, A, (size_t)(np + 1), &t_q[i], &W.f_q[i]));
+    }
+    int tk_hs = hite_prof_begin(ctx, "seed_hsp_emit_sort", st);
+    seed_piece_pass<true>(ctx, W, W.pfirst, okey, oval, t_qseg, t_sseg, t_q);
+    Sorter so;
+    HITE_TRY(sorter_from_arena(so, ctx, A, st, np));
+    HITE_TRY(sorter_sort(so, okey, oval, np, 32));
+    hipLaunchKernelGGL(seed_gather_kernel, CGRID(np), 0, st, np, oval, t_qseg, t_sseg, t_q[0], t_q[1], t_q[2], t_q[3], W.f_qseg, W.f_sseg, W.f_q[0],
+                       W.f_q[1], W.f_q[2], W.f_q[3]);
+    hite_prof_end(ctx, tk_hs, st);
+    HITE_CHECK(ctx, hipGetLastError());
+    HITE_CHECK(ctx, hipStreamSynchronize(st));
+    return HITE_OK;
+}
+
 static int seed_allvsall_impl(hite_ctx *ctx, void **state_io, int64_t seg_len, int64_t max_anchors, int64_t cap,
                               int32_t *qseg, int32_t *sseg, int64_t *qs, int64_t *qe, int64_t *ss, int64_t *se,
-                              int64_t *n_out, int64_t *stats_out, void **dev_out);
+                              int64_t *n_out, int64_t *stats_out, void **dev_out /* 6 pointers, or NULL: copy to the host arrays */) {
+    if (!ctx || !ctx->d_bases || !state_io || seg_len <= 0 || !n_out) return HITE_EINVAL;
+    HITE_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!*state_io || ((CopyState *)*state_io)->restricted) HITE_TRY(hite_copy_index_build(ctx, state_io, nullptr));   // seeding walks EVERY minimizer
+    CopyState *S = (CopyState *)*state_io;
+    *n_out = 0;
+    SeedWs W;
+    W.st = nullptr; W.M = S->M; W.G = ctx->n_bases; W.seg_len = seg_len;
+    if (stats_out) { stats_out[0] = W.M; stats_out[1] = stats_out[2] = stats_out[3] = 0; }
+    if (W.M == 0) return HITE_OK;
+    HITE_TRY(arena_reset(ctx, S->arena, true));
+    // segment bases per contig
+    std::vector<int32_t> hbase(ctx->n_contigs + 1);          // (hbase[0] = 0)
+    for (int c = 0; c < ctx->n_contigs; c++) {
+        const int64_t L = ctx->h_contig_off[c + 1] - ctx->h_contig_off[c];
+        hbase[c + 1] = hbase[c] + (int32_t)(L > 0 ? (L + seg_len - 1) / seg_len : 1);
+    }
+    if (hbase[ctx->n_contigs] >= 65536) return HITE_EINVAL;   // segment ids are packed into 16 bits of the final sort key
+    HITE_TRY(arena_get(ctx, S->arena, (size_t)(ctx->n_contigs + 1), &W.seg_base));
+    HITE_CHECK(ctx, hipMemcpyAsync(W.seg_base, hbase.data(), (size_t)(ctx->n_contigs + 1) * 4, hipMemcpyHostToDevice, W.st));
+    W.shard = seed_shard_of(ctx, W.G);
+    HITE_TRY(seed_runs_counts(ctx, S, W));
+    if (stats_out) stats_out[1] = W.na;
+    if (W.na == 0) return HITE_OK;
+    if (W.na > max_anchors || W.na >= 0xffffffffll) return HITE_ECAP;
+    // HITE_SEED_PACK=0 (tests): the unpacked records also where the packed ones fit
+    W.packed = copy_knobs().seed_pack && W.G <= SEED_PACK_MAXG;
+    HITE_TRY(seed_anchors_sorted(ctx, S, W));
+    HITE_TRY(seed_clusters(ctx, S, W));
+    if (stats_out) stats_out[2] = W.ncl;
+    HITE_TRY(seed_pieces(ctx, S, W));
+    const int64_t np = *n_out = W.np;
+    if (stats_out) stats_out[3] = np;
+    if (np == 0) return HITE_OK;
+    if ((!dev_out && np > cap) || np >= 0xffffffffll) return HITE_ECAP;
+    HITE_TRY(seed_emit_sorted(ctx, S, W));
+    void *const from[6] = {W.f_qseg, W.f_sseg, W.f_q[0], W.f_q[1], W.f_q[2], W.f_q[3]};
+    void *const to[6] = {qseg, sseg, qs, qe, ss, se};
+    for (int i = 0; i < 6; i++) {
+        if (dev_out) dev_out[i] = from[i];
+        else HITE_CHECK(ctx, hipMemcpy(to[i], from[i], (size_t)np * (i < 2 ? 4 : 8), hipMemcpyDeviceToHost));
+    }
+    return HITE_OK;
+}
 // device-resident form: the six arrays stay in the index state's arena (valid until the next call that uses the state)
 extern "C" int hite_seed_allvsall_dev(hite_ctx *ctx, void **state_io, int64_t seg_len, int64_t max_anchors, int32_t **d_qseg,
                                       int32_t **d_sseg, int64_t **d_qs, int64_t **d_qe, int64_t **d_ss, int64_t **d_se, int64_t *n_out,
@@ -2407,201 +2628,4 @@ extern "C" int hite_seed_allvsall(hite_ctx *ctx, void **state_io, int64_t seg_le
                                   int64_t *n_out, int64_t *stats_out /* 4 x int64 or NULL: seeds, anchors, clusters, records */) {
     if (cap < 0) return HITE_EINVAL;
     return seed_allvsall_impl(ctx, state_io, seg_len, max_anchors, cap, qseg, sseg, qs, qe, ss, se, n_out, stats_out, nullptr);
-}
-static int seed_allvsall_impl(hite_ctx *ctx, void **state_io, int64_t seg_len, int64_t max_anchors, int64_t cap,
-                              int32_t *qseg, int32_t *sseg, int64_t *qs, int64_t *qe, int64_t *ss, int64_t *se,
-                              int64_t *n_out, int64_t *stats_out, void **dev_out /* 6 pointers, or NULL: copy to the host arrays */) {
-    if (!ctx || !ctx->d_bases || !state_io || seg_len <= 0 || !n_out) return HITE_EINVAL;
-    HITE_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = nullptr;
-    if (!*state_io || ((CopyState *)*state_io)->restricted) CCHK(hite_copy_index_build(ctx, state_io, nullptr));   // seeding walks EVERY minimizer
-    CopyState *S = (CopyState *)*state_io;
-    *n_out = 0;
-    const int64_t M = S->M, G = ctx->n_bases;
-    if (stats_out) { stats_out[0] = M; stats_out[1] = stats_out[2] = stats_out[3] = 0; }
-    if (M == 0) return HITE_OK;
-    CCHK(arena_reset(ctx, S->arena, true));
-    Arena &A = S->arena;
-    void *p;
-    // segment bases per contig
-    std::vector<int32_t> hbase(ctx->n_contigs + 1);
-    hbase[0] = 0;
-    for (int c = 0; c < ctx->n_contigs; c++) {
-        const int64_t L = ctx->h_contig_off[c + 1] - ctx->h_contig_off[c];
-        hbase[c + 1] = hbase[c] + (int32_t)(L > 0 ? (L + seg_len - 1) / seg_len : 1);
-    }
-    if (hbase[ctx->n_contigs] >= 65536) return HITE_EINVAL;   // segment ids are packed into 16 bits of the final sort key
-    int32_t *seg_base;
-    CCHK(arena_alloc(ctx, A, (size_t)(ctx->n_contigs + 1) * 4, &p)); seg_base = (int32_t *)p;
-    HITE_CHECK(ctx, hipMemcpyAsync(seg_base, hbase.data(), (size_t)(ctx->n_contigs + 1) * 4, hipMemcpyHostToDevice, st));
-    int tk_rc = hite_prof_begin(ctx, "seed_runs_count", st);
-    // runs of equal hs >> 1 in the index; per seed -- in position order, the rank the index build left in idx_t -- its partner count
-    // and its record (index entry, place in its run)
-    // HITE_SEED_COUNT2=0: the run arrays (flags, scan, first-of-run) and the thread-per-entry kernel of round 5
-    static const bool count2 = [] { const char *e = getenv("HITE_SEED_COUNT2"); return !(e && *e == '0'); }();
-    int32_t *rflag = nullptr, *cnt; int64_t *rid = nullptr, *bs, *aoff; unsigned *run_first = nullptr; uint2 *srec;
-    if (!count2) {
-        CCHK(arena_alloc(ctx, A, (size_t)(M + 1) * 4, &p)); rflag = (int32_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(M + 2) * 8, &p)); rid = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(M + 2) * 4, &p)); run_first = (unsigned *)p;
-    }
-    CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(M) * 8, &p)); bs = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(M + 1) * 4, &p)); cnt = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(M + 2) * 8, &p)); aoff = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(M + 1) * 8, &p)); srec = (uint2 *)p;
-    const dim3 c2grid((unsigned)((M + SC_TILE - 1) / SC_TILE));
-    if (!count2) {
-        hipLaunchKernelGGL(seed_runflag_kernel, CGRID(M), 0, st, M, S->idx_hs, rflag);
-        CCHK(scan_excl_buf<int32_t>(ctx, bs, rflag, M, rid, st));
-        hipLaunchKernelGGL(seed_runfirst_kernel, CGRID(M), 0, st, M, rflag, rid, run_first);
-    }
-    const SeedShard shard = seed_shard_of(ctx, G);
-    // HITE_SEED_PLACE=0 / 1 (tests): never / always through the grouped form
-    static const int place_mode = [] { const char *e = getenv("HITE_SEED_PLACE"); return e && *e ? atoi(e) : -1; }();
-    if (place_mode == 1 || (place_mode != 0 && M >= RS_WIDE_MIN)) {
-        unsigned long long *pk; unsigned *pv;
-        CCHK(arena_alloc(ctx, A, (size_t)(M + 1) * 8, &p)); pk = (unsigned long long *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(M + 1) * 4, &p)); pv = (unsigned *)p;
-        Sorter sp;
-        CCHK(sorter_from_arena(sp, ctx, A, st, M));
-        if (count2) hipLaunchKernelGGL(seed_count2_kernel<true>, c2grid, dim3(256), 0, st, M, G, S->idx_hs, S->idx_key, S->idx_t, shard, srec, pk, pv);
-        else hipLaunchKernelGGL(seed_count_kernel<true>, CGRID(M), 0, st, M, G, rflag, rid, run_first, S->idx_key, S->idx_t, shard, srec, pk, pv);
-        int mb = 1;
-        while (mb < 32 && (1ll << mb) < M) mb++;                  // ranks < 2^mb
-        const int shift = mb > 10 ? mb - 10 : 0;
-        CCHK(sorter_sort_bits_swap(sp, &pk, &pv, M, shift, shift + (M >= RS_WIDE_MIN ? 10 : 8)));       // ONE pass
-        const int nb = (int)((M + 256 * SPL_ITEMS - 1) / (256 * SPL_ITEMS));
-        // what keeps the window inside an L2 (4 MB): two workgroups per compute unit -- 64 KB of LDS asked for, none used --, i.e. 131 k
-        // records of a chiplet in flight, half a group; and the counts NOT scattered beside the records (a second window): seed_cnt_kernel
-        // reads them back in order.  1 Gbp, 182 M seeds, seed_runs_count: direct scatter 10.7 ms; grouped 9.1; without the counts 7.8;
-        // with the LDS cap 7.1.
-        static const int place_lds = [] { const char *e = getenv("HITE_SEED_PLACE_LDS"); return e && *e ? atoi(e) : 65536; }();
-        static const bool place_cnt = [] { const char *e = getenv("HITE_SEED_PLACE_CNT"); return e && *e == '1'; }();
-        hipLaunchKernelGGL(seed_place_kernel, dim3((unsigned)nb), dim3(256), (size_t)place_lds, st, M, nb, pk, pv, srec, place_cnt ? cnt : (int32_t *)nullptr);
-        if (!place_cnt) hipLaunchKernelGGL(seed_cnt_kernel, CGRID(M), 0, st, M, srec, cnt);
-    } else {
-        if (count2) hipLaunchKernelGGL(seed_count2_kernel<false>, c2grid, dim3(256), 0, st, M, G, S->idx_hs, S->idx_key, S->idx_t, shard, srec,
-                                       (unsigned long long *)nullptr, (unsigned *)nullptr);
-        else hipLaunchKernelGGL(seed_count_kernel<false>, CGRID(M), 0, st, M, G, rflag, rid, run_first, S->idx_key, S->idx_t, shard, srec,
-                                (unsigned long long *)nullptr, (unsigned *)nullptr);
-        hipLaunchKernelGGL(seed_cnt_kernel, CGRID(M), 0, st, M, srec, cnt);
-    }
-    CCHK(scan_excl_buf<int32_t>(ctx, bs, cnt, M, aoff, st));
-    hite_prof_end(ctx, tk_rc, st);
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, aoff + M, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(read_back(ctx, S, st, 1));
-    const int64_t na = S->h_pin[0];
-    if (stats_out) stats_out[1] = na;
-    if (na == 0) return HITE_OK;
-    if (na > max_anchors || na >= 0xffffffffll) return HITE_ECAP;
-    // HITE_SEED_PACK=0 (tests): the unpacked records also where the packed ones fit
-    static const bool pack_ok = [] { const char *e = getenv("HITE_SEED_PACK"); return !(e && *e == '0'); }();
-    const bool packed = pack_ok && G <= SEED_PACK_MAXG;
-    unsigned long long *akey; unsigned *aval = nullptr;
-    CCHK(arena_alloc(ctx, A, (size_t)(na + 1) * 8, &p)); akey = (unsigned long long *)p;
-    if (!packed) { CCHK(arena_alloc(ctx, A, (size_t)(na + 1) * 4, &p)); aval = (unsigned *)p; }
-    {
-        int tk = hite_prof_begin(ctx, "seed_anchor", st);
-        const dim3 cgrid((unsigned)((M + 255) / 256));
-        if (shard.sharded) {
-            if (packed) hipLaunchKernelGGL(seed_anchor_kernel<true>, CGRID(M), 0, st, M, G, srec, S->idx_key, cnt, aoff, shard, akey, aval);
-            else hipLaunchKernelGGL(seed_anchor_kernel<false>, CGRID(M), 0, st, M, G, srec, S->idx_key, cnt, aoff, shard, akey, aval);
-        } else if (packed) hipLaunchKernelGGL(seed_anchor_coop_kernel<true>, cgrid, dim3(256), 0, st, M, G, srec, S->idx_key, aoff, akey, aval);
-        else hipLaunchKernelGGL(seed_anchor_coop_kernel<false>, cgrid, dim3(256), 0, st, M, G, srec, S->idx_key, aoff, akey, aval);
-        hite_prof_end(ctx, tk, st);
-    }
-    {
-        // stable sort on (strand, diagonal >> 6); after an odd number of passes the sorted records sit in the sorter's buffers
-        // (no copy back: akey / aval are re-pointed)
-        int tk = hite_prof_begin(ctx, "seed_anchor_sort", st);
-        Sorter so;
-        CCHK(sorter_from_arena(so, ctx, A, st, na, !packed));
-        if (packed) { unsigned *nov = nullptr; CCHK(sorter_sort_bits_swap(so, &akey, &nov, na, 36, 62)); }
-        else CCHK(sorter_sort_bits_swap(so, &akey, &aval, na, 6, 35));
-        hite_prof_end(ctx, tk, st);
-    }
-    // clusters: starts per tile of 2048 anchors -> scan -> the index of every cluster's first anchor (+ sentinel)
-    int tk_cl = hite_prof_begin(ctx, "seed_clusters", st);
-    const int64_t ntile = (na + SF_TILE - 1) / SF_TILE;
-    int32_t *tcnt; int64_t *tfirst, *bs2; unsigned *c_first;
-    CCHK(arena_alloc(ctx, A, (size_t)(ntile + 1) * 4, &p)); tcnt = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(ntile + 2) * 8, &p)); tfirst = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(ntile) * 8, &p)); bs2 = (int64_t *)p;
-    uint8_t *sbits;
-    CCHK(arena_alloc(ctx, A, (size_t)ntile * 256, &p)); sbits = (uint8_t *)p;
-    if (packed) hipLaunchKernelGGL(seed_clusters_kernel<true>, dim3((unsigned)ntile), dim3(256), 0, st, na, G, akey, aval, ctx->d_contig_off, ctx->n_contigs, tcnt, sbits);
-    else hipLaunchKernelGGL(seed_clusters_kernel<false>, dim3((unsigned)ntile), dim3(256), 0, st, na, G, akey, aval, ctx->d_contig_off, ctx->n_contigs, tcnt, sbits);
-    CCHK(scan_excl_buf<int32_t>(ctx, bs2, tcnt, ntile, tfirst, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, tfirst + ntile, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(read_back(ctx, S, st, 1));
-    const int64_t ncl = S->h_pin[0];
-    if (stats_out) stats_out[2] = ncl;
-    CCHK(arena_alloc(ctx, A, (size_t)(ncl + 2) * 4, &p)); c_first = (unsigned *)p;
-    hipLaunchKernelGGL(seed_cluster_emit_kernel, dim3((unsigned)ntile), dim3(256), 0, st, na, sbits, (const int64_t *)tfirst, c_first);
-    hite_prof_end(ctx, tk_cl, st);
-    // pieces: count, scan, emit
-    int tk_pc = hite_prof_begin(ctx, "seed_pieces", st);
-    int32_t *pcnt; int64_t *pfirst, *bs3;
-    CCHK(arena_alloc(ctx, A, (size_t)(ncl + 1) * 4, &p)); pcnt = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(ncl + 2) * 8, &p)); pfirst = (int64_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)scan_tmp_elems(ncl) * 8, &p)); bs3 = (int64_t *)p;
-    unsigned *plist; unsigned long long *pn;       // the clusters that can be an HSP (each holds >= SEED_MINANCH anchors)
-    CCHK(arena_alloc(ctx, A, (size_t)(na / SEED_MINANCH + 64) * 4, &p)); plist = (unsigned *)p;
-    CCHK(arena_alloc(ctx, A, 16, &p)); pn = (unsigned long long *)p;
-    HITE_CHECK(ctx, hipMemsetAsync(pn, 0, 16, st));
-    if (packed) hipLaunchKernelGGL(HIP_KERNEL_NAME(seed_piece_select_kernel<true>), dim3((unsigned)((ncl + 256 * SPS_ITEMS - 1) / (256 * SPS_ITEMS))), dim3(256), 0, st, ncl, akey, aval, c_first, pcnt, plist, pn);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(seed_piece_select_kernel<false>), dim3((unsigned)((ncl + 256 * SPS_ITEMS - 1) / (256 * SPS_ITEMS))), dim3(256), 0, st, ncl, akey, aval, c_first, pcnt, plist, pn);
-    const dim3 pgrid(8192);       // (both passes stride over the list, whose length stays on the device)
-#define SEED_PIECE_COUNT(PKV) hipLaunchKernelGGL(HIP_KERNEL_NAME(seed_piece_kernel<false, PKV>), pgrid, dim3(256), 0, st, ncl, G, seg_len, akey, aval, c_first, ctx->d_contig_off, ctx->n_contigs, \
-                       seg_base, pcnt, (const int64_t *)nullptr, (unsigned long long *)nullptr, (unsigned *)nullptr, (int32_t *)nullptr, \
-                       (int32_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr, plist, pn)
-    if (packed) SEED_PIECE_COUNT(true); else SEED_PIECE_COUNT(false);
-#undef SEED_PIECE_COUNT
-    CCHK(scan_excl_buf<int32_t>(ctx, bs3, pcnt, ncl, pfirst, st));
-    hite_prof_end(ctx, tk_pc, st);
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, pfirst + ncl, 8, hipMemcpyDeviceToDevice, st));
-    CCHK(read_back(ctx, S, st, 1));
-    const int64_t np = S->h_pin[0];
-    *n_out = np;
-    if (stats_out) stats_out[3] = np;
-    if (np == 0) return HITE_OK;
-    if (!dev_out && np > cap) return HITE_ECAP;
-    if (np >= 0xffffffffll) return HITE_ECAP;
-    unsigned long long *okey; unsigned *oval; int32_t *t_qseg, *t_sseg, *f_qseg, *f_sseg; int64_t *t_q[4], *f_q[4];
-    CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 8, &p)); okey = (unsigned long long *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 4, &p)); oval = (unsigned *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 4, &p)); t_qseg = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 4, &p)); t_sseg = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 4, &p)); f_qseg = (int32_t *)p;
-    CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 4, &p)); f_sseg = (int32_t *)p;
-    for (int i = 0; i < 4; i++) {
-        CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 8, &p)); t_q[i] = (int64_t *)p;
-        CCHK(arena_alloc(ctx, A, (size_t)(np + 1) * 8, &p)); f_q[i] = (int64_t *)p;
-    }
-#define SEED_PIECE_EMIT(PKV) hipLaunchKernelGGL(HIP_KERNEL_NAME(seed_piece_kernel<true, PKV>), pgrid, dim3(256), 0, st, ncl, G, seg_len, akey, aval, c_first, ctx->d_contig_off, ctx->n_contigs, \
-                       seg_base, pcnt, (const int64_t *)pfirst, okey, oval, t_qseg, t_sseg, t_q[0], t_q[1], t_q[2], t_q[3], plist, pn)
-    int tk_hs = hite_prof_begin(ctx, "seed_hsp_emit_sort", st);
-    if (packed) SEED_PIECE_EMIT(true); else SEED_PIECE_EMIT(false);
-#undef SEED_PIECE_EMIT
-    {
-        Sorter so;
-        CCHK(sorter_from_arena(so, ctx, A, st, np));
-        CCHK(sorter_sort(so, okey, oval, np, 32));
-    }
-    hipLaunchKernelGGL(seed_gather_kernel, CGRID(np), 0, st, np, oval, t_qseg, t_sseg, t_q[0], t_q[1], t_q[2], t_q[3], f_qseg, f_sseg, f_q[0],
-                       f_q[1], f_q[2], f_q[3]);
-    hite_prof_end(ctx, tk_hs, st);
-    HITE_CHECK(ctx, hipGetLastError());
-    HITE_CHECK(ctx, hipStreamSynchronize(st));
-    if (dev_out) {
-        dev_out[0] = f_qseg; dev_out[1] = f_sseg; dev_out[2] = f_q[0]; dev_out[3] = f_q[1]; dev_out[4] = f_q[2]; dev_out[5] = f_q[3];
-        return HITE_OK;
-    }
-    HITE_CHECK(ctx, hipMemcpy(qseg, f_qseg, (size_t)np * 4, hipMemcpyDeviceToHost));
-    HITE_CHECK(ctx, hipMemcpy(sseg, f_sseg, (size_t)np * 4, hipMemcpyDeviceToHost));
-    HITE_CHECK(ctx, hipMemcpy(qs, f_q[0], (size_t)np * 8, hipMemcpyDeviceToHost));
-    HITE_CHECK(ctx, hipMemcpy(qe, f_q[1], (size_t)np * 8, hipMemcpyDeviceToHost));
-    HITE_CHECK(ctx, hipMemcpy(ss, f_q[2], (size_t)np * 8, hipMemcpyDeviceToHost));
-    HITE_CHECK(ctx, hipMemcpy(se, f_q[3], (size_t)np * 8, hipMemcpyDeviceToHost));
-    return HITE_OK;
 }

@@ -1,5 +1,5 @@
 // hite_hostbuf.h -- what the host wrappers share: the owner of a call's temporary device buffers, the layout of a block carved from
-// the context's scratch, and the checks of offset tables and of pairs of intervals.
+// the context's scratch, the pinned scalars of a driver, and the checks of offset tables and of pairs of intervals.
 #pragma once
 #include "hite_common.h"
 #include <initializer_list>
@@ -31,6 +31,32 @@ struct DevPool {
         const hipError_t e = bufs.back().alloc(bytes);
         out = bufs.back().as<T>();
         return e;
+    }
+};
+
+// The scalars a driver reads back: SCAL_WORDS words on the device (`d`), where scans and kernels leave totals and counters, and
+// their pinned mirror (`h`).  The owner gives the words their meaning (CopySlot in hite_copies.hip, the pipeline's numbers).
+#define SCAL_WORDS 64
+template <typename TIn> static int scan_excl_buf(hite_ctx *, int64_t *, const TIn *, int64_t, int64_t *, hipStream_t);      // (hite_scan.h)
+struct ScalPin {
+    int64_t *h = nullptr, *d = nullptr;
+    hipError_t alloc() {
+        const hipError_t e = hipHostMalloc((void **)&h, SCAL_WORDS * sizeof(int64_t));
+        return e != hipSuccess ? e : hipMalloc((void **)&d, SCAL_WORDS * sizeof(int64_t));
+    }
+    void release() { if (h) (void)hipHostFree(h); if (d) (void)hipFree(d); h = d = nullptr; }
+    // words [0, count) to the host; synchronises the stream
+    int read_back(hite_ctx *ctx, hipStream_t st, int count) {
+        HITE_CHECK(ctx, hipMemcpyAsync(h, d, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
+        HITE_CHECK(ctx, hipStreamSynchronize(st));
+        return HITE_OK;
+    }
+    // exclusive scan of n counters into out[n + 1] (bs: scan_tmp_elems(n) words; a caller includes hite_scan.h); the total goes to word `slot`
+    template <class TIn>
+    int scan_total(hite_ctx *ctx, hipStream_t st, int64_t *bs, const TIn *in, int64_t n, int64_t *out, int slot) {
+        HITE_TRY(scan_excl_buf<TIn>(ctx, bs, in, n, out, st));
+        HITE_CHECK(ctx, hipMemcpyAsync(d + slot, out + n, 8, hipMemcpyDeviceToDevice, st));
+        return HITE_OK;
     }
 };
 

@@ -30,8 +30,7 @@ extern "C" int hite_judge_classify_dev(hite_ctx *ctx, int32_t n, const int32_t *
 
 struct PipeState {
     Arena keep, tmp;
-    int64_t *h_pin = nullptr;  // pinned scalars for read-backs
-    int64_t *d_scal = nullptr;
+    ScalPin pin;               // pinned scalars for read-backs
 };
 
 extern "C" void hite_pipeline_release(void *state) {
@@ -39,17 +38,15 @@ extern "C" void hite_pipeline_release(void *state) {
     if (!s) return;
     arena_free(s->keep);
     arena_free(s->tmp);
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
-    if (s->d_scal) (void)hipFree(s->d_scal);
+    s->pin.release();
     delete s;
 }
 
 template <typename TIn>
 static int scan_excl(hite_ctx *ctx, Arena &tmp, const TIn *d_in, int64_t n, int64_t *d_out /* n+1 */, hipStream_t st) {
-    void *bs = nullptr;
-    int rc = arena_alloc(ctx, tmp, (size_t)scan_tmp_elems(n) * 8, &bs);
-    if (rc) return rc;
-    return scan_excl_buf<TIn>(ctx, (int64_t *)bs, d_in, n, d_out, st);
+    int64_t *bs = nullptr;
+    HITE_TRY(arena_get(ctx, tmp, (size_t)scan_tmp_elems(n), &bs));
+    return scan_excl_buf<TIn>(ctx, bs, d_in, n, d_out, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -559,14 +556,6 @@ struct PassOut {
 };
 struct StageTimes;  // (events are recorded by bench.py around the whole call; per-kernel via rocprof)
 
-static int read_scalars(hite_ctx *ctx, PipeState *S, hipStream_t st, int count) {
-    HITE_CHECK(ctx, hipMemcpyAsync(S->h_pin, S->d_scal, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
-    HITE_CHECK(ctx, hipStreamSynchronize(st));
-    return HITE_OK;
-}
-
-#define ACHK(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
-
 // The front of a pass: the rows of every candidate (select_rows_kernel), their place in the batch (scan), what each row is
 // (row_meta_kernel), where its window lies (scan), and the windows themselves (row_gather_kernel) -- with the sizes of the
 // alignment's ops the stage needs next.  Shared by run_pass and by hite_fine_rows (the rows of a pass by themselves), so that the
@@ -586,70 +575,65 @@ static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_
     int32_t *nrows, *sel, *row_first32, *row_copy, *row_len, *row_pad;
     int64_t *row_first, *win_off, *ops_cnt, *ops_base;
     uint8_t *row_trunc, *win;
-    void *p;
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); nrows = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)n * MAXROWS * 4, &p)); sel = (int32_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &nrows));
+    HITE_TRY(arena_get(ctx, T, (size_t)n * MAXROWS, &sel));
     int tk = hite_prof_begin(ctx, "select_rows_kernel", st);
     hipLaunchKernelGGL(select_rows_kernel, dim3(n), dim3(256), 0, st, n, d_copy_first, d_len, d_mode, d_contig, d_s1, d_e1, d_minus,
                        (const int32_t *)ctx->d_contig_rank, nrows, sel);
     hite_prof_end(ctx, tk, st);
-    ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 8, &p)); row_first = (int64_t *)p;
-    ACHK(scan_excl<int32_t>(ctx, T, nrows, n, row_first, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, row_first + n, 8, hipMemcpyDeviceToDevice, st));
-    ACHK(read_scalars(ctx, S, st, 1));
-    const int64_t total_rows = S->h_pin[0];
+    HITE_TRY(arena_get(ctx, T, (size_t)(n + 1), &row_first));
+    HITE_TRY(scan_excl<int32_t>(ctx, T, nrows, n, row_first, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d, row_first + n, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    const int64_t total_rows = S->pin.h[0];
     F.nrows = nrows; F.sel = sel; F.row_first = row_first; F.total_rows = total_rows;
     if (calls_out) {
-        ACHK(arena_alloc(ctx, K, sizeof(hite_call) * (size_t)n, &p)); *calls_out = (hite_call *)p;
+        HITE_TRY(arena_get(ctx, K, (size_t)n, calls_out));
         HITE_CHECK(ctx, hipMemsetAsync(*calls_out, 0, sizeof(hite_call) * (size_t)n, st));
     }
     if (total_rows == 0) return HITE_OK;
     if (total_rows > 0x7fffffff) return HITE_EINVAL;
 
-    ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 4, &p)); row_first32 = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_copy = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_len = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_pad = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)total_rows, &p)); row_trunc = (uint8_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)(n + 1), &row_first32));
+    HITE_TRY(arena_get(ctx, T, (size_t)total_rows, &row_copy, &row_len, &row_pad, &row_trunc));
     int32_t *row_cp0 = nullptr;
-    if (d_clip) { ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_cp0 = (int32_t *)p; }
+    if (d_clip) { HITE_TRY(arena_get(ctx, T, (size_t)total_rows, &row_cp0)); }
     const bool chunks = hite_sw(ctx, HITE_SW_GATHER_CHUNKS) != 0;
     GatherRow *desc = nullptr;
     int32_t *row_items = nullptr;
     int64_t *item_start = nullptr;
     if (chunks) {
-        ACHK(arena_alloc(ctx, T, (size_t)total_rows * sizeof(GatherRow), &p)); desc = (GatherRow *)p;
-        ACHK(arena_alloc(ctx, T, (size_t)total_rows * 4, &p)); row_items = (int32_t *)p;
-        ACHK(arena_alloc(ctx, T, (size_t)(total_rows + 1) * 8, &p)); item_start = (int64_t *)p;
+        HITE_TRY(arena_get(ctx, T, (size_t)total_rows, &desc, &row_items));
+        HITE_TRY(arena_get(ctx, T, (size_t)(total_rows + 1), &item_start));
     }
-    HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
+    HITE_CHECK(ctx, hipMemsetAsync(S->pin.d, 0, 64, st));
     hipLaunchKernelGGL(row_meta_kernel, dim3(n), dim3(128), 0, st, n, row_first, nrows, sel, d_mode, d_len, row_first32,
-                       row_copy, row_len, row_pad, row_trunc, (int32_t *)(S->d_scal + 2), d_clip, d_minus, row_cp0,
+                       row_copy, row_len, row_pad, row_trunc, (int32_t *)(S->pin.d + 2), d_clip, d_minus, row_cp0,
                        desc, row_items, (const int64_t *)ctx->d_contig_off, (int32_t)ctx->n_contigs, d_contig, d_s1, d_e1, (int32_t)flank);
-    ACHK(arena_alloc(ctx, T, (size_t)(total_rows + 1) * 8, &p)); win_off = (int64_t *)p;
-    ACHK(scan_excl<int32_t>(ctx, T, row_pad, total_rows, win_off, st));
+    HITE_TRY(arena_get(ctx, T, (size_t)(total_rows + 1), &win_off));
+    HITE_TRY(scan_excl<int32_t>(ctx, T, row_pad, total_rows, win_off, st));
     if (chunks) {
         // the items of every row, counted on the device; their total rides on the read-back below
-        ACHK(scan_excl<int32_t>(ctx, T, row_items, total_rows, item_start, st));
-        HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 6, item_start + total_rows, 8, hipMemcpyDeviceToDevice, st));
+        HITE_TRY(scan_excl<int32_t>(ctx, T, row_items, total_rows, item_start, st));
+        HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + 6, item_start + total_rows, 8, hipMemcpyDeviceToDevice, st));
     }
-    ACHK(arena_alloc(ctx, T, (size_t)n * 8, &p)); ops_cnt = (int64_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 8, &p)); ops_base = (int64_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &ops_cnt));
+    HITE_TRY(arena_get(ctx, T, (size_t)(n + 1), &ops_base));
     hipLaunchKernelGGL(ops_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, row_first, nrows, row_len, ops_cnt,
-                       (unsigned long long *)(S->d_scal + 4));
-    ACHK(scan_excl<int64_t>(ctx, T, ops_cnt, n, ops_base, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, win_off + total_rows, 8, hipMemcpyDeviceToDevice, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 1, ops_base + n, 8, hipMemcpyDeviceToDevice, st));
-    ACHK(read_scalars(ctx, S, st, 7));
-    const int64_t win_bytes = S->h_pin[0];
-    F.win_bytes = win_bytes; F.ops_elems = S->h_pin[1];
-    F.max_len = (int)(((int32_t *)(S->h_pin + 2))[0]);
-    F.align_bytes = S->h_pin[4];  // alignment algorithmic bytes
-    F.steps = S->h_pin[5];        // anti-diagonal steps
+                       (unsigned long long *)(S->pin.d + 4));
+    HITE_TRY(scan_excl<int64_t>(ctx, T, ops_cnt, n, ops_base, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d, win_off + total_rows, 8, hipMemcpyDeviceToDevice, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + 1, ops_base + n, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.read_back(ctx, st, 7));
+    const int64_t win_bytes = S->pin.h[0];
+    F.win_bytes = win_bytes; F.ops_elems = S->pin.h[1];
+    F.max_len = (int)(((int32_t *)(S->pin.h + 2))[0]);
+    F.align_bytes = S->pin.h[4];  // alignment algorithmic bytes
+    F.steps = S->pin.h[5];        // anti-diagonal steps
 
-    ACHK(arena_alloc(ctx, T, (size_t)win_bytes + 64, &p)); win = (uint8_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)win_bytes + 64, &win));
     // (both forms under the one name of the stage table: the item list is part of what the chunk form costs)
-    const int64_t n_items = chunks ? S->h_pin[6] : 0;
+    const int64_t n_items = chunks ? S->pin.h[6] : 0;
     // (row_items says how many items a row is: ceil(row_pad / 4096), none for a row of no bytes; a workgroup takes 4 * GR_WAVE_ITEMS items)
     const int64_t item_groups = (n_items + 4 * GR_WAVE_ITEMS - 1) / (4 * GR_WAVE_ITEMS);
     if (chunks && (n_items < 0 || n_items > win_bytes / (16 * GR_ITEM_CHUNKS) + total_rows || item_groups > 0x7fffffff)) return HITE_EINVAL;
@@ -658,7 +642,7 @@ static int pass_front(hite_ctx *ctx, PipeState *S, int n, const int32_t *d_copy_
         // (no row has a byte: nothing to gather)
     } else if (chunks) {
         uint2 *items;
-        ACHK(arena_alloc(ctx, T, (size_t)n_items * sizeof(uint2), &p)); items = (uint2 *)p;
+        HITE_TRY(arena_get(ctx, T, (size_t)n_items, &items));
         hipLaunchKernelGGL(gather_items_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, st, total_rows, item_start, items);
         hipLaunchKernelGGL(row_gather_chunks_kernel, dim3((unsigned)item_groups), dim3(256), 0, st, (const uint32_t *)ctx->d_bases,
                            (const uint32_t *)ctx->d_nmask, n_items, items, desc, win_off, win);
@@ -683,12 +667,11 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
     int32_t *cols, *status, *eff, *new_cols;
     int64_t *msa_bytes, *msa_off, *col_off2;
     uint8_t *clean;
-    void *p;
     PassFront F;
-    ACHK(pass_front(ctx, S, n, d_copy_first, d_contig, d_s1, d_e1, d_minus, d_clip, flank, d_len, d_mode, &out->calls, F, st));
+    HITE_TRY(pass_front(ctx, S, n, d_copy_first, d_contig, d_s1, d_e1, d_minus, d_clip, flank, d_len, d_mode, &out->calls, F, st));
     const int64_t total_rows = F.total_rows;
     stats[0] += total_rows;
-    if (total_rows == 0) { ACHK(arena_alloc(ctx, K, 256, &p)); out->cons = (uint8_t *)p; return HITE_OK; }
+    if (total_rows == 0) { HITE_TRY(arena_get(ctx, K, 256, &out->cons)); return HITE_OK; }
     stats[1] += F.win_bytes;
     stats[3] += F.align_bytes;
     extra[0] += F.steps;
@@ -699,22 +682,19 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
     uint8_t *const win = F.win;
     int tk;
 
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); cols = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); status = (int32_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); new_cols = (int32_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &cols, &status, &new_cols));
     int32_t *last_extra;
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); last_extra = (int32_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &last_extra));
     // alignment + layout + sparse-column selection: the full alignment is never written
     int32_t *rows_al;
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); rows_al = (int32_t *)p;
-    ACHK(hite_star_msa_sparse_dev(ctx, n, win, win_off, row_len, row_first32, total_rows, ops_base, ops_elems, max_len > 0 ? max_len : 1,
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &rows_al));
+    HITE_TRY(hite_star_msa_sparse_dev(ctx, n, win, win_off, row_len, row_first32, total_rows, ops_base, ops_elems, max_len > 0 ? max_len : 1,
                                   cols, status, new_cols, last_extra, rows_al, st));
-    ACHK(arena_alloc(ctx, T, (size_t)n * 4, &p)); eff = (int32_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &eff));
     hipLaunchKernelGGL(eff_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, rows_al, cols, eff);
-    ACHK(arena_alloc(ctx, T, (size_t)n * 8, &p)); msa_bytes = (int64_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 8, &p)); msa_off = (int64_t *)p;
-    ACHK(arena_alloc(ctx, T, (size_t)(n + 1) * 8, &p)); col_off2 = (int64_t *)p;
-    HITE_CHECK(ctx, hipMemsetAsync(S->d_scal, 0, 64, st));
+    HITE_TRY(arena_get(ctx, T, (size_t)n, &msa_bytes));
+    HITE_TRY(arena_get(ctx, T, (size_t)(n + 1), &msa_off, &col_off2));
+    HITE_CHECK(ctx, hipMemsetAsync(S->pin.d, 0, 64, st));
     // fill fused into the judge, when the judge's LDS kernels are switched on (HITE_JUDGE_LDS=1; HITE_JUDGE_FUSE=0 then makes
     // them copy their alignment from HBM instead): the LDS classes are left out of the fill, their kernels build the alignment
     // from windows + ops + layout words
@@ -722,19 +702,19 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
     {
         const char *e = getenv("HITE_JUDGE_FUSE");
         if (!(e && *e && atoi(e) == 0) && hite_judge_lds_enabled(n)) {
-            ACHK(arena_alloc(ctx, T, (size_t)n + 16, &p)); jcls = (uint8_t *)p;
-            ACHK(hite_judge_classify_dev(ctx, n, eff, new_cols, jcls, st));
+            HITE_TRY(arena_get(ctx, T, (size_t)n + 16, &jcls));
+            HITE_TRY(hite_judge_classify_dev(ctx, n, eff, new_cols, jcls, st));
         }
     }
-    hipLaunchKernelGGL(msa_size_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, eff, new_cols, jcls, msa_bytes, (int32_t *)(S->d_scal + 2));
-    ACHK(scan_excl<int64_t>(ctx, T, msa_bytes, n, msa_off, st));
-    ACHK(scan_excl<int32_t>(ctx, T, new_cols, n, col_off2, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, col_off2 + n, 8, hipMemcpyDeviceToDevice, st));
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal + 1, msa_off + n, 8, hipMemcpyDeviceToDevice, st));
-    ACHK(read_scalars(ctx, S, st, 3));
-    const int64_t msa_total = S->h_pin[1];
+    hipLaunchKernelGGL(msa_size_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, eff, new_cols, jcls, msa_bytes, (int32_t *)(S->pin.d + 2));
+    HITE_TRY(scan_excl<int64_t>(ctx, T, msa_bytes, n, msa_off, st));
+    HITE_TRY(scan_excl<int32_t>(ctx, T, new_cols, n, col_off2, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d, col_off2 + n, 8, hipMemcpyDeviceToDevice, st));
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d + 1, msa_off + n, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.read_back(ctx, st, 3));
+    const int64_t msa_total = S->pin.h[1];
     stats[2] += msa_total;
-    ACHK(arena_alloc(ctx, T, (size_t)msa_total + 64, &p)); clean = (uint8_t *)p;
+    HITE_TRY(arena_get(ctx, T, (size_t)msa_total + 64, &clean));
     tk = hite_prof_begin(ctx, extra == nullptr ? "star_fill_sparse_kernel" : (pass_b ? "star_fill_sparse_kernel_passB" : "star_fill_sparse_kernel_passA"), st);
     // (what the judge's LDS kernels read is what the fill reads: the state of the last hite_star_msa_sparse_dev call)
     struct FuseGuard {      // cleared on every way out: a later stand-alone hite_judge_dev call must not see this pass's buffers
@@ -749,15 +729,15 @@ static int run_pass(hite_ctx *ctx, PipeState *S, int te_type, int plant, int n, 
         F.row_map = ctx->d_msa_row_map; F.rows_eff = ctx->d_msa_rows_eff;
         ctx->judge_fuse = F; ctx->d_judge_cls = jcls;
     }
-    ACHK(hite_star_msa_fill_sparse_dev(ctx, n, win, win_off, row_len, row_first32, ops_base, new_cols, last_extra, msa_off, clean, st));
+    HITE_TRY(hite_star_msa_fill_sparse_dev(ctx, n, win, win_off, row_len, row_first32, ops_base, new_cols, last_extra, msa_off, clean, st));
     hite_prof_end(ctx, tk, st);
-    const int64_t total_cols2 = S->h_pin[0];
+    const int64_t total_cols2 = S->pin.h[0];
     if (cols_acc) *cols_acc += total_cols2;
-    const int max_cols2 = (int)(((int32_t *)(S->h_pin + 2))[0]);
-    ACHK(arena_alloc(ctx, K, (size_t)total_cols2 + 8 * (size_t)n + 64, &p)); out->cons = (uint8_t *)p;
+    const int max_cols2 = (int)(((int32_t *)(S->pin.h + 2))[0]);
+    HITE_TRY(arena_get(ctx, K, (size_t)total_cols2 + 8 * (size_t)n + 64, &out->cons));
     tk = hite_prof_begin(ctx, extra == nullptr ? "judge_kernel" : (pass_b ? "judge_kernel_passB" : "judge_kernel_passA"), st);
     if (max_cols2 > 0)
-        ACHK(hite_judge_dev(ctx, te_type, plant, n, clean, msa_off, eff, new_cols, d_cand, d_cand_off, col_off2, max_cols2,
+        HITE_TRY(hite_judge_dev(ctx, te_type, plant, n, clean, msa_off, eff, new_cols, d_cand, d_cand_off, col_off2, max_cols2,
                             MAXROWS + 1, out->calls, out->cons, st));
     hite_prof_end(ctx, tk, st);
     return HITE_OK;
@@ -857,7 +837,6 @@ static int stage_tables(hite_ctx *ctx, PipeState *S, int32_t n_cand, const uint8
                         const int32_t *d_copy_first, int64_t n_copies, const int32_t *d_contig, const int64_t *d_start1,
                         const int64_t *d_end1, const uint8_t *d_minus, const uint32_t **d_clip_io, int32_t flank, int64_t *len,
                         int32_t *mode_a, hipStream_t st) {
-    void *p;
     if (n_copies > 0)
         hipLaunchKernelGGL(flank_sizes_kernel, dim3((unsigned)((n_copies + 255) / 256)), dim3(256), 0, st, ctx->d_contig_off,
                            ctx->n_contigs, n_copies, d_contig, d_start1, d_end1, flank, len, (int64_t *)nullptr);
@@ -866,7 +845,7 @@ static int stage_tables(hite_ctx *ctx, PipeState *S, int32_t n_cand, const uint8
         // supplies them, so that the rows are padded as the copy finder's own records are -- bare aligned windows, aligned globally
         // against a longer centre, cost a fifth of the calls (profiles/r05_scale_tests.txt)
         uint16_t *est;
-        ACHK(arena_alloc(ctx, S->keep, (size_t)n_copies * 4 + 16, &p)); est = (uint16_t *)p;
+        HITE_TRY(arena_get(ctx, S->keep, (size_t)n_copies * 2 + 8, &est));
         const int tkp = hite_prof_begin(ctx, "clip_probe_kernel", st);
         hipLaunchKernelGGL(clip_probe_kernel, dim3((unsigned)((2 * n_copies + 255) / 256)), dim3(256), 0, st, ctx->d_bases, ctx->d_nmask,
                            ctx->d_contig_off, ctx->n_contigs, n_copies, n_cand, d_copy_first, d_cand, d_cand_off, d_contig, d_start1, d_end1,
@@ -895,46 +874,41 @@ extern "C" int hite_flank_region_align_clip_dev(hite_ctx *ctx, void **state_io, 
     PipeState *S = (PipeState *)*state_io;
     if (!S) {
         S = new PipeState();
-        HITE_CHECK(ctx, hipHostMalloc((void **)&S->h_pin, 64 * sizeof(int64_t)));
-        HITE_CHECK(ctx, hipMalloc((void **)&S->d_scal, 64 * sizeof(int64_t)));
+        HITE_CHECK(ctx, S->pin.alloc());
         *state_io = S;
     }
-    ACHK(arena_reset(ctx, S->keep, true));
-    ACHK(arena_reset(ctx, S->tmp, true));
+    HITE_TRY(arena_reset(ctx, S->keep, true));
+    HITE_TRY(arena_reset(ctx, S->tmp, true));
     int64_t stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    void *p;
     int64_t *len;
     int32_t *mode_a, *mode_b, *src_pass;
     int64_t *keep_len, *out_off;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)(n_copies + 1) * 8, &p)); len = (int64_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); mode_a = (int32_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); mode_b = (int32_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); src_pass = (int32_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 8, &p)); keep_len = (int64_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)(n_cand + 1) * 8, &p)); out_off = (int64_t *)p;
-    ACHK(stage_tables(ctx, S, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_start1, d_end1, d_minus, &d_clip, flank, len,
+    HITE_TRY(arena_get(ctx, S->keep, (size_t)(n_copies + 1), &len));
+    HITE_TRY(arena_get(ctx, S->keep, (size_t)n_cand, &mode_a, &mode_b, &src_pass, &keep_len));
+    HITE_TRY(arena_get(ctx, S->keep, (size_t)(n_cand + 1), &out_off));
+    HITE_TRY(stage_tables(ctx, S, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_start1, d_end1, d_minus, &d_clip, flank, len,
                       mode_a, st));
     PassOut A, B;
-    ACHK(run_pass(ctx, S, te_type, plant, n_cand, d_cand, d_cand_off, d_copy_first, d_contig, d_start1, d_end1, d_minus, d_clip, flank,
+    HITE_TRY(run_pass(ctx, S, te_type, plant, n_cand, d_cand, d_cand_off, d_copy_first, d_contig, d_start1, d_end1, d_minus, d_clip, flank,
                   len, mode_a, &A, stats, stats + 8, stats + 11, false, st));
-    ACHK(arena_reset(ctx, S->tmp, false));
+    HITE_TRY(arena_reset(ctx, S->tmp, false));
     hipLaunchKernelGGL(mode_b_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, mode_a, A.calls, mode_b);
-    ACHK(run_pass(ctx, S, te_type, plant, n_cand, d_cand, d_cand_off, d_copy_first, d_contig, d_start1, d_end1, d_minus, d_clip, flank,
+    HITE_TRY(run_pass(ctx, S, te_type, plant, n_cand, d_cand, d_cand_off, d_copy_first, d_contig, d_start1, d_end1, d_minus, d_clip, flank,
                   len, mode_b, &B, stats + 4, stats + 9, stats + 11, true, st));
     hipLaunchKernelGGL(merge_calls_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, mode_a, A.calls, B.calls, d_calls,
                        src_pass, keep_len);
-    ACHK(scan_excl<int64_t>(ctx, S->tmp, keep_len, n_cand, out_off, st));
+    HITE_TRY(scan_excl<int64_t>(ctx, S->tmp, keep_len, n_cand, out_off, st));
     hipLaunchKernelGGL(copy_cons_kernel, dim3(n_cand), dim3(256), 0, st, n_cand, d_calls, src_pass, A.cons, B.cons, out_off, d_cons,
                        cons_cap);
     HITE_CHECK(ctx, hipGetLastError());
-    HITE_CHECK(ctx, hipMemcpyAsync(S->d_scal, out_off + n_cand, 8, hipMemcpyDeviceToDevice, st));
-    ACHK(read_scalars(ctx, S, st, 1));
-    if (stats_out) { memcpy(stats_out, stats, sizeof stats); stats_out[10] = S->h_pin[0]; }
-    const int64_t cons_need = S->h_pin[0];
+    HITE_CHECK(ctx, hipMemcpyAsync(S->pin.d, out_off + n_cand, 8, hipMemcpyDeviceToDevice, st));
+    HITE_TRY(S->pin.read_back(ctx, st, 1));
+    if (stats_out) { memcpy(stats_out, stats, sizeof stats); stats_out[10] = S->pin.h[0]; }
+    const int64_t cons_need = S->pin.h[0];
     // everything in the two arenas is dead now (the stream is drained): if they grew into several chunks, merge them so that
     // the next call performs no hipMalloc
-    ACHK(arena_reset(ctx, S->keep, true));
-    ACHK(arena_reset(ctx, S->tmp, true));
+    HITE_TRY(arena_reset(ctx, S->keep, true));
+    HITE_TRY(arena_reset(ctx, S->tmp, true));
     if (cons_need > cons_cap) return HITE_ECAP;
     return HITE_OK;
 }
@@ -1045,17 +1019,15 @@ static int fine_rows_dev(hite_ctx *ctx, PipeState *S, int32_t n_cand, const uint
                          int32_t *row_copy, int32_t *row_len, uint8_t *row_trunc, int64_t *win_off, int64_t win_cap, uint8_t *win,
                          int64_t *totals) {
     hipStream_t st = nullptr;
-    void *p;
     int64_t *len;
     int32_t *mode_a, *mode;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)(n_copies + 1) * 8, &p)); len = (int64_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); mode_a = (int32_t *)p;
-    ACHK(arena_alloc(ctx, S->keep, (size_t)n_cand * 4, &p)); mode = (int32_t *)p;
-    ACHK(stage_tables(ctx, S, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_s1, d_e1, d_minus, &d_clip, flank, len, mode_a, st));
+    HITE_TRY(arena_get(ctx, S->keep, (size_t)(n_copies + 1), &len));
+    HITE_TRY(arena_get(ctx, S->keep, (size_t)n_cand, &mode_a, &mode));
+    HITE_TRY(stage_tables(ctx, S, n_cand, d_cand, d_cand_off, d_copy_first, n_copies, d_contig, d_s1, d_e1, d_minus, &d_clip, flank, len, mode_a, st));
     if (pass) hipLaunchKernelGGL(mode_full_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, st, n_cand, mode_a, mode);
     HITE_CHECK(ctx, hipGetLastError());
     PassFront F;
-    ACHK(pass_front(ctx, S, n_cand, d_copy_first, d_contig, d_s1, d_e1, d_minus, d_clip, flank, len, pass ? mode : mode_a, nullptr, F, st));
+    HITE_TRY(pass_front(ctx, S, n_cand, d_copy_first, d_contig, d_s1, d_e1, d_minus, d_clip, flank, len, pass ? mode : mode_a, nullptr, F, st));
     totals[0] = F.total_rows; totals[1] = F.win_bytes; totals[2] = F.max_len; totals[3] = 0;
     HITE_CHECK(ctx, hipMemcpy(nrows, F.nrows, (size_t)n_cand * 4, hipMemcpyDeviceToHost));
     if (F.total_rows > row_cap || F.win_bytes > win_cap) return HITE_ECAP;
@@ -1094,8 +1066,7 @@ extern "C" int hite_fine_rows(hite_ctx *ctx, int32_t n_cand, const uint8_t *cand
     hipLaunchKernelGGL(fold_bytes_kernel, dim3(256), dim3(256), 0, nullptr, (uint8_t *)dc.p, cand_off[n_cand]);
     PipeState *S = new PipeState();
     int rc = HITE_OK;
-    if (hipHostMalloc((void **)&S->h_pin, 64 * sizeof(int64_t)) != hipSuccess || hipMalloc((void **)&S->d_scal, 64 * sizeof(int64_t)) != hipSuccess)
-        rc = HITE_EHIP;
+    if (S->pin.alloc() != hipSuccess) rc = HITE_EHIP;
     if (rc == HITE_OK)
         rc = fine_rows_dev(ctx, S, n_cand, (uint8_t *)dc.p, (int64_t *)dco.p, (int32_t *)dcf.p, n_copies, (int32_t *)dct.p, (int64_t *)ds.p,
                            (int64_t *)de.p, (uint8_t *)dm.p, clip ? (const uint32_t *)dcl.p : nullptr, flank, pass, nrows, row_cap, row_copy,

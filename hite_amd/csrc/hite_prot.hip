@@ -386,12 +386,11 @@ static int prot_lib_build(hite_ctx *ctx, ProtLib *L, const uint8_t *aa, const in
     HITE_CHECK(ctx, hipMemset(L->d_dir, 0, (size_t)(PROT_BUCKETS + 1) * 8));
     if (N == 0) return HITE_OK;
     int rc;
-    void *p;
     uint8_t *d_raw; unsigned long long *d_keys; int32_t *d_cnt; int64_t *d_bs;
-    if ((rc = arena_alloc(ctx, L->arena, (size_t)N, &p))) return rc; d_raw = (uint8_t *)p;
-    if ((rc = arena_alloc(ctx, L->arena, (size_t)(N + 1) * 8, &p))) return rc; d_keys = (unsigned long long *)p;
-    if ((rc = arena_alloc(ctx, L->arena, (size_t)PROT_BUCKETS * 4, &p))) return rc; d_cnt = (int32_t *)p;
-    if ((rc = arena_alloc(ctx, L->arena, (size_t)scan_tmp_elems(PROT_BUCKETS) * 8, &p))) return rc; d_bs = (int64_t *)p;
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)N, &d_raw));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(N + 1), &d_keys));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)PROT_BUCKETS, &d_cnt));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)scan_tmp_elems(PROT_BUCKETS), &d_bs));
     HITE_CHECK(ctx, hipMemcpy(d_raw, aa, (size_t)N, hipMemcpyHostToDevice));
     HITE_CHECK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)PROT_BUCKETS * 4, st));
     int tk = hite_prof_begin(ctx, "prot_kmer_kernel", st);
@@ -402,10 +401,7 @@ static int prot_lib_build(hite_ctx *ctx, ProtLib *L, const uint8_t *aa, const in
     if ((rc = scan_excl_buf<int32_t>(ctx, d_bs, d_cnt, PROT_BUCKETS, L->d_dir, st))) return rc;
     // the fill: a stable sort by bucket leaves every bucket's entries in position order (positions without a seed go behind them all)
     Sorter S;
-    tl_sort_arena = &L->arena;
-    rc = sorter_init(S, ctx, st, N);
-    tl_sort_arena = nullptr;
-    if (rc) return rc;
+    HITE_TRY(sorter_init_in(S, ctx, &L->arena, st, N));
     tk = hite_prof_begin(ctx, "prot_index_sort", st);
     rc = sorter_sort(S, d_keys, L->d_ent, N, 18);
     hite_prof_end(ctx, tk, st);
@@ -593,13 +589,6 @@ extern "C" int hite_protein_hsp_filter(int64_t n, const int32_t *score, const in
 }
 
 // ---- host: the search -------------------------------------------------------------------------------------------------------------------
-#define PROT_ALLOC(ptr, type, bytes)                                            \
-    do {                                                                        \
-        void *p__;                                                              \
-        if ((rc = arena_alloc(ctx, L->arena, (size_t)(bytes), &p__))) return rc; \
-        ptr = (type)p__;                                                        \
-    } while (0)
-
 struct ProtOut { int32_t q, prot, f, qs, qe, ss, se, score, ident, cols; };
 
 static int prot_search(hite_ctx *ctx, ProtLib *L, int64_t nq, const uint8_t *nt, const int64_t *nt_off, double evalue,
@@ -620,14 +609,13 @@ static int prot_search(hite_ctx *ctx, ProtLib *L, int64_t nq, const uint8_t *nt,
     if (R == 0 || L->n_res == 0) return HITE_OK;
     if ((rc = arena_reset(ctx, L->arena, true))) return rc;
     uint8_t *d_nt, *d_fr; int64_t *d_off, *d_foff, *d_hit_off, *d_bs; int32_t *d_key, *d_cnt;
-    PROT_ALLOC(d_nt, uint8_t *, nb + 16);
-    PROT_ALLOC(d_fr, uint8_t *, R + 16);
-    PROT_ALLOC(d_off, int64_t *, (nq + 1) * 8);
-    PROT_ALLOC(d_foff, int64_t *, (NF + 1) * 8);
-    PROT_ALLOC(d_key, int32_t *, R * 4);
-    PROT_ALLOC(d_cnt, int32_t *, R * 4);
-    PROT_ALLOC(d_hit_off, int64_t *, (R + 1) * 8);
-    PROT_ALLOC(d_bs, int64_t *, scan_tmp_elems(R) * 8);
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(nb + 16), &d_nt));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(R + 16), &d_fr));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(nq + 1), &d_off));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(NF + 1), &d_foff));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)R, &d_key, &d_cnt));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(R + 1), &d_hit_off));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)scan_tmp_elems(R), &d_bs));
     HITE_CHECK(ctx, hipMemcpy(d_nt, nt + nt_off[0], (size_t)nb, hipMemcpyHostToDevice));
     HITE_CHECK(ctx, hipMemcpy(d_off, rel.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice));
     HITE_CHECK(ctx, hipMemcpy(d_foff, foff.data(), (size_t)(NF + 1) * 8, hipMemcpyHostToDevice));
@@ -647,11 +635,10 @@ static int prot_search(hite_ctx *ctx, ProtLib *L, int64_t nq, const uint8_t *nt,
 
     // ungapped filter; the survivors are counted exactly, so a second run with room for all of them is the only retry there can be
     unsigned long long *d_k1 = nullptr, *d_k2 = nullptr, *d_count;
-    PROT_ALLOC(d_count, unsigned long long *, 8);
+    HITE_TRY(arena_get(ctx, L->arena, 1, &d_count));
     int64_t cap = n_hits < (1 << 20) ? n_hits : (1 << 20), n_surv = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        PROT_ALLOC(d_k1, unsigned long long *, (cap + 1) * 8);
-        PROT_ALLOC(d_k2, unsigned long long *, (cap + 1) * 8);
+        HITE_TRY(arena_get(ctx, L->arena, (size_t)(cap + 1), &d_k1, &d_k2));
         HITE_CHECK(ctx, hipMemsetAsync(d_count, 0, 8, st));
         ProtUngapArgs a;
         a.fr = d_fr; a.frame_off = d_foff; a.n_frames = NF; a.aa = L->d_aa; a.aa_off = L->d_aa_off; a.prot_of = L->d_prot_of;
@@ -672,19 +659,12 @@ static int prot_search(hite_ctx *ctx, ProtLib *L, int64_t nq, const uint8_t *nt,
 
     // order (two stable stages: (diagonal, segment), then (frame, protein)) and keep each survivor once
     unsigned *d_idx; unsigned long long *d_g1, *d_g2, *d_u1, *d_u2; int32_t *d_flag; int64_t *d_pos, *d_bs2;
-    PROT_ALLOC(d_idx, unsigned *, (n_surv + 1) * 4);
-    PROT_ALLOC(d_g1, unsigned long long *, (n_surv + 1) * 8);
-    PROT_ALLOC(d_g2, unsigned long long *, (n_surv + 1) * 8);
-    PROT_ALLOC(d_u1, unsigned long long *, (n_surv + 1) * 8);
-    PROT_ALLOC(d_u2, unsigned long long *, (n_surv + 1) * 8);
-    PROT_ALLOC(d_flag, int32_t *, n_surv * 4);
-    PROT_ALLOC(d_pos, int64_t *, (n_surv + 1) * 8);
-    PROT_ALLOC(d_bs2, int64_t *, scan_tmp_elems(n_surv) * 8);
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(n_surv + 1), &d_idx, &d_g1, &d_g2, &d_u1, &d_u2));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)n_surv, &d_flag));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(n_surv + 1), &d_pos));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)scan_tmp_elems(n_surv), &d_bs2));
     Sorter S;
-    tl_sort_arena = &L->arena;
-    rc = sorter_init(S, ctx, st, n_surv);
-    tl_sort_arena = nullptr;
-    if (rc) return rc;
+    HITE_TRY(sorter_init_in(S, ctx, &L->arena, st, n_surv));
     const unsigned gs = prot_grid(n_surv, 256);
     int fbits = 1;
     while (((int64_t)1 << fbits) < NF) fbits++;
@@ -718,8 +698,8 @@ static int prot_search(hite_ctx *ctx, ProtLib *L, int64_t nq, const uint8_t *nt,
     for (ProtTask &t : tasks) t.smin = smin[t.gf / 6];
     if (stats) stats[2] += n_tasks;
     ProtTask *d_tasks; int32_t *d_res;
-    PROT_ALLOC(d_tasks, ProtTask *, n_tasks * sizeof(ProtTask));
-    PROT_ALLOC(d_res, int32_t *, n_tasks * 32);
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)n_tasks, &d_tasks));
+    HITE_TRY(arena_get(ctx, L->arena, (size_t)(n_tasks * 8), &d_res));
     HITE_CHECK(ctx, hipMemcpy(d_tasks, tasks.data(), (size_t)n_tasks * sizeof(ProtTask), hipMemcpyHostToDevice));
     tk = hite_prof_begin(ctx, "prot_gapped_kernel", st);
     hipLaunchKernelGGL(prot_gapped_kernel, dim3(prot_grid(n_tasks, PROT_WAVES)), dim3(PROT_WAVES * 64), 0, st, d_tasks, n_tasks, d_fr, d_foff,

@@ -295,24 +295,27 @@ static inline int64_t sorter_hist_elems(int64_t n) {
     return a > b ? a : b;
 }
 
-static int sorter_init(Sorter &S, hite_ctx *ctx, hipStream_t st, int64_t n) {
-    S.ctx = ctx; S.st = st; S.cap = n;
+// the sorter's buffers from an arena (with_vals false: a keys-only sorter).  Sets no kernel attribute: see sorter_init_in
+static int sorter_from_arena(Sorter &S, hite_ctx *ctx, Arena &A, hipStream_t st, int64_t n, bool with_vals = true) {
+    S.ctx = ctx; S.st = st; S.cap = n; S.owned = false;
+    S.hist_n = sorter_hist_elems(n);
+    HITE_TRY(arena_get(ctx, A, (size_t)(n + 1), &S.k2));
+    S.v2 = nullptr;
+    if (with_vals) HITE_TRY(arena_get(ctx, A, (size_t)(n + 1), &S.v2));
+    HITE_TRY(arena_get(ctx, A, (size_t)S.hist_n, &S.hist));
+    HITE_TRY(arena_get(ctx, A, (size_t)(S.hist_n + 1), &S.offs));
+    HITE_TRY(arena_get(ctx, A, (size_t)sorter_tmp_elems(S.hist_n), &S.bs));
+    return HITE_OK;
+}
+// the staged scatter kernels' LDS attribute, then the buffers: from `arena` if there is one, else by hipMalloc (sorter_free)
+static int sorter_init_in(Sorter &S, hite_ctx *ctx, Arena *arena, hipStream_t st, int64_t n) {
     HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rs_scatter_staged_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         RSS_LDS_BYTES));
     HITE_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rs_scatter_staged_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         RSS_KLDS_BYTES));
+    if (arena) return sorter_from_arena(S, ctx, *arena, st, n);
+    S.ctx = ctx; S.st = st; S.cap = n;
     S.hist_n = sorter_hist_elems(n);
-    if (tl_sort_arena) {
-        void *p;
-        S.owned = false;
-        int rc;
-        if ((rc = arena_alloc(ctx, *tl_sort_arena, (size_t)(n + 1) * 8, &p))) return rc; S.k2 = (unsigned long long *)p;
-        if ((rc = arena_alloc(ctx, *tl_sort_arena, (size_t)(n + 1) * 4, &p))) return rc; S.v2 = (unsigned *)p;
-        if ((rc = arena_alloc(ctx, *tl_sort_arena, (size_t)S.hist_n * sizeof(rs_cnt_t), &p))) return rc; S.hist = (rs_cnt_t *)p;
-        if ((rc = arena_alloc(ctx, *tl_sort_arena, (size_t)(S.hist_n + 1) * sizeof(rs_off_t), &p))) return rc; S.offs = (rs_off_t *)p;
-        if ((rc = arena_alloc(ctx, *tl_sort_arena, (size_t)sorter_tmp_elems(S.hist_n) * 8, &p))) return rc; S.bs = (int64_t *)p;
-        return HITE_OK;
-    }
     HITE_CHECK(ctx, hipMalloc((void **)&S.k2, (size_t)(n + 1) * 8));
     HITE_CHECK(ctx, hipMalloc((void **)&S.v2, (size_t)(n + 1) * 4));
     HITE_CHECK(ctx, hipMalloc((void **)&S.hist, (size_t)S.hist_n * sizeof(rs_cnt_t)));
@@ -320,6 +323,7 @@ static int sorter_init(Sorter &S, hite_ctx *ctx, hipStream_t st, int64_t n) {
     HITE_CHECK(ctx, hipMalloc((void **)&S.bs, (size_t)sorter_tmp_elems(S.hist_n) * 8));
     return HITE_OK;
 }
+static int sorter_init(Sorter &S, hite_ctx *ctx, hipStream_t st, int64_t n) { return sorter_init_in(S, ctx, tl_sort_arena, st, n); }
 static void sorter_free(Sorter &S) {
     if (!S.owned) return;
     if (S.k2) (void)hipFree(S.k2);
